@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X-native ORB-SLAM3 matching (+ BA) hot path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: it sets up, warms up, times the K steps, writes
+the last step's outputs if --dump-outputs is given, and prints the result line.  Everything else listed under
+"Also reported" below needs --full.
 
 Headline (BASELINE.json metric "Mmatches/s (256-bit Hamming) + LocalBA iters/s"), workload
 configs[1]: brute-force 256-bit Hamming top-2 of 2000 x 2000 descriptors (C2).  One step = one
@@ -12,17 +16,22 @@ k_top2_mfma) with inputs resident in HBM; the one-problem launch
 independent frames (weak scaling; no collective in the data path); value = pairs of all ranks /
 max-over-ranks time.
 
-Also reported (same run):
-  * the dominant kernel's roofline (HIP events on its stream) and the C2' streaming kernel's HBM roofline
-    (Q = 4 x M = 2^24);
+Also reported (same run, with --full only):
+  * the one-problem launch (single_launch), its equality with frame 0 of the batch, and the headline kernel's
+    back-to-back time behind a spin kernel;
+  * the C2' streaming kernel's HBM roofline (Q = 4 x M = 2^24); the dominant kernel's roofline comes from HIP
+    events around the K timed steps themselves, so a plain run's line carries it too;
   * the CPU restatement timed on this host (cpu_baseline);
   * the frame-batched workloads: C3, C5, DBoW2 and ComputeStereoMatches, each valued at the C++ adapter's wall
     rate (tools/adapter_wall_bench.cpp: mock ORB-SLAM3 objects -> C-ABI -> write-back, as many host threads as
     the CPU baseline) with the batched launches' device-time rate beside it, and the ORB extractor stages;
   * LocalBA iterations/s on C4 (64-window batches, --lba-threads host threads);
   * global BA on 150 KeyFrames and on the 1500-KeyFrame map.
---only STAGE[,STAGE] runs a subset of those stages (A/B runs).
-stdout carries one compact JSON line (<= 8 KB, compact_line); the full record goes to --detail.
+--only STAGE[,STAGE] runs a subset of those stages (A/B runs; needs --full).
+stdout carries one compact JSON line (<= 8 KB, compact_line); with --full the full record goes to --detail.
+--dump-outputs DIR writes DIR/top2.npy (DIR/top2_rank<r>.npy for N > 1): the (frames x nq, 3) triples
+(best train row, best distance, second distance) the last timed step left, as float32 (every value is an
+integer below 2^24, so exact).  Inputs are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -82,6 +91,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the one-problem launch and its checks, the "
+                         "streaming roofline, the CPU baselines, the frame-batched, ORB and BA stages, and write "
+                         "the --detail record (minutes; a plain run times the headline alone)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (float32)")
     ap.add_argument("--ramp-s", type=float, default=0.5,
                     help="untimed launches of the headline step for this long before the warmup (GPU clock ramp)")
     ap.add_argument("--nq", type=int, default=2000)
@@ -124,8 +139,16 @@ def parse():
     ap.add_argument("--schur-pmc", default=os.path.join(ROOT, "profiles", "r06_lba_pmc.json"),
                     help="the LBA engine's SQ / MFMA / HBM counters (tools/pmc_kernel_summary.py)")
     ap.add_argument("--detail", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"),
-                    help="file for the full per-stage record (stdout carries the compact line); '' for none")
-    return ap.parse_args()
+                    help="with --full: file for the full per-stage record (stdout carries the compact line); "
+                         "'' for none")
+    args = ap.parse_args()
+    if not args.full:
+        if args.only:
+            ap.error("--only selects among the stages of --full")
+        # a plain run is the headline alone: no secondary stage, no CPU baseline, no detail record
+        args.no_cpu = args.no_stream = args.no_frames = args.no_ba = args.no_gba = True
+        args.detail = ""
+    return args
 
 
 def _spawn_ranks(n):
@@ -230,10 +253,14 @@ def main():
     pairs_per_step = B * nq * nt
     elapsed, total_pairs = job_totals(elapsed, pairs_per_step * args.steps, world, dist if world > 1 else None, dev)
     value = total_pairs / elapsed / 1e6
-    # frame 0 of the batch equals the single-problem launch (both are the serial loop's result)
-    step_single()
-    torch.cuda.synchronize(dev)
-    batch_frame0_equal = bool(torch.equal(doutb[:nq], dout))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"top2" if world == 1 else f"top2_rank{rank}": doutb.cpu().numpy()},
+                     DUMP_MAX_BYTES // world)
+    if args.full:
+        # frame 0 of the batch equals the single-problem launch (both are the serial loop's result)
+        step_single()
+        torch.cuda.synchronize(dev)
+        batch_frame0_equal = bool(torch.equal(doutb[:nq], dout))
 
     # ---- dominant kernel roofline: HIP events on the launch stream -------------------------
     # The kernel's average duration = (end - start) / n over n back-to-back launches between two
@@ -250,8 +277,9 @@ def main():
         torch.cuda.synchronize(dev)
         return e0.elapsed_time(e1) * 1e3 / n_ev
 
-    k_us_spin = kernel_us(step, max(20, min(args.steps, 100)))
-    k1_us = kernel_us(step_single, max(50, min(args.steps, 500)))
+    if args.full:
+        k_us_spin = kernel_us(step, max(20, min(args.steps, 100)))
+        k1_us = kernel_us(step_single, max(50, min(args.steps, 500)))
     k_us = k_us_loop
     alg_bytes = B * ((nq + nt) * 32 + nq * 12)
     # the kernel the batched entry launches, named by the library itself
@@ -312,23 +340,24 @@ def main():
         "traffic": None if tr is None else round(tr[0]),
         "traffic_source": None if tr is None else f"{os.path.relpath(args.traffic, ROOT)}: {tr[1]}",
         # kernel time = HIP events around the K timed steps on the launch stream (inside the wall-clock
-        # region, so <= ms_per_step); the back-to-back launches behind a spin kernel are reported beside it
+        # region, so <= ms_per_step); with --full the back-to-back launches behind a spin kernel are beside it
         "kernel_us": round(k_us, 3),
-        "kernel_us_backtoback_after_spin": round(k_us_spin, 3),
         "kernel_us_le_ms_per_step": bool(k_us <= elapsed / args.steps * 1e6 + 1e-6),
         "algorithmic_bytes_per_launch": alg_bytes,
         "hbm_frac_if_priced_as_hbm": round(alg_bytes / (k_us * 1e-6) / 1e9 / PEAK_HBM_GBS, 5),
     })
-    plan = ctx.hamming_top2_plan(nq, nt)
-    tr1 = pmc_traffic(args.traffic, plan.split(" ")[0].split("<")[0])
-    single = {
-        "kernel": plan, "kernel_us": round(k1_us, 3),
-        "Mmatches_per_s_kernel": round(nq * nt / (k1_us * 1e-6) / 1e6, 1),
-        "frac": round(nq * nt * VALU_OPS_PER_PAIR / (k1_us * 1e-6) / 1e12 / PEAK_VALU_GUIDE_TOPS, 4),
-        "frac_measured_16_lanes": round(nq * nt * VALU_OPS_PER_PAIR / (k1_us * 1e-6) / 1e12 / PEAK_VALU_TOPS, 4),
-        "traffic": None if tr1 is None else round(tr1[0]),
-        "note": "one 2000 x 2000 problem per launch (osg_hamming_top2_dev): the latency form",
-    }
+    if args.full:
+        roofline["kernel_us_backtoback_after_spin"] = round(k_us_spin, 3)
+        plan = ctx.hamming_top2_plan(nq, nt)
+        tr1 = pmc_traffic(args.traffic, plan.split(" ")[0].split("<")[0])
+        single = {
+            "kernel": plan, "kernel_us": round(k1_us, 3),
+            "Mmatches_per_s_kernel": round(nq * nt / (k1_us * 1e-6) / 1e6, 1),
+            "frac": round(nq * nt * VALU_OPS_PER_PAIR / (k1_us * 1e-6) / 1e12 / PEAK_VALU_GUIDE_TOPS, 4),
+            "frac_measured_16_lanes": round(nq * nt * VALU_OPS_PER_PAIR / (k1_us * 1e-6) / 1e12 / PEAK_VALU_TOPS, 4),
+            "traffic": None if tr1 is None else round(tr1[0]),
+            "note": "one 2000 x 2000 problem per launch (osg_hamming_top2_dev): the latency form",
+        }
 
     out = {
         "metric": "Mmatches/s (256-bit Hamming)",
@@ -350,9 +379,10 @@ def main():
                    "untimed_ramp_launches": ramp_n,
                    "parallelism": f"replicas x{world} (independent frames per GPU, no data-path collective)"},
         "roofline": roofline,
-        "single_launch": single,
-        "batch_frame0_equals_single": batch_frame0_equal,
     }
+    if args.full:
+        out["single_launch"] = single
+        out["batch_frame0_equals_single"] = batch_frame0_equal
 
     # ---- C2' streaming kernel: HBM roofline (Q = 4 x M = 2^24, 512 MiB > Infinity Cache) -----
     if not args.no_stream:
@@ -444,6 +474,23 @@ def main():
     ctx.close()
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_MAX_BYTES = 64_000_000    # --dump-outputs writes at most this much in all (every rank its share)
+
+
+def dump_outputs(directory, arrays, budget=DUMP_MAX_BYTES):
+    """Write each array as directory/<name>.npy in float32, at most `budget` bytes of files in all.  When
+    the arrays exceed it together, every array keeps a fixed, seeded sample of its rows (sorted, the same
+    from run to run) sized to its share."""
+    os.makedirs(directory, exist_ok=True)
+    budget -= 128 * len(arrays)  # the .npy headers
+    total = sum(a.size * 4 for a in arrays.values())
+    for name, a in arrays.items():
+        if total > budget:
+            keep = max(1, int(len(a) * (budget / total)))
+            a = a[np.sort(np.random.default_rng(0x0B5EED0D).choice(len(a), size=keep, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 _LINE_HEAD = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",

@@ -122,3 +122,40 @@ def test_batch_plan_tables_match_the_launchers():
         assert i8[k] == v, (k, v)
     for k, v in switch(fp4_sw, "launch_fp4").items():
         assert f4[k] == v, (k, v)
+
+
+def test_plain_run_is_the_headline_alone(monkeypatch):
+    """Without --full every secondary stage, the CPU baselines and the detail record are off; --only needs --full."""
+    import pytest
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs == ""
+    assert a.no_cpu and a.no_stream and a.no_frames and a.no_ba and a.no_gba and a.detail == ""
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d" and a.detail
+    assert not (a.no_cpu or a.no_stream or a.no_frames or a.no_ba or a.no_gba)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--only", "local_ba"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_dump_outputs_is_float32_exact_and_bounded(tmp_path):
+    """--dump-outputs: float32 .npy files that hold the int32 triples exactly; past the budget a seeded sample of
+    the rows, the same on every run, and never more bytes than the budget in all."""
+    import os
+    import numpy as np
+    rng = np.random.default_rng(5)
+    a = rng.integers(-1, 2000, size=(5000, 3), dtype=np.int32)
+    a[:, 0] = np.arange(len(a))  # a row names itself
+    bench.dump_outputs(str(tmp_path / "all"), {"top2": a})
+    got = np.load(tmp_path / "all" / "top2.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, a)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), {"top2": a, "other": a[:100]}, budget=20000)
+    size = sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1"))
+    assert size <= 20000
+    s1, s2 = np.load(tmp_path / "s1" / "top2.npy"), np.load(tmp_path / "s2" / "top2.npy")
+    assert 1000 < len(s1) < len(a) and np.array_equal(s1, s2)
+    ids = s1[:, 0].astype(np.int64)
+    assert np.all(np.diff(ids) > 0) and np.array_equal(s1, a[ids])  # distinct rows of the array, in its order

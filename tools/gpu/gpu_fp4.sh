@@ -14,6 +14,6 @@ timeout -k 10 300 python -u -m pytest tests/test_top2_gpu.py -m gpu -q --timeout
 echo "pytest rc=$?" >> $OUT/pytest_top2.log
 ARGS="--no-frames --no-ba --no-gba --no-cpu --no-stream --steps 200 --warmup 20"
 for v in 0 1 0 1; do
-  OSG_TOP2_FP4=$v timeout -k 10 200 python bench.py $ARGS --detail $OUT/c2_fp4_$v.json >> $OUT/c2_fp4_$v.jsonl 2>> $OUT/bench.err || exit 1
+  OSG_TOP2_FP4=$v timeout -k 10 200 python bench.py --full $ARGS --detail $OUT/c2_fp4_$v.json >> $OUT/c2_fp4_$v.jsonl 2>> $OUT/bench.err || exit 1
 done
 echo "exit=0"

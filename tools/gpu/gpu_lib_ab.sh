@@ -11,7 +11,7 @@ mkdir -p $OUT
 cd $R
 for v in cur other cur other; do
   if [ $v = other ]; then export OSG_LIB_PATH=$OTHER; else unset OSG_LIB_PATH; fi
-  timeout -k 10 300 python3 bench.py --no-cpu --no-stream --steps 3 --warmup 1 --only $STAGES > $OUT/$v.json 2>> $OUT/err.log || exit 1
+  timeout -k 10 300 python3 bench.py --full --no-cpu --no-stream --steps 3 --warmup 1 --only $STAGES > $OUT/$v.json 2>> $OUT/err.log || exit 1
   python3 -c "
 import json; d=json.loads(open('$OUT/$v.json').read().strip().splitlines()[-1])
 for k in '$STAGES'.split(','):

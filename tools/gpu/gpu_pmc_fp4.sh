@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/${1:-pmcfp4}
 mkdir -p $OUT
 ARGS="--no-frames --no-ba --no-gba --no-cpu --no-stream"
 cd /tmp
-timeout -s KILL 200 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o fetch -- python3 $R/bench.py $ARGS --steps 20 --warmup 5 > $OUT/fetch.log 2>&1 &&
-timeout -s KILL 200 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/write -o write -- python3 $R/bench.py $ARGS --steps 20 --warmup 5 > $OUT/write.log 2>&1 &&
+timeout -s KILL 200 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o fetch -- python3 $R/bench.py --full $ARGS --steps 20 --warmup 5 > $OUT/fetch.log 2>&1 &&
+timeout -s KILL 200 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/write -o write -- python3 $R/bench.py --full $ARGS --steps 20 --warmup 5 > $OUT/write.log 2>&1 &&
 python3 $R/tools/pmc_traffic.py $(find $OUT/fetch -name '*counter_collection.csv' | head -1) $(find $OUT/write -name '*counter_collection.csv' | head -1) $OUT/pmc_traffic_fp4.json
 rc=$?; rm -rf $OUT/fetch $OUT/write; echo "exit=$rc"; exit $rc
