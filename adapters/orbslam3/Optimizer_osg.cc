@@ -1,6 +1,6 @@
 // Optimizer_osg.cc — drop-in bodies for Optimizer::PoseOptimization, the g2o part of
-// Optimizer::LocalBundleAdjustment (both overloads) and Optimizer::BundleAdjustment (global BA) on the
-// MI355X path (ORB-SLAM3 tree built with -DORB_SLAM3_OSG;
+// Optimizer::LocalBundleAdjustment (both overloads), Optimizer::BundleAdjustment (global BA) and
+// Optimizer::OptimizeSim3 on the MI355X path (ORB-SLAM3 tree built with -DORB_SLAM3_OSG;
 // see INTEGRATION.md).  Signatures: ref:include/Optimizer.h:54-90.
 #include "Optimizer.h"
 #include "osg_hooks_orbslam3.h"
@@ -52,6 +52,14 @@ void Optimizer::LocalBundleAdjustment(KeyFrame *pMainKF, std::vector<KeyFrame *>
     if (out.aborted) return;  // :5444-5446
     std::unique_lock<std::mutex> lock(pMainKF->GetMap()->mMutexMapUpdate);  // :5551
     osg_orbslam3::apply_merge_local_bundle_adjustment<OsgHooks>(out);
+}
+
+int Optimizer::OptimizeSim3(KeyFrame *pKF1, KeyFrame *pKF2, std::vector<MapPoint *> &vpMatches1, g2o::Sim3 &g2oS12,
+                            const float th2, const bool bFixScale, Eigen::Matrix<double, 7, 7> &mAcumHessian,
+                            const bool bAllPoints)
+{  // ref:src/Optimizer.cc:4213-4512 (LoopClosing's Sim3 refinement of a loop / merge candidate)
+    return osg_orbslam3::optimize_sim3<OsgHooks>(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale, mAcumHessian,
+                                                 bAllPoints);
 }
 
 }  // namespace ORB_SLAM3

@@ -7,6 +7,7 @@
 #include "Frame.h"
 #include "KeyFrame.h"
 #include "MapPoint.h"
+#include "Thirdparty/g2o/g2o/types/sim3.h"
 #include "osg_orbslam3.h"
 
 namespace ORB_SLAM3 {
@@ -266,6 +267,28 @@ struct OsgHooks {
     {
         return sim3_query(pKF, Scw, pMP, false, u, v, level);
     }
+    // OptimizeSim3, ref:src/Optimizer.cc:4232-4235, 4297-4307: P3Dc = Rcw * P3Dw + tcw in float, cast to double
+    static void cam_point(KeyFrame *pKF, MapPoint *pMP, double x[3])
+    {
+        const Eigen::Matrix3f Rcw = pKF->GetRotation();
+        const Eigen::Vector3f tcw = pKF->GetTranslation();
+        const Eigen::Vector3f P3Dw = pMP->GetWorldPos();
+        const Eigen::Vector3f P3Dc = Rcw * P3Dw + tcw;
+        const Eigen::Vector3d d = P3Dc.cast<double>();
+        x[0] = d.x(); x[1] = d.y(); x[2] = d.z();
+    }
+    static void sim3_get(const g2o::Sim3 &S, double q[4], double t[3], double &s)
+    {
+        const Eigen::Quaterniond &r = S.rotation();
+        q[0] = r.x(); q[1] = r.y(); q[2] = r.z(); q[3] = r.w();
+        for (int i = 0; i < 3; i++) t[i] = S.translation()[i];
+        s = S.scale();
+    }
+    static void sim3_set(g2o::Sim3 &S, const double q[4], const double t[3], double s)
+    {  // the estimate's own members: g2o::Sim3 never renormalises its quaternion
+        S = g2o::Sim3(Eigen::Quaterniond(q[3], q[0], q[1], q[2]), Eigen::Vector3d(t[0], t[1], t[2]), s);
+    }
+    static void zero_hessian(Eigen::Matrix<double, 7, 7> &H) { H = Eigen::MatrixXd::Zero(7, 7); }  // :4483
 };
 
 }  // namespace ORB_SLAM3

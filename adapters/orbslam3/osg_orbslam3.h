@@ -2011,6 +2011,139 @@ void apply_merge_local_bundle_adjustment(const MergeLbaOutcome<KeyFrameT, MapPoi
     for (const auto &mp : o.points) H::set_world_pos(mp.first, mp.second.data());
 }
 
+// ------------------------------------------------------------------------------- OptimizeSim3
+// Optimizer::OptimizeSim3 (ref:src/Optimizer.cc:4213-4512), LoopClosing's Sim3 refinement between two
+// KeyFrames.  Hooks:
+//   static void H::cam_point(KeyFrame*, MapPoint*, double x[3])   Rcw * GetWorldPos() + tcw evaluated in
+//                float as :4297-4307 does, cast to double
+//   static int  H::index_in_keyframe(MapPoint*, KeyFrame*)         get<0>(GetIndexInKeyFrame(pKF))
+//   static void H::sim3_get(const Sim3&, double q[4], double t[3], double& s)   g2o::Sim3 -> (x y z w), t, s
+//   static void H::sim3_set(Sim3&, const double q[4], const double t[3], double s)
+//   static void H::zero_hessian(Hessian&)                          mAcumHessian = MatrixXd::Zero(7, 7)
+//
+// Sim3Gather is the graph build of :4272-4425 as plain host code: the slot filter IN THE REFERENCE'S
+// ORDER (no match -> skip; both MapPoints there but one bad -> skip; no MapPoint in KeyFrame 1 -> no edges;
+// not observed in KeyFrame 2 and !bAllPoints -> skip; P3D2c(2) < 0 -> skip; P3D1c's depth is not tested),
+// the kept pairs in slot order, vnIndexEdge, and for a pair without a keypoint in KeyFrame 2 the float
+// (x/z, y/z) of P3D2c as obs2 with mvInvLevelSigma2[0] (:4389-4404; kpUn2's octave stays 0 because
+// mnTrackScaleLevel is passed as the KeyPoint's size).
+template <class H, class KeyFrameT, class MapPointT>
+struct Sim3Gather {
+    OSG_PINNED_STRUCT(Sim3Gather);
+    std::vector<double> p1c, p2c, obs1, obs2;
+    std::vector<float> w1, w2;
+    std::vector<size_t> vnIndexEdge;
+    std::vector<uint8_t> vbIsInKF2, state;
+    osg_sim3_problem p{};
+    Sim3Gather() = default;
+    void assign(KeyFrameT *pKF1, KeyFrameT *pKF2, const std::vector<MapPointT *> &vpMatches1, float th2, bool bFixScale,
+                bool bAllPoints)
+    {
+        p = osg_sim3_problem{};
+        for (auto *v : {&p1c, &p2c, &obs1, &obs2}) v->clear();
+        w1.clear();
+        w2.clear();
+        vnIndexEdge.clear();
+        vbIsInKF2.clear();
+        const int N = (int)vpMatches1.size();
+        const std::vector<MapPointT *> vpMapPoints1 = pKF1->GetMapPointMatches();
+        for (int i = 0; i < N; i++) {
+            if (!vpMatches1[i]) continue;
+            MapPointT *pMP1 = vpMapPoints1[i];
+            MapPointT *pMP2 = vpMatches1[i];
+            const int i2 = H::index_in_keyframe(pMP2, pKF2);
+            double P1[3], P2[3];
+            if (pMP1 && pMP2) {
+                if (!pMP1->isBad() && !pMP2->isBad()) {      // :4293-4311
+                    H::cam_point(pKF1, pMP1, P1);
+                    H::cam_point(pKF2, pMP2, P2);
+                } else {
+                    continue;                                // :4312-4316
+                }
+            } else {
+                continue;                                    // :4318-4337 a fixed vertex at most, no edges
+            }
+            if (i2 < 0 && !bAllPoints) continue;             // :4339-4343
+            if (P2[2] < 0) continue;                         // :4345-4349
+            const auto &kpUn1 = pKF1->mvKeysUn[i];
+            double o2[2];
+            float invSigmaSquare2;
+            if (i2 >= 0) {
+                const auto &kpUn2 = pKF2->mvKeysUn[i2];
+                o2[0] = kpUn2.pt.x;
+                o2[1] = kpUn2.pt.y;
+                invSigmaSquare2 = pKF2->mvInvLevelSigma2[kpUn2.octave];
+            } else {
+                const float invz = 1 / (float)P2[2];
+                o2[0] = (float)P2[0] * invz;
+                o2[1] = (float)P2[1] * invz;
+                invSigmaSquare2 = pKF2->mvInvLevelSigma2[0];
+            }
+            p1c.insert(p1c.end(), P1, P1 + 3);
+            p2c.insert(p2c.end(), P2, P2 + 3);
+            obs1.push_back(kpUn1.pt.x);
+            obs1.push_back(kpUn1.pt.y);
+            obs2.push_back(o2[0]);
+            obs2.push_back(o2[1]);
+            w1.push_back(pKF1->mvInvLevelSigma2[kpUn1.octave]);
+            w2.push_back(invSigmaSquare2);
+            vnIndexEdge.push_back((size_t)i);
+            vbIsInKF2.push_back(i2 >= 0 ? 1 : 0);
+        }
+        state.assign(vnIndexEdge.size(), 0);
+        p.fix_scale = bFixScale ? 1 : 0;
+        p.th2 = th2;
+        H::camera(*pKF1, false, p.cam1);
+        H::camera(*pKF2, false, p.cam2);
+        p.n_pairs = (int32_t)vnIndexEdge.size();
+        p.p1c = p1c.data();
+        p.p2c = p2c.data();
+        p.obs1 = obs1.data();
+        p.obs2 = obs2.data();
+        p.inv_sigma2_1 = w1.data();
+        p.inv_sigma2_2 = w2.data();
+    }
+};
+
+template <class H, class KeyFrameT, class MapPointT>
+void gather_optimize_sim3(Sim3Gather<H, KeyFrameT, MapPointT> &g, KeyFrameT *pKF1, KeyFrameT *pKF2,
+                          const std::vector<MapPointT *> &vpMatches1, float th2, bool bFixScale, bool bAllPoints)
+{
+    g.assign(pKF1, pKF2, vpMatches1, th2, bFixScale, bAllPoints);
+}
+
+// The write-back of :4445-4448, 4474-4475, 4483-4511: the matches of the pairs nulled by either
+// classification; on the early return (fewer than 10 survivors) nothing else, the reference's return 0
+// with g2oS12 and mAcumHessian untouched; otherwise mAcumHessian = 0, g2oS12 = estimate, return nIn.
+template <class H, class KeyFrameT, class MapPointT, class Sim3T, class HessianT>
+int apply_optimize_sim3(const Sim3Gather<H, KeyFrameT, MapPointT> &g, const osg_sim3_result &r,
+                        std::vector<MapPointT *> &vpMatches1, Sim3T &g2oS12, HessianT &mAcumHessian)
+{
+    for (size_t e = 0; e < g.vnIndexEdge.size(); e++)
+        if (g.state[e]) vpMatches1[g.vnIndexEdge[e]] = static_cast<MapPointT *>(nullptr);
+    if (r.early_return) return 0;
+    H::zero_hessian(mAcumHessian);
+    H::sim3_set(g2oS12, r.q, r.t, r.s);
+    return r.n_inliers;
+}
+
+// On an ABI error: 0 with vpMatches1, g2oS12 and mAcumHessian untouched (LoopClosing then drops the
+// candidate, as after the reference's early return).
+template <class H, class KeyFrameT, class MapPointT, class Sim3T, class HessianT>
+int optimize_sim3(KeyFrameT *pKF1, KeyFrameT *pKF2, std::vector<MapPointT *> &vpMatches1, Sim3T &g2oS12, float th2,
+                  bool bFixScale, HessianT &mAcumHessian, bool bAllPoints)
+{
+    osg_ctx *ctx = thread_ctx();
+    using G = Sim3Gather<H, KeyFrameT, MapPointT>;
+    G &g = gather_pool<G>(1)[0];
+    gather_optimize_sim3<H>(g, pKF1, pKF2, vpMatches1, th2, bFixScale, bAllPoints);
+    H::sim3_get(g2oS12, g.p.q, g.p.t, g.p.s);
+    osg_sim3_result r{};
+    r.pair_state = g.state.data();
+    if (call(ctx, "osg_optimize_sim3", [&] { return osg_optimize_sim3(ctx, &g.p, &r); }) < 0) return 0;
+    return apply_optimize_sim3<H>(g, r, vpMatches1, g2oS12, mAcumHessian);
+}
+
 // ------------------------------------------------------------------------------ batched forms
 // B independent problems gathered from the reference's objects, solved in one launch (the
 // osg_*_batch entry points: one workgroup or frame slice per problem), and written back exactly as

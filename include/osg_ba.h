@@ -69,6 +69,58 @@ int osg_pose_optimization(struct osg_ctx *ctx, const osg_pose_problem *p, osg_po
 int osg_pose_optimization_batch(struct osg_ctx *ctx, const osg_pose_problem *p, int32_t n,
                                 osg_pose_result *r);
 
+/* ---- OptimizeSim3 --------------------------------------------------------------------------
+ * Optimizer::OptimizeSim3 (ref:src/Optimizer.cc:4213-4512), LoopClosing's Sim3 refinement between two
+ * KeyFrames: one free g2o::Sim3 vertex S12, per kept match a pair of fixed camera-frame points and the
+ * two reprojection edges
+ *   e12 = obs1 - cam1.project(S12.map(p2c)),   e21 = obs2 - cam2.project(S12.inverse().map(p1c)),
+ * both Huber with delta = sqrt(th2) (a float).  The reference writes no Jacobians for these edges, so
+ * g2o differentiates them numerically (central differences, delta = 1e-9, through
+ * Sim3(update) * estimate); the kernel does the same, and the result is defined up to that
+ * differentiation noise: parity with the reference is tolerance-based.  The flow —
+ * optimize(5), pair classification on the last computed errors, the < 10 survivors early return,
+ * optimize(5 | 10) without Huber, the final classification — runs in one launch.
+ *
+ * The caller applies the reference's slot filter (ref:src/Optimizer.cc:4272-4350) and passes the kept
+ * pairs in slot order; a pair whose MapPoint is not observed in KeyFrame 2 carries the normalised
+ * (x/z, y/z) of p2c as obs2 and mvInvLevelSigma2[0], as the reference does (:4389-4404). */
+typedef struct osg_sim3_problem {
+    double q[4];              /* g2oS12 in: rotation (x, y, z, w) */
+    double t[3];              /*            translation */
+    double s;                 /*            scale */
+    int32_t fix_scale;        /* bFixScale */
+    float th2;                /* chi2 threshold; Huber delta = sqrt(th2) */
+    osg_camera cam1, cam2;    /* pKF1->mpCamera, pKF2->mpCamera (type and p[] are read) */
+    int32_t n_pairs;          /* nCorrespondences */
+    const double *p1c;        /* 3 per pair: R1w X1w + t1w computed in float, cast to double */
+    const double *p2c;        /* 3 per pair: R2w X2w + t2w computed in float, cast to double */
+    const double *obs1;       /* 2 per pair: kpUn1.pt */
+    const double *obs2;       /* 2 per pair: kpUn2.pt, or (x/z, y/z) of p2c when not in KeyFrame 2 */
+    const float *inv_sigma2_1; /* pKF1->mvInvLevelSigma2[kpUn1.octave] */
+    const float *inv_sigma2_2; /* pKF2->mvInvLevelSigma2[kpUn2.octave] */
+    int32_t max_iterations;   /* 0: the reference's optimize(5) and optimize(5 | 10); n > 0 caps both at n */
+} osg_sim3_problem;
+
+typedef struct osg_sim3_result {
+    double q[4], t[3], s;     /* g2oS12 out (the input when early_return) */
+    int32_t n_inliers;        /* the reference's return value (0 when early_return) */
+    uint8_t *pair_state;      /* n_pairs: 0 inlier, 1 nulled after the first optimize, 2 nulled by the final check */
+    int32_t n_bad_first;      /* nBad of the first classification */
+    int32_t lm_iterations[2]; /* solve() calls of the two optimize() */
+    int32_t lm_trials[2];     /* linear solves incl. rejected steps */
+    double chi2_final;        /* sum of both edges' e'Omega e over the pairs of state 0, at the returned Sim3 */
+    double *pair_chi2;        /* optional (NULL: not written), 2 per pair: (e12, e21) chi2 as read by the pair's
+                                 last classification */
+    int32_t early_return;     /* nCorrespondences - nBad < 10: Sim3 and mAcumHessian stay untouched */
+} osg_sim3_result;
+
+/* Returns n_inliers or a negative OSG_E_* code. */
+int osg_optimize_sim3(struct osg_ctx *ctx, const osg_sim3_problem *p, osg_sim3_result *r);
+/* n independent problems in one launch, one workgroup each (e.g. every loop / merge candidate of a
+ * KeyFrame at once).  Returns the summed n_inliers or a negative OSG_E_* code.  No reference
+ * counterpart. */
+int osg_optimize_sim3_batch(struct osg_ctx *ctx, const osg_sim3_problem *p, int32_t n, osg_sim3_result *r);
+
 /* ---- LocalBundleAdjustment ------------------------------------------------------------------
  * Vertices are given sorted by g2o vertex id (KeyFrames: mnId; MapPoints: mnId + maxKFid + 1),
  * which fixes the Hessian index order (ref:Thirdparty/g2o/g2o/core/sparse_optimizer.cpp:181-211,

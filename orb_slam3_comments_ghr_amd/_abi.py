@@ -149,6 +149,22 @@ class OsgPoseResult(C.Structure):
     ]
 
 
+class OsgSim3Problem(C.Structure):
+    _fields_ = [
+        ("q", f64 * 4), ("t", f64 * 3), ("s", f64), ("fix_scale", i32), ("th2", f32),
+        ("cam1", OsgCamera), ("cam2", OsgCamera), ("n_pairs", i32), ("p1c", P), ("p2c", P),
+        ("obs1", P), ("obs2", P), ("inv_sigma2_1", P), ("inv_sigma2_2", P), ("max_iterations", i32),
+    ]
+
+
+class OsgSim3Result(C.Structure):
+    _fields_ = [
+        ("q", f64 * 4), ("t", f64 * 3), ("s", f64), ("n_inliers", i32), ("pair_state", P),
+        ("n_bad_first", i32), ("lm_iterations", i32 * 2), ("lm_trials", i32 * 2), ("chi2_final", f64),
+        ("pair_chi2", P), ("early_return", i32),
+    ]
+
+
 class OsgBaGraph(C.Structure):
     _fields_ = [
         ("n_poses", i32), ("pose", P), ("pose_fixed", P), ("n_points", i32), ("point", P),
@@ -190,7 +206,7 @@ EXPORTS = [
     "osg_search_by_projection_kf_batch", "osg_search_by_bow_kf_f_batch", "osg_search_by_bow_kf_kf_batch",
     "osg_match_last_stats", "osg_ctx_last_kernel_ms", "osg_ctx_device_bytes", "osg_pose_optimization", "osg_pose_optimization_batch",
     "osg_local_bundle_adjustment", "osg_local_bundle_adjustment_batch", "osg_bundle_adjustment",
-    "osg_lba_kernel_times",
+    "osg_lba_kernel_times", "osg_optimize_sim3", "osg_optimize_sim3_batch",
     "osg_vocabulary_create", "osg_vocabulary_load_text", "osg_vocabulary_destroy", "osg_vocabulary_info",
     "osg_vocabulary_transform", "osg_vocabulary_transform_batch",
     "osg_fuse_search", "osg_fuse_search_batch", "osg_search_for_triangulation", "osg_search_for_triangulation_batch",
@@ -247,6 +263,8 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.osg_pose_optimization.argtypes = [vp, C.POINTER(OsgPoseProblem), C.POINTER(OsgPoseResult)]
     lib.osg_pose_optimization_batch.argtypes = [vp, C.POINTER(OsgPoseProblem), i32,
                                                 C.POINTER(OsgPoseResult)]
+    lib.osg_optimize_sim3.argtypes = [vp, C.POINTER(OsgSim3Problem), C.POINTER(OsgSim3Result)]
+    lib.osg_optimize_sim3_batch.argtypes = [vp, C.POINTER(OsgSim3Problem), i32, C.POINTER(OsgSim3Result)]
     lib.osg_local_bundle_adjustment.argtypes = [vp, C.POINTER(OsgBaGraph), C.POINTER(OsgBaResult),
                                                 vp]
     lib.osg_bundle_adjustment.argtypes = [vp, C.POINTER(OsgBaGraph), C.POINTER(OsgBaResult),

@@ -221,6 +221,72 @@ class BAResult:
     edge_chi2: np.ndarray | None = None   # e->chi2() of each edge's last computed error
 
 
+@dataclass
+class Sim3Problem:
+    """One ``Optimizer::OptimizeSim3`` call as the adapter gathers it (include/osg_ba.h): the kept
+    pairs in slot order, camera-frame points as float-valued doubles."""
+    q: np.ndarray             # 4 doubles, g2oS12 rotation (x, y, z, w)
+    t: np.ndarray             # 3 doubles
+    s: float
+    p1c: np.ndarray           # n x 3 double
+    p2c: np.ndarray           # n x 3 double
+    obs1: np.ndarray          # n x 2 double
+    obs2: np.ndarray          # n x 2 double (normalised x/z, y/z for a pair that is not in KeyFrame 2)
+    inv_sigma2_1: np.ndarray  # float32 per pair
+    inv_sigma2_2: np.ndarray  # float32 per pair
+    fix_scale: bool = False
+    th2: float = 10.0         # LoopClosing passes 10 (ref:src/LoopClosing.cc:740, 1075)
+    cam1: object = field(default_factory=pinhole_camera)
+    cam2: object = field(default_factory=pinhole_camera)
+    max_iterations: int = 0   # 0: optimize(5), optimize(5 | 10); n > 0 caps both
+    truth: tuple | None = None  # generator only: the (R, t, s) the observations were drawn from
+
+    def __post_init__(self):
+        self.q = np.ascontiguousarray(self.q, np.float64)
+        self.t = np.ascontiguousarray(self.t, np.float64)
+        self.p1c = np.ascontiguousarray(self.p1c, np.float64).reshape(-1, 3)
+        self.p2c = np.ascontiguousarray(self.p2c, np.float64).reshape(-1, 3)
+        self.obs1 = np.ascontiguousarray(self.obs1, np.float64).reshape(-1, 2)
+        self.obs2 = np.ascontiguousarray(self.obs2, np.float64).reshape(-1, 2)
+        self.inv_sigma2_1 = np.ascontiguousarray(self.inv_sigma2_1, np.float32)
+        self.inv_sigma2_2 = np.ascontiguousarray(self.inv_sigma2_2, np.float32)
+
+    @property
+    def n(self):
+        return len(self.p1c)
+
+    def struct(self):
+        st = _abi.OsgSim3Problem()
+        for i in range(4):
+            st.q[i] = float(self.q[i])
+        for i in range(3):
+            st.t[i] = float(self.t[i])
+        st.s = float(self.s)
+        st.fix_scale = int(bool(self.fix_scale))
+        st.th2 = float(self.th2)
+        st.cam1, st.cam2 = self.cam1, self.cam2
+        st.n_pairs = self.n
+        st.p1c, st.p2c, st.obs1, st.obs2 = _p(self.p1c), _p(self.p2c), _p(self.obs1), _p(self.obs2)
+        st.inv_sigma2_1, st.inv_sigma2_2 = _p(self.inv_sigma2_1), _p(self.inv_sigma2_2)
+        st.max_iterations = int(self.max_iterations)
+        return st
+
+
+@dataclass
+class Sim3Result:
+    q: np.ndarray
+    t: np.ndarray
+    s: float
+    n_inliers: int            # the reference's return value
+    pair_state: np.ndarray    # 0 inlier, 1 nulled after the first optimize, 2 nulled by the final check
+    n_bad_first: int
+    lm_iterations: tuple
+    lm_trials: tuple
+    chi2_final: float
+    pair_chi2: np.ndarray     # n x 2: (e12, e21) chi2 as read by the pair's last classification
+    early_return: bool
+
+
 def run_pose(fn, problems, handle=None):
     """Call a PoseOptimization entry point on problems: the batch API (handle given) or a
     per-problem function fn(problem_structs, result_structs)."""
@@ -265,6 +331,25 @@ class Optimizer:
         lib, h = self.ctx.lib, self.ctx.handle
         rc, out = run_pose(lib.osg_pose_optimization_batch, probs, handle=h)
         self.ctx.check(rc, "PoseOptimization")
+        return out[0] if single else out
+
+    def OptimizeSim3(self, problems):
+        """``Optimizer::OptimizeSim3`` (ref:src/Optimizer.cc:4213-4512) for one Sim3Problem or a list of
+        them (one launch, a workgroup per problem).  The caller nulls ``vpMatches1`` where ``pair_state``
+        is nonzero and takes the Sim3 unless ``early_return``."""
+        single = isinstance(problems, Sim3Problem)
+        probs = [problems] if single else list(problems)
+        nb = len(probs)
+        ps = (_abi.OsgSim3Problem * max(1, nb))(*[p.struct() for p in probs])
+        rs = (_abi.OsgSim3Result * max(1, nb))()
+        state = [np.zeros(p.n, np.uint8) for p in probs]
+        chi2 = [np.zeros((p.n, 2), np.float64) for p in probs]
+        for r, st, c in zip(rs, state, chi2):
+            r.pair_state, r.pair_chi2 = _p(st), _p(c)
+        self.ctx.check(self.ctx.lib.osg_optimize_sim3_batch(self.ctx.handle, ps, nb, rs), "OptimizeSim3")
+        out = [Sim3Result(np.array(list(r.q)), np.array(list(r.t)), float(r.s), r.n_inliers, st, r.n_bad_first,
+                          tuple(r.lm_iterations), tuple(r.lm_trials), r.chi2_final, c, bool(r.early_return))
+               for r, st, c in zip(rs, state, chi2)]
         return out[0] if single else out
 
     def LocalBundleAdjustment(self, G: BAGraph, stop_flag: np.ndarray | None = None) -> BAResult:
@@ -416,6 +501,73 @@ def synth_pose_problem(rng, n_edges=400, stereo_frac=0.6, outlier_frac=0.1, n_le
         obs = obs.astype(np.float32).astype(np.float64)
         kind = np.where(body, _abi.EDGE_BODY, kind).astype(np.int8)
     return PoseProblem(pose7(R0, t0), kind, Xw, obs, isig, cam=cam, cam2=cam2)
+
+
+def _project(cam, X):
+    """GeometricCamera::project of rows of X in float64 (generators only)."""
+    if cam.type == _abi.CAM_KB8:
+        u, v = kb8_project(cam, X)
+    else:
+        u = float(cam.p[0]) * X[:, 0] / X[:, 2] + float(cam.p[2])
+        v = float(cam.p[1]) * X[:, 1] / X[:, 2] + float(cam.p[3])
+    return np.stack([u, v], 1)
+
+
+def synth_sim3_problem(rng, n_pairs=100, outlier_frac=0.1, out_of_kf2_frac=0.0, fix_scale=False, cam1=None, cam2=None,
+                       n_levels=8, noise_px=1.0, noise_m=0.01, th2=10.0):
+    """One loop-closure Sim3 refinement as LoopClosing hands it to OptimizeSim3: points 2 .. 8 m in front
+    of KeyFrame 2, the true S12 a few degrees / decimetres / per cent away from identity (scale 1 when
+    ``fix_scale``), each KeyFrame's own MapPoint ``noise_m`` off the common point, pixel noise ``noise_px``
+    x 1.2^octave, gross outliers (+20 .. 50 px in one image), and an initial S12 0.5 deg / 2 cm / 1 % off.
+    ``out_of_kf2_frac`` of the pairs have no keypoint in KeyFrame 2: obs2 is the float (x/z, y/z) of p2c and
+    the weight mvInvLevelSigma2[0], as ref:src/Optimizer.cc:4389-4404 builds them.  Points and keypoints are
+    float-valued doubles, as the adapter gathers them."""
+    cam1 = cam1 or pinhole_camera()
+    cam2 = cam2 or pinhole_camera()
+    n = int(n_pairs)
+    if cam2.type == _abi.CAM_KB8:
+        th = rng.uniform(0.05, 0.9, n)
+        ps = rng.uniform(-np.pi, np.pi, n)
+        d = rng.uniform(2.0, 8.0, n)
+        P2 = np.stack([d * np.sin(th) * np.cos(ps), d * np.sin(th) * np.sin(ps), d * np.cos(th)], 1)
+    else:
+        u = rng.uniform(60, EUROC_W - 60, n)
+        v = rng.uniform(60, EUROC_H - 60, n)
+        z = rng.uniform(2.0, 8.0, n)
+        P2 = np.stack([(u - float(cam2.p[2])) / float(cam2.p[0]) * z, (v - float(cam2.p[3])) / float(cam2.p[1]) * z, z], 1)
+    R = small_rotation(rng, 3.0)
+    t = rng.normal(0, 0.15, 3)
+    s = 1.0 if fix_scale else float(rng.uniform(0.9, 1.1))
+    P1 = s * P2 @ R.T + t
+    isig = inv_level_sigma2(n_levels)
+    lev_p = np.array([1.2 ** -i for i in range(n_levels)])
+    lev_p /= lev_p.sum()
+    oct1 = rng.choice(n_levels, n, p=lev_p)
+    oct2 = rng.choice(n_levels, n, p=lev_p)
+    obs1 = _project(cam1, P1) + rng.normal(0, noise_px, (n, 2)) * (1.2 ** oct1)[:, None]
+    obs2 = _project(cam2, P2) + rng.normal(0, noise_px, (n, 2)) * (1.2 ** oct2)[:, None]
+    out = rng.random(n) < outlier_frac
+    side = rng.random(n) < 0.5
+    shift = rng.uniform(20, 50, (n, 2)) * rng.choice([-1, 1], (n, 2))
+    obs1[out & side] += shift[out & side]
+    obs2[out & ~side] += shift[out & ~side]
+    p1c = (P1 + rng.normal(0, noise_m, (n, 3))).astype(np.float32)
+    p2c = (P2 + rng.normal(0, noise_m, (n, 3))).astype(np.float32)
+    obs1 = obs1.astype(np.float32).astype(np.float64)
+    obs2 = obs2.astype(np.float32).astype(np.float64)
+    w1 = isig[oct1].copy()
+    w2 = isig[oct2].copy()
+    nokf2 = rng.random(n) < out_of_kf2_frac
+    if nokf2.any():
+        invz = np.float32(1) / p2c[nokf2, 2]
+        obs2[nokf2, 0] = (p2c[nokf2, 0] * invz).astype(np.float64)
+        obs2[nokf2, 1] = (p2c[nokf2, 1] * invz).astype(np.float64)
+        w2[nokf2] = isig[0]
+    R0 = small_rotation(rng, 0.5) @ R
+    t0 = t + rng.normal(0, 0.02, 3)
+    s0 = s if fix_scale else s * float(1 + rng.normal(0, 0.01))
+    return Sim3Problem(rot_to_quat(R0), t0, s0, p1c.astype(np.float64), p2c.astype(np.float64), obs1, obs2, w1, w2,
+                       fix_scale=bool(fix_scale), th2=th2, cam1=cam1, cam2=cam2, truth=(R, t, s))
 
 
 def synth_lba_graph(rng, n_kf=50, n_points=10000, k_range=(2, 8), n_fixed=2, stereo_frac=0.0,
