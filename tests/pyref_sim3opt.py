@@ -348,7 +348,7 @@ def _optimize(P, S, n_iter, robust, delta_f, fix_scale, flags):
             S_eval = S
             temp = robust_chi2(S)
             if not ok2:
-                temp = np.finfo(float).max
+                temp = float(np.finfo(float).max)  # a Python float: rho / scale overflows to -inf without a warning
             rho = current - temp
             scale = float(np.sum(x * (lam * x + b))) + 1e-3
             rho /= scale
@@ -431,10 +431,21 @@ def nudged(P, rng):
     return Q
 
 
-def spreads(base, reps):
+def pair_chi2_rel(got, base, th2):
+    """Largest |got - base| / max(|base|, th2) over all pairs and both columns of pair_chi2 (0 when empty).
+    A single residual is not stationary at the optimum, so this is orders of magnitude above the relative
+    deviation of their sum; th2 in the denominator keeps a near-zero chi2 from dominating."""
+    got, base = np.asarray(got, float), np.asarray(base, float)
+    if base.size == 0:
+        return 0.0
+    return float(np.max(np.abs(got - base) / np.maximum(np.abs(base), float(np.float32(th2)))))
+
+
+def spreads(base, reps, th2):
     """Largest deviation of the replicas from the base result, per compared quantity."""
     tn = max(np.linalg.norm(base.t), 1e-300)
     return {
+        "pair_chi2_rel": max([pair_chi2_rel(r.pair_chi2, base.pair_chi2, th2) for r in reps] + [0.0]),
         "chi2_rel": max([abs(r.chi2_final - base.chi2_final) / max(abs(base.chi2_final), 1e-300) for r in reps] + [0.0]),
         "rot_rad": max([rot_log_norm(r.R, base.R) for r in reps] + [0.0]),
         "t_rel": max([float(np.linalg.norm(r.t - base.t) / tn) for r in reps] + [0.0]),

@@ -7,6 +7,8 @@
 * csrc/sim3_common.h built as plain host code and compared with pyref.
 * the guard conditions of the fixtures (tests/sim3opt_fixtures.py) and the committed golden replay.
 """
+import copy
+import functools
 import json
 import os
 import shutil
@@ -205,13 +207,19 @@ def margins():
         return json.load(f)
 
 
+@functools.lru_cache(maxsize=None)
+def pyref(name, cap=0):
+    """pyref's result of a fixture, computed once for the tests of this module (read, never written)"""
+    return R.optimize_sim3(FX.build(name, cap))
+
+
 @pytest.mark.parametrize("cap", [0, 1])
 @pytest.mark.parametrize("name", list(FX.FIXTURES))
 def test_fixture_guard_conditions(name, cap):
     """Every classified chi2 of pyref and of the 16 nudged replicas lies outside th2 (1 +- 1e-3), and the
     discrete outcome is the same in all of them: the GPU comparison needs no exclusions."""
     P = FX.build(name, cap)
-    base = R.optimize_sim3(P)
+    base = pyref(name, cap)
     reps = [R.optimize_sim3(Q) for Q in FX.replicas(name, P)]
     margin, same = R.guard_report(P, base, reps)
     print(name, cap, "margin", margin, "state counts", np.bincount(base.pair_state, minlength=3))
@@ -219,18 +227,85 @@ def test_fixture_guard_conditions(name, cap):
     assert same
 
 
+QUANTITIES = ("chi2_rel", "rot_rad", "t_rel", "s_rel", "pair_chi2_rel")
+
+
 def test_margins_profile_covers_the_fixtures(margins):
     for mode in ("full", "cap1"):
         assert set(margins[mode]) == set(FX.FIXTURES)
         assert all(v["stable"] for v in margins[mode].values())
+        assert all(set(QUANTITIES) <= set(v) for v in margins[mode].values())
+
+
+def test_margins_profile_maxima_are_per_group(margins):
+    """full_max / cap1_max are maxima over the twelve original fixtures alone, every later group has its own:
+    a new fixture cannot widen the tolerance an older one is held to."""
+    assert len(FX.ORIGINAL) == 12 and set(margins["groups"]) == set(FX.GROUPS)
+    for mode in ("full", "cap1"):
+        for q in QUANTITIES:
+            assert margins[mode + "_max"][q] == max(margins[mode][k][q] for k in FX.ORIGINAL)
+            for g in FX.GROUPS:
+                members = [k for k, f in FX.FIXTURES.items() if f.group == g]
+                assert members and margins["groups"][g][mode + "_max"][q] == max(margins[mode][k][q] for k in members)
 
 
 def test_fixture_shapes():
     """What each size is there for."""
-    r = {k: R.optimize_sim3(FX.build(k)) for k in FX.FIXTURES}
+    r = {k: pyref(k) for k in FX.FIXTURES}
     assert all(r[k].early_return for k in ("m0_free", "m0_fixed", "m9_free", "m9_fixed"))
     assert all(not r[k].early_return and r[k].n_inliers >= 10 for k in FX.FIXTURES if not k.startswith(("m0", "m9")))
     assert r["m12_free"].n_bad_first > 0 and r["m70_free"].n_bad_first > 0  # the 10-iteration second pass
+    # second-classification outliers in pinhole fixtures whose pairs all lie in KeyFrame 2
+    pinhole = [k for k, f in FX.FIXTURES.items() if f.cam1[0] == f.cam2[0] == "pinhole" and f.out_of_kf2_frac == 0]
+    with_state2 = [k for k in pinhole if np.any(r[k].pair_state == 2)]
+    print("state-2 pairs:", {k: int(np.count_nonzero(r[k].pair_state == 2)) for k in with_state2})
+    assert len(with_state2) >= 3
+    # a th2 that is not a float, with a Huber delta^2 that is not th2
+    th2 = np.float32(FX.FIXTURES["m70_th599"].th2)
+    assert float(th2) != 5.99 and np.float32(float(np.sqrt(th2)) ** 2) != th2
+    # the chunk edges: one lane short of a chunk, a full chunk, one lane into the next; the same at two chunks
+    assert [FX.FIXTURES[k].n_pairs for k in FX.FIXTURES if FX.FIXTURES[k].group == "chunk_edges"] == [127, 128, 129, 256, 257]
+    # every solve fails: one iteration of ten trials per optimize(), nothing moves, nothing is nulled
+    z = r["m40_zero_w"]
+    assert z.lm_iterations == (1, 1) and z.lm_trials == (10, 10) and z.n_inliers == 40 and not z.pair_state.any()
+    assert z.chi2_final == 0.0
+    P = FX.build("m40_zero_w")
+    np.testing.assert_array_equal(z.R, R.quat_to_rot(P.q))
+    assert np.array_equal(z.t, P.t) and z.s == P.s
+    # bits 32 and 63 of the mask of nulled pairs are set on some lane, and so is a bit in between
+    assert FX.FIXTURES["m4097_fixed"].n_pairs == 32 * 128 + 1 and r["m4097_fixed"].pair_state[4096] == 1
+    s8 = r["m8192_free"].pair_state
+    assert FX.FIXTURES["m8192_free"].n_pairs == 64 * 128
+    assert np.any(s8[63 * 128:] == 1) and np.any(s8[32 * 128:63 * 128] == 1)
+    assert FX.FIXTURES["m4097_fixed"].fix_scale != FX.FIXTURES["m8192_free"].fix_scale
+    # about 10 % nulled in every chunk
+    assert all(np.any(s8[c * 128:(c + 1) * 128] == 1) for c in range(64))
+
+
+@pytest.mark.parametrize("name", FX.PINHOLE_CAMERA_PAIRS)
+def test_exchanged_cameras_change_the_classification(name):
+    """The fixtures with two different pinhole cameras discriminate: with cam1 and cam2 exchanged (edge 12
+    projected through cam2, edge 21 through cam1) pyref gives another pair_state, so a kernel or an adapter
+    that exchanges them cannot pass the GPU comparison."""
+    P = FX.build(name)
+    assert bytes(P.cam1) != bytes(P.cam2)
+    Q = copy.copy(P)
+    Q.cam1, Q.cam2 = P.cam2, P.cam1
+    a, b = pyref(name), R.optimize_sim3(Q)
+    print(name, "inliers", a.n_inliers, "exchanged", b.n_inliers, "early return", b.early_return)
+    assert not np.array_equal(a.pair_state, b.pair_state)
+    assert a.n_inliers >= 10 and b.n_inliers != a.n_inliers
+
+
+def test_pyref_is_blind_to_the_quaternion_sign():
+    """q and -q are the same rotation, and pyref holds it as a matrix: bit-identical results."""
+    P = FX.build("m70_free")
+    Q = copy.copy(P)
+    Q.q = -P.q
+    a, b = pyref("m70_free"), R.optimize_sim3(Q)
+    np.testing.assert_array_equal(a.R, b.R)
+    np.testing.assert_array_equal(a.pair_chi2, b.pair_chi2)
+    assert np.array_equal(a.t, b.t) and a.s == b.s and a.chi2_final == b.chi2_final and a.lm_trials == b.lm_trials
 
 
 def test_golden_replay():

@@ -1,6 +1,8 @@
 """GPU: osg_optimize_sim3 (csrc/sim3opt.hip) against tests/pyref_sim3opt.py on the fixtures of
-tests/sim3opt_fixtures.py (pair counts 0, 9, 12, 70, 150 with free and fixed scale, 20 % pairs outside
-KeyFrame 2, KannalaBrandt8 cameras).
+tests/sim3opt_fixtures.py: the twelve original ones (pair counts 0, 9, 12, 70, 150 with free and fixed scale,
+20 % pairs outside KeyFrame 2, KannalaBrandt8 cameras) and the later groups (two different cameras per
+problem, th2 = 5.99, the chunk edges 127 .. 257, the full 64-bit chunk mask at 4097 and 8192 pairs, a problem
+whose every solve fails).
 
 The reference differentiates these edges numerically, so the result is defined up to differentiation
 noise.  Against pyref:
@@ -9,17 +11,35 @@ noise.  Against pyref:
   * within tolerance: chi2_final (relative), the rotation (|log(Ra Rb^T)|), the translation (relative to
     |t|), the scale (relative).  The tolerance of a quantity is 10 x its largest spread in the 16-replica
     +-1 ulp nudge study of pyref (profiles/sim3opt_margins.json, written by tools/sim3opt_margins.py), or
-    the matching BA tolerance of DESIGN.md §5 (chi2 1e-9 relative, states 1e-6) where that is larger;
-  * printed, not asserted: LM iteration and trial counts (at convergence rho is differentiation noise).
+    the matching BA tolerance of DESIGN.md §5 (chi2 1e-9 relative, states 1e-6) where that is larger.  The
+    largest spread is taken over the fixture's own group: the twelve original fixtures (full_max /
+    cap1_max), or the later group the fixture belongs to (groups), so a new fixture never widens an older
+    one's tolerance;
+  * within tolerance, without a floor: every pair's (e12, e21) chi2 as its last classification read it,
+    |gpu - pyref| / max(|pyref|, th2) over all pairs and both columns, 10 x the group's largest spread of
+    the same quantity.  A single residual is not stationary at the optimum, so these spreads are orders of
+    magnitude above chi2_final's.  Measured largest spreads (uncapped / max_iterations = 1):
+    original 1.6e-6 / 3.3e-6, cameras 1.9e-6 / 2.6e-6, th2 1.0e-6 / 8.4e-7, chunk_edges 9.4e-7 / 1.1e-6,
+    full_mask 1.1e-8 / 2.2e-7, failed_solve 0 / 0 (every chi2 is exactly 0 there);
+  * printed, not asserted: LM iteration and trial counts (at convergence rho is differentiation noise),
+    except on the failed-solve fixture, where nothing depends on differentiation.
 The tight tests run the same problems with max_iterations = 1 against the nudge study at that cap.
+
+Measured on an MI355X: the 8192-pair call takes 5.0 ms of wall time and its test 0.06 s with pyref, the
+4097-pair call 3.1 ms and its test 0.04 s; at max_iterations = 1 the two tests take 0.02 s and 0.01 s; the
+whole module runs in 2.5 s.
 """
+import copy
+import ctypes
 import functools
 import json
 import os
+import time
 
 import numpy as np
 import pytest
 
+from orb_slam3_comments_ghr_amd import _abi
 from orb_slam3_comments_ghr_amd import optimizer as op
 from tests import pyref_sim3opt as R
 from tests import sim3opt_fixtures as FX
@@ -31,10 +51,15 @@ FLOOR = {"chi2_rel": 1e-9, "rot_rad": 1e-6, "t_rel": 1e-6, "s_rel": 1e-6}  # DES
 
 
 @functools.lru_cache(maxsize=None)
-def tolerances(cap):
+def tolerances(name, cap):
+    """10 x the largest nudge spread over the fixture's own group, or the floor where there is one"""
     with open(os.path.join(ROOT, "profiles", "sim3opt_margins.json")) as f:
-        m = json.load(f)["cap1_max" if cap else "full_max"]
-    return {q: max(10.0 * m[q], FLOOR[q]) for q in FLOOR}
+        m = json.load(f)
+    group = FX.FIXTURES[name].group
+    m = (m if group == "original" else m["groups"][group])["cap1_max" if cap else "full_max"]
+    tol = {q: max(10.0 * m[q], FLOOR[q]) for q in FLOOR}
+    tol["pair_chi2_rel"] = 10.0 * m["pair_chi2_rel"]
+    return tol
 
 
 @functools.lru_cache(maxsize=None)
@@ -45,6 +70,15 @@ def reference(name, cap):
 def rot_of(q):
     q = np.asarray(q, float)
     return R.quat_to_rot(q / np.linalg.norm(q))
+
+
+def differences(got, Rm, t, s, chi2_final, pair_chi2, th2):
+    """The compared quantities of a GPU result against (Rm, t, s, chi2_final, pair_chi2)."""
+    return {"chi2_rel": abs(got.chi2_final - chi2_final) / max(abs(chi2_final), 1e-300),
+            "rot_rad": R.rot_log_norm(rot_of(got.q), Rm),
+            "t_rel": float(np.linalg.norm(got.t - t) / max(np.linalg.norm(t), 1e-300)),
+            "s_rel": abs(got.s - s) / s,
+            "pair_chi2_rel": R.pair_chi2_rel(got.pair_chi2, pair_chi2, th2)}
 
 
 def compare(name, cap, P, got):
@@ -62,11 +96,9 @@ def compare(name, cap, P, got):
         np.testing.assert_array_equal(got.q, P.q)
         np.testing.assert_array_equal(got.t, P.t)
         assert got.s == P.s
-    tol = tolerances(cap)
-    d = {"chi2_rel": abs(got.chi2_final - ref.chi2_final) / max(abs(ref.chi2_final), 1e-300),
-         "rot_rad": R.rot_log_norm(rot_of(got.q), ref.R),
-         "t_rel": float(np.linalg.norm(got.t - ref.t) / max(np.linalg.norm(ref.t), 1e-300)),
-         "s_rel": abs(got.s - ref.s) / ref.s}
+    tol = tolerances(name, cap)
+    assert got.pair_chi2.shape == ref.pair_chi2.shape
+    d = differences(got, ref.R, ref.t, ref.s, ref.chi2_final, ref.pair_chi2, P.th2)
     print("   differences", d, "tolerances", tol)
     for q in tol:
         assert d[q] <= tol[q], (q, d[q], tol[q])
@@ -75,7 +107,10 @@ def compare(name, cap, P, got):
 @pytest.mark.parametrize("name", list(FX.FIXTURES))
 def test_optimize_sim3_matches_pyref(ctx, name):
     P = FX.build(name)
-    compare(name, 0, P, op.Optimizer(ctx).OptimizeSim3(P))
+    t0 = time.perf_counter()
+    got = op.Optimizer(ctx).OptimizeSim3(P)
+    print(f"{name}: {P.n} pairs, call {1e3 * (time.perf_counter() - t0):.2f} ms wall")
+    compare(name, 0, P, got)
 
 
 @pytest.mark.parametrize("name", list(FX.FIXTURES))
@@ -85,6 +120,43 @@ def test_optimize_sim3_one_iteration_matches_pyref(ctx, name):
     got = op.Optimizer(ctx).OptimizeSim3(P)
     assert got.lm_iterations[0] <= 1 and got.lm_iterations[1] <= 1
     compare(name, 1, P, got)
+
+
+@pytest.mark.parametrize("cap", [0, 1])
+def test_failed_solves_terminate_after_ten_trials(ctx, cap):
+    """All weights 0: H = 0 and lambda = 0, so every LDL^T meets a non-positive pivot, tempChi is DBL_MAX,
+    the estimate is popped, and the tenth trial terminates optimize().  Nothing here is differentiation
+    noise, so the counts and the bits are asserted."""
+    P = FX.build("m40_zero_w", cap)
+    got = op.Optimizer(ctx).OptimizeSim3(P)
+    compare("m40_zero_w", cap, P, got)
+    assert got.lm_iterations == (1, 1)
+    assert got.lm_trials == (10, 10)
+    np.testing.assert_array_equal(got.q, P.q)
+    np.testing.assert_array_equal(got.t, P.t)
+    assert got.s == P.s
+    assert got.n_inliers == P.n == 40 and got.n_bad_first == 0 and not got.early_return
+    assert not got.pair_state.any()
+    assert got.chi2_final == 0.0
+    assert not got.pair_chi2.any()
+
+
+def test_negated_quaternion_is_the_same_problem(ctx):
+    """-q is the same rotation (pyref, which holds a matrix, is bit-identical for both): the same discrete
+    outcome, and the Sim3 and chi2 within the fixture's tolerance of the un-negated GPU result and of pyref."""
+    opt = op.Optimizer(ctx)
+    P = FX.build("m70_free")
+    N = copy.copy(P)
+    N.q = -P.q
+    a, b = opt.OptimizeSim3(P), opt.OptimizeSim3(N)
+    compare("m70_free", 0, N, b)
+    np.testing.assert_array_equal(a.pair_state, b.pair_state)
+    assert (a.n_inliers, a.n_bad_first, a.early_return) == (b.n_inliers, b.n_bad_first, b.early_return)
+    tol = tolerances("m70_free", 0)
+    d = differences(b, rot_of(a.q), a.t, a.s, a.chi2_final, a.pair_chi2, P.th2)
+    print("   negated against un-negated", d)
+    for q in tol:
+        assert d[q] <= tol[q], (q, d[q], tol[q])
 
 
 def same(a, b):
@@ -105,6 +177,40 @@ def test_batch_equals_single_calls_bit_for_bit(ctx):
         compare(n, 0, P, b)
 
 
+def test_mixed_batch_equals_single_calls_bit_for_bit(ctx):
+    """One launch whose problems differ in fix_scale, camera model and parameters, th2, max_iterations and
+    size, with empty problems first and last: a workgroup that read any of these from another problem than
+    its own would differ from the single call."""
+    opt = op.Optimizer(ctx)
+    probs = [FX.build(n, cap) for n, cap in FX.MIXED_BATCH]
+    assert len({P.fix_scale for P in probs}) == 2 and len({float(P.th2) for P in probs}) == 2
+    assert len({P.cam1.type for P in probs}) == 2 and len({P.max_iterations for P in probs}) == 2
+    assert probs[0].n == 0 and probs[-1].n == 0
+    batch = opt.OptimizeSim3(probs)
+    assert len(batch) == len(probs)
+    for (n, cap), P, b in zip(FX.MIXED_BATCH, probs, batch):
+        assert same(opt.OptimizeSim3(P), b), (n, cap)
+        compare(n, cap, P, b)
+
+
+def test_wide_batch_equals_single_calls_bit_for_bit(ctx):
+    """300 problems, more workgroups than the device has compute units, cycling through every fixture of at
+    most 150 pairs, with an empty problem first, in the middle and last."""
+    opt = op.Optimizer(ctx)
+    names = [k for k, f in FX.FIXTURES.items() if 0 < f.n_pairs <= 150]
+    probs = {k: FX.build(k) for k in names + ["m0_free"]}
+    single = {k: opt.OptimizeSim3(P) for k, P in probs.items()}
+    order = [names[i % len(names)] for i in range(300)]
+    for i in (0, 150, 299):
+        order[i] = "m0_free"
+    assert len(names) >= 12 and set(order) == set(probs)
+    batch = opt.OptimizeSim3([probs[k] for k in order])
+    assert len(batch) == 300
+    wrong = [(i, k) for i, (k, b) in enumerate(zip(order, batch)) if not same(single[k], b)]
+    assert not wrong, wrong[:10]
+    assert any(single[k].n_inliers > 0 for k in names)
+
+
 def test_two_runs_are_bit_identical(ctx):
     opt = op.Optimizer(ctx)
     P = FX.build("m150_free")
@@ -117,3 +223,54 @@ def test_rejects_more_pairs_than_the_chunk_mask_holds(ctx):
     P = op.synth_sim3_problem(np.random.default_rng(1), 64 * 128 + 1, 0.0, 0.0, False)
     with pytest.raises(Exception):
         op.Optimizer(ctx).OptimizeSim3(P)
+
+
+def raw_call(ctx, P, nb=1, handle=True, with_chi2=True, with_state=True, **override):
+    """osg_optimize_sim3_batch through ctypes on one problem, with fields of the problem struct overridden:
+    (return code, pair_state, pair_chi2, result struct).  The arrays of P stay referenced by the caller."""
+    st = P.struct()
+    for k, v in override.items():
+        setattr(st, k, v)
+    ps = (_abi.OsgSim3Problem * 1)(st)
+    rs = (_abi.OsgSim3Result * 1)()
+    n = max(P.n, int(st.n_pairs), 0)
+    state, chi2 = np.full(n, 255, np.uint8), np.full((n, 2), -1.0)
+    rs[0].pair_state = state.ctypes.data if with_state else None
+    rs[0].pair_chi2 = chi2.ctypes.data if with_chi2 else None
+    rc = ctx.lib.osg_optimize_sim3_batch(ctx.handle if handle else None, ps, nb, rs)
+    return rc, state, chi2, rs[0]
+
+
+def test_rejected_arguments_leave_the_context_usable(ctx):
+    """Every argument check of osg_optimize_sim3_batch returns a negative code before anything is launched,
+    and a valid call on the same context afterwards gives bit-for-bit what it gave before."""
+    opt = op.Optimizer(ctx)
+    P = FX.build("m12_fixed")
+    before = opt.OptimizeSim3(P)
+    five = op.synth_sim3_problem(np.random.default_rng(5), 5, 0.0, 0.0, False)
+    cases = {"n_pairs = -1": raw_call(ctx, P, n_pairs=-1),
+             "th2 = 0": raw_call(ctx, P, th2=0.0),
+             "s = 0": raw_call(ctx, P, s=0.0),
+             "max_iterations = -1": raw_call(ctx, P, max_iterations=-1),
+             "null p1c": raw_call(ctx, five, p1c=None),
+             "null pair_state": raw_call(ctx, five, with_state=False),
+             "nb = -1": raw_call(ctx, P, nb=-1),
+             "null handle": raw_call(ctx, P, handle=False)}
+    for what, (rc, state, chi2, _) in cases.items():
+        assert rc < 0, what
+        assert np.all(state == 255) and np.all(chi2 == -1.0), what  # nothing was written
+    with pytest.raises(Exception):
+        bad = copy.copy(P)
+        bad.th2 = 0.0
+        opt.OptimizeSim3(bad)
+    assert five.n == 5 and raw_call(ctx, five)[0] >= 0  # the five-pair problem itself is valid
+    # an empty batch is no error
+    assert raw_call(ctx, P, nb=0)[0] == 0
+    assert opt.OptimizeSim3([]) == []
+    # pair_chi2 is optional
+    rc, state, chi2, r = raw_call(ctx, P, with_chi2=False)
+    assert rc == before.n_inliers and np.all(chi2 == -1.0)
+    np.testing.assert_array_equal(state, before.pair_state)
+    assert (list(r.q), list(r.t), r.s, r.chi2_final) == (list(before.q), list(before.t), before.s, before.chi2_final)
+    assert (r.n_inliers, r.n_bad_first, bool(r.early_return)) == (before.n_inliers, before.n_bad_first, before.early_return)
+    assert same(before, opt.OptimizeSim3(P))
