@@ -18,12 +18,10 @@
 //                 workgroup reduction; no per-edge contribution round trip through HBM), its edge
 //                 inputs from pose-major records (k_hp_rec, once per call)
 // Per LM trial:
-//   (k_schur_point per landmark: Dinv = (Hll + lambda I)^-1, Dinv b_l; only with OSG_SCHUR_POINT=1:
-//                 by default k_schur_rows and k_update form Dinv from Hll themselves)
-//   k_schur_rows   per row segment (pose i, 200 of its blocks): BD = Hpl Dinv staged in LDS, the
+//   k_schur_rows   per row segment (pose i, 200 of its blocks): BD = Hpl Dinv (Dinv = (Hll + lambda I)^-1
+//                 formed from Hll on the spot, here and in k_update) staged in LDS, the
 //                 segment's chunks of S_ij = sum_p BD_ip Hpl_jp^T on FP64 MFMA (v_mfma_f64_4x4x4f64,
-//                 one contribution per instruction; OSG_SCHUR_VALU=1: the VALU form) and its share
-//                 of b_schur
+//                 one contribution per instruction) and its share of b_schur
 //   k_schur_pairs  per pose pair: chunk partials summed in chunk order -> the dense reduced camera
 //                 matrix Hpp + lambda I - S, and b_schur
 //   k_chol_col x ceil(n/32), k_chol_back   left-looking blocked Cholesky (FP64 MFMA tile updates),
@@ -34,6 +32,13 @@
 //   k_step_reduce the step's scalars per graph (chi2 of trial and current, scale, lambda, pivot flag)
 // The host reads back 5 scalars per graph per trial and runs the accept / reject / lambda logic
 // exactly as the reference; push/pop is a swap of the current / trial estimate buffers.
+//
+// Environment switches (read once per process unless noted): OSG_LBA_HPL=1 stores Hpl whole instead of
+// the compact per-block factor (k_linearize<.., false>, k_schur_rows, k_update: the independent check of
+// the compact kernels); OSG_CHOL_DENSE=0 factors small systems by the column launches too;
+// OSG_LBA_MAP_MODE=1 (per call) builds every structure on the map path; OSG_LBA_PROFILE=1 / 2 prints
+// host timings / kernel phase stamps.  The A/B variants that lost their measurements are gone: DESIGN.md
+// §3.4 keeps the numbers.
 #include <algorithm>
 #include <cfloat>
 #include <chrono>
@@ -75,7 +80,7 @@ struct LbaCtl {
 struct LbaDev {
     // sizes
     int np, npt, ne, nhp, nhl, nblk, npairs, n_cams;
-    int n_graphs, xcd_map;        // the batch (the same in every graph's entry): LBA_GRAPH's mapping
+    int n_graphs;                 // the batch (the same in every graph's entry)
     // inputs
     const uint8_t *pose_fixed;
     const int32_t *e_pose, *e_point, *e_cam;
@@ -122,7 +127,7 @@ struct LbaDev {
     double *chunk_part;                  // 36 per chunk
     double *bs_part;                     // 6 per row segment: sum of Hpl Dinv b_l
     // launch extents of this graph (grids are sized for the largest graph of the batch)
-    int ge, gl, gll, gu, nblk_red;       // gll: k_linearize's landmark groups
+    int ge, gll, gu, nblk_red;           // gll: k_linearize's landmark groups
     double user_lambda;
     // state: estimate buffers A / B; ctl->sel says which one is current
     double *poseA, *poseB, *pointA, *pointB;
@@ -133,12 +138,7 @@ struct LbaDev {
     double *chi2o;                       // per edge chi2 of the last computed error (classification)
     double *err;                         // 3 per edge
     double *Hll, *bl, *Hpl, *Hpp, *bp;
-    // per landmark: Hll (3 x 3), b_l (3) and, compact, its position (lmX) at strides ls_h / ls_b / ls_x: three
-    // arrays (strides 9, 3, 3) by default; OSG_LBA_LREC=1 one 128-byte record per landmark (stride 16: Hll at
-    // 0, b_l at 9, X at 12), one line per landmark for the Schur staging's scattered reads but strided for
-    // the landmark-parallel kernels: k_schur_rows_c 5.99 against 5.95-6.04 ms, k_linearize 1.82 against
-    // 1.70 and k_update_c 1.50 against 1.29 ms per 14 launches (A/B runs, the same values)
-    int ls_h, ls_b, ls_x;
+    // per landmark: Hll (3 x 3), b_l (3) and, compact, its position (lmX): three arrays (strides 9, 3, 3)
     // the compact per-block factor (the default; OSG_LBA_HPL=1 stores Hpl whole): 6 doubles per block,
     // the symmetric M' = sum over the block's edges of J_point^T rho' W J_point (see z_rows), in Hpl's storage
     int compact;
@@ -146,8 +146,6 @@ struct LbaDev {
                                          // current estimate (k_pose_red, every linearisation)
     double *lmX;                         // per landmark: its current position (k_linearize, compact form):
                                          // one dependent load level less for the Schur staging
-    double *Dinv, *db;                   // k_schur_point's outputs (OSG_SCHUR_POINT=1 only)
-    int dinv_inline;                     // 1: k_schur_rows / k_update form Dinv from Hll themselves
     double *Hs, *bs, *x;
     double *Linv;                        // inverses of the 32x32 diagonal blocks of L, row-major per block row
     int npart;                           // partial slots per kind (>= ge, gu, gll + nhp)
@@ -169,7 +167,7 @@ struct LbaDev {
     // past CMAX, Hs holds only the envelope's lower 32 x 32 tiles: row block t keeps column blocks
     // blk_first[t] .. t, contiguous after env_off[t] tiles, each tile row-major; null: dense n x n
     const int32_t *env_off;
-    int chol_fused;                      // 0: column launches, 1: k_chol_dense, 2: k_chol_env (+ its own back solve)
+    int chol_fused;                      // 0: column launches, 1: k_chol_dense
     int *flag;                           // [0] cholesky ok
     unsigned long long *tstamp;          // phase timestamps (OSG_LBA_PROFILE=2), else null
 };
@@ -210,15 +208,9 @@ __device__ inline const double *cur_point(const LbaDev &D) { return D.ctl->sel ?
 __device__ inline double *new_pose(const LbaDev &D) { return D.ctl->sel ? D.poseA : D.poseB; }
 __device__ inline double *new_point(const LbaDev &D) { return D.ctl->sel ? D.pointA : D.pointB; }
 // One problem per workgroup row; a workgroup whose graph skips this kernel leaves at once.
-// With OSG_LBA_XCD=1, batches of >= 8 graphs run XCD-aware: grid (8 gx, ceil(B / 8)); workgroup (x, y) of the launch
-// goes to XCD x % 8 (dispatch is round-robin over the 8 XCDs in linear order and 8 gx is a multiple
-// of 8), so graph (x % 8) + 8 y runs on one XCD and its Hpl / Dinv / edge arrays stay in that XCD's
-// L2, while the chip works on 8 graphs at a time (their working set fits the MALL).  Measured slower
-// than the default grid (gx, B), which spreads each graph over the whole chip.
+// Grid (gx, B): each graph is spread over the whole chip.
 #define LBA_GRAPH(MODEBITS)                                                                      \
-    const bool xcd_map_ = Ds[0].xcd_map;                                                         \
-    const int by = xcd_map_ ? (int)(blockIdx.x & 7) + 8 * (int)blockIdx.y : (int)blockIdx.y;     \
-    const int bx = xcd_map_ ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;                          \
+    const int by = (int)blockIdx.y, bx = (int)blockIdx.x;                                        \
     (void)bx;                                                                                    \
     if (by >= Ds[0].n_graphs) return;                                                            \
     const LbaDev &D = Ds[by];                                                                    \
@@ -339,11 +331,10 @@ __device__ __forceinline__ void z_rows(const double *m, double x, double y, doub
 // The workgroup's max |diag Hll| goes to the computeLambdaInit partials.  The edges' pose parts
 // {Hpp upper 21, b_p 6} are not stored: k_pose_red recomputes them pose-major (27 doubles per edge
 // written and read back cost more HBM time than the recomputed Jacobian costs VALU time).
-// WPE: the minimum waves per SIMD the register allocation must allow (1: the compiler's choice, 146
-// VGPRs = 3 waves; 4: 128 VGPRs with a few spills, OSG_LIN_WPE=4)
+// The register allocation is left to the compiler (146 VGPRs = 3 waves per SIMD).
 // COMPACT (the default): a block's M' (its Hll terms, 6) instead of its Hpl (18)
-template <bool MULTI, int WPE = 1, bool COMPACT = false>
-__global__ __launch_bounds__(EB) __attribute__((amdgpu_waves_per_eu(WPE, 8))) void k_linearize(const LbaDev *__restrict__ Ds)
+template <bool MULTI, bool COMPACT>
+__global__ __launch_bounds__(EB) __attribute__((amdgpu_waves_per_eu(1, 8))) void k_linearize(const LbaDev *__restrict__ Ds)
 {
     LBA_GRAPH(M_LIN);
     if (bx >= max(D.gll, 1)) return;
@@ -437,12 +428,12 @@ __global__ __launch_bounds__(EB) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
         }
         if (COMPACT && owner) {
             const int p = D.hl_point[ol];
-            for (int k = 0; k < 3; k++) D.lmX[D.ls_x * (size_t)ol + k] = points[3 * (size_t)p + k];
+            for (int k = 0; k < 3; k++) D.lmX[3 * (size_t)ol + k] = points[3 * (size_t)p + k];
         }
         if (owner) {
             const double H[9] = {H6[0], H6[1], H6[2], H6[1], H6[3], H6[4], H6[2], H6[4], H6[5]};
-            for (int i = 0; i < 9; i++) D.Hll[D.ls_h * (size_t)ol + i] = H[i];
-            for (int i = 0; i < 3; i++) D.bl[D.ls_b * (size_t)ol + i] = bl3[i];
+            for (int i = 0; i < 9; i++) D.Hll[9 * (size_t)ol + i] = H[i];
+            for (int i = 0; i < 3; i++) D.bl[3 * (size_t)ol + i] = bl3[i];
             md = fmax(fabs(H[0]), fmax(fabs(H[4]), fabs(H[8])));
         }
     }
@@ -462,9 +453,7 @@ __global__ __launch_bounds__(EB) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
 // copy-engine blits per graph: 128 dispatches of ~5 us each for a 64-window batch, r05a trace)
 __global__ __launch_bounds__(EB) void k_init_state(const LbaDev *__restrict__ Ds)
 {
-    const bool xcd_map_ = Ds[0].xcd_map;
-    const int by = xcd_map_ ? (int)(blockIdx.x & 7) + 8 * (int)blockIdx.y : (int)blockIdx.y;
-    const int bx = xcd_map_ ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+    const int by = (int)blockIdx.y, bx = (int)blockIdx.x;
     if (by >= Ds[0].n_graphs) return;
     const LbaDev &D = Ds[by];
     const size_t i = (size_t)bx * EB + threadIdx.x, np7 = 7 * (size_t)D.np, npt3 = 3 * (size_t)D.npt;
@@ -477,9 +466,7 @@ __global__ __launch_bounds__(EB) void k_init_state(const LbaDev *__restrict__ Ds
 __global__ __launch_bounds__(EB) void k_hp_rec(const LbaDev *__restrict__ Ds)
 {
     // launched before the first step's control upload: no mode check
-    const bool xcd_map_ = Ds[0].xcd_map;
-    const int by = xcd_map_ ? (int)(blockIdx.x & 7) + 8 * (int)blockIdx.y : (int)blockIdx.y;
-    const int bx = xcd_map_ ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+    const int by = (int)blockIdx.y, bx = (int)blockIdx.x;
     if (by >= Ds[0].n_graphs) return;
     const LbaDev &D = Ds[by];
     const int q = bx * EB + threadIdx.x;
@@ -491,9 +478,8 @@ __global__ __launch_bounds__(EB) void k_hp_rec(const LbaDev *__restrict__ Ds)
     *(i4 *)(D.hp_rec + 4 * (size_t)q) = i4{e, D.e_point[e], meta, __float_as_int(D.e_isig2[e])};
 }
 
-// per free pose (one workgroup): Hpp (6x6) and b_p from its edges.  REC: the edge inputs from the
-// pose-major records (default); false: gathered through hp_e (OSG_POSE_RED_GATHER=1, A/B runs)
-template <bool REC>
+// per free pose (one workgroup): Hpp (6x6) and b_p from its edges, the edge inputs from the pose-major
+// records (k_hp_rec)
 __global__ __launch_bounds__(EB) __attribute__((amdgpu_waves_per_eu(3, 8))) void k_pose_red(const LbaDev *__restrict__ Ds)
 {
     LBA_GRAPH(M_LIN);
@@ -509,33 +495,19 @@ __global__ __launch_bounds__(EB) __attribute__((amdgpu_waves_per_eu(3, 8))) void
     const SE3 T = se3_from7(cur_pose(D) + 7 * (size_t)D.hp_pose[i]);
     const double *points = cur_point(D);
     typedef int i4 __attribute__((ext_vector_type(4)));
-    // REC: the thread's next record is loaded one edge ahead, so an edge waits for its point and error
+    // the thread's next record is loaded one edge ahead, so an edge waits for its point and error
     // (which the record indexes) but not for the record itself
     const int q_end = D.hp_e_start[i + 1];
     i4 rnext = i4{0, 0, 0, 0};
-    if (REC && D.hp_e_start[i] + (int)threadIdx.x < q_end)
+    if (D.hp_e_start[i] + (int)threadIdx.x < q_end)
         rnext = *(const GLOBAL i4 *)(gbl(D.hp_rec) + 4 * (size_t)(D.hp_e_start[i] + threadIdx.x));
     for (int q = D.hp_e_start[i] + threadIdx.x; q < q_end; q += EB) {
-        int e, k, cam, pt;
-        bool robust;
-        double w;
-        if (REC) {
-            const i4 r = rnext;
-            if (q + EB < q_end) rnext = *(const GLOBAL i4 *)(gbl(D.hp_rec) + 4 * (size_t)(q + EB));
-            e = r.x;
-            pt = r.y;
-            cam = r.z & 0xffff;
-            k = (int)(int8_t)((r.z >> 16) & 0xff);
-            robust = (r.z >> 24) & 1;
-            w = (double)__int_as_float(r.w);
-        } else {
-            e = D.hp_e[q];
-            k = D.e_kind[e];
-            cam = D.e_cam[e];
-            pt = D.e_point[e];
-            robust = !(D.e_robust && !D.e_robust[e]);
-            w = edge_w(D, e);
-        }
+        const i4 r = rnext;
+        if (q + EB < q_end) rnext = *(const GLOBAL i4 *)(gbl(D.hp_rec) + 4 * (size_t)(q + EB));
+        const int e = r.x, pt = r.y, cam = r.z & 0xffff;
+        const int k = (int)(int8_t)((r.z >> 16) & 0xff);
+        const bool robust = (r.z >> 24) & 1;
+        const double w = (double)__int_as_float(r.w);
         double Jp[3][6], Jx[3][3];
         edge_jacobians(k, true, D.cams[cam], T, points + 3 * (size_t)pt, Jp, Jx);
         const int dim = (k == OSG_EDGE_STEREO) ? 3 : 2;
@@ -626,32 +598,19 @@ __global__ void k_lambda_init(const LbaDev *__restrict__ Ds)
 // Dinv_l = (Hll_l + lambda I)^-1 and, with db, Dinv_l b_l (ref:Thirdparty/g2o/g2o/core/block_solver.hpp:
 // 381-395).  Formed where it is used (the BD staging of k_schur_rows, and k_update) instead of
 // written by a kernel of its own and read back: Hll is as many bytes as Dinv, so each reader's
-// traffic is unchanged, and k_schur_point's launch and its 107 MB per 64 C4 windows are gone.
+// traffic is unchanged, and that kernel's launch and its 107 MB per 64 C4 windows are saved.
 __device__ inline void landmark_dinv(const LbaDev &D, int l, double lambda, double *Di, double *db)
 {
     double Dm[9];
-    for (int i = 0; i < 9; i++) Dm[i] = D.Hll[D.ls_h * (size_t)l + i];
+    for (int i = 0; i < 9; i++) Dm[i] = D.Hll[9 * (size_t)l + i];
     Dm[0] += lambda;
     Dm[4] += lambda;
     Dm[8] += lambda;
     inv3(Dm, Di);
     if (db) {
-        const double *b = D.bl + D.ls_b * (size_t)l;
+        const double *b = D.bl + 3 * (size_t)l;
         for (int r = 0; r < 3; r++) db[r] = Di[3 * r] * b[0] + Di[3 * r + 1] * b[1] + Di[3 * r + 2] * b[2];
     }
-}
-
-// the separate per-landmark pass (OSG_SCHUR_POINT=1, A/B runs): bit-identical
-__global__ __launch_bounds__(EB) void k_schur_point(const LbaDev *__restrict__ Ds)
-{
-    LBA_GRAPH(M_ACT);
-    const double lambda = D.ctl->lambda;
-    const int l = bx * EB + threadIdx.x;
-    if (l >= D.nhl) return;
-    double Di[9], db[3];
-    landmark_dinv(D, l, lambda, Di, db);
-    for (int i = 0; i < 9; i++) D.Dinv[9 * (size_t)l + i] = Di[i];
-    for (int r = 0; r < 3; r++) D.db[3 * (size_t)l + r] = db[r];
 }
 
 // Schur accumulation S_ij = sum_p BD_ip Hpl_jp^T (BD = Hpl Dinv) over the (block_i, block_j)
@@ -663,16 +622,12 @@ __global__ __launch_bounds__(EB) void k_schur_point(const LbaDev *__restrict__ D
 // in the segment): BD_a from LDS, Hpl_b from HBM.  A block's BD is formed once per trial instead of
 // written to HBM and gathered again per contribution (the contribution count is sum_l k_l(k_l+1)/2
 // against the block count sum_l k_l).
-//   The product runs on FP64 MFMA by default (layout below, at the chunk loop).  The VALU form
-// (OSG_SCHUR_VALU=1, kept for A/B measurements: DESIGN.md §3.4) uses lane = (group g = lane >> 2,
-// quarter q = lane & 3); group g takes contributions g, g + 16, ... of the chunk; quarter q owns
-// rows 3 (q >> 1) .. + 2 and columns 3 (q & 1) .. + 2 of the 6x6 product (9 + 9 doubles loaded for
-// 27 FMAs), the 16 groups summed by a fixed xor butterfly.  Both are deterministic; k_schur_pairs
-// then sums a pair's chunks in chunk order.
+//   The product runs on FP64 MFMA (layout below, at the chunk loop), in a fixed order: deterministic;
+// k_schur_pairs then sums a pair's chunks in chunk order.  This kernel is the whole-Hpl form
+// (OSG_LBA_HPL=1); the default is k_schur_rows_c on the compact factor.
 constexpr int SCH = 64;
 constexpr int RS = 200;  // blocks per row segment: 200 x 18 doubles = 28 KiB of LDS
 constexpr int RT = 512;  // threads per row-segment workgroup
-template <bool VALU, bool DIRECT = false>
 __global__ __launch_bounds__(RT, 6) void k_schur_rows(const LbaDev *__restrict__ Ds)
 {
     LBA_GRAPH(M_ACT);
@@ -741,15 +696,11 @@ __global__ __launch_bounds__(RT, 6) void k_schur_rows(const LbaDev *__restrict__
             if (idx < GC * 9 && c < cnt) R[r] = *(const GLOBAL u4 *)(Hv + 18 * (size_t)bj + 2 * gq);
         }
     };
-    i4 dc = {0, 0, 0, 0}, dn = {0, 0, 0, 0};
+    i4 dc = desc(t), dn = desc(t + RT / 64);
     int my_rank = 0, my_b = 0, n_rank = 0, n_b = 0;
     u4 R[3];
-    if (!VALU) {
-        dc = desc(t);
-        dn = desc(t + RT / 64);
-        contrib(dc, my_rank, my_b);
-        contrib(dn, n_rank, n_b);
-    }
+    contrib(dc, my_rank, my_b);
+    contrib(dn, n_rank, n_b);
     double cf[6] = {0, 0, 0, 0, 0, 0};
     // two threads per block (rows 3h .. 3h + 2 each): half the staging registers per thread
     {
@@ -760,12 +711,7 @@ __global__ __launch_bounds__(RT, 6) void k_schur_rows(const LbaDev *__restrict__
             const int a = gbl(D.hp_b)[hb0 + rb + r];
             const int l = gbl(D.hp_b_lm)[hb0 + rb + r];
             double Di[9], db[3], B[9];
-            if (D.dinv_inline) {
-                landmark_dinv(D, l, lam, Di, db);
-            } else {
-                for (int k = 0; k < 9; k++) Di[k] = gbl(D.Dinv)[9 * (size_t)l + k];
-                for (int k = 0; k < 3; k++) db[k] = gbl(D.db)[3 * (size_t)l + k];
-            }
+            landmark_dinv(D, l, lam, Di, db);
             for (int k = 0; k < 9; k++) B[k] = gbl(D.Hpl)[18 * (size_t)a + 9 * h + k];
             double *BD = s_bd + 18 * r + 9 * h;
             for (int rr = 0; rr < 3; rr++) {
@@ -784,86 +730,6 @@ __global__ __launch_bounds__(RT, 6) void k_schur_rows(const LbaDev *__restrict__
         double t = 0.0;
         for (int w = 0; w < RT / 64; w++) t += s_cf[w][threadIdx.x];
         D.bs_part[6 * (size_t)rs + threadIdx.x] = t;
-    }
-    if (VALU) {
-        const int g = lane >> 2, q = lane & 3;
-        const int r0 = 3 * (q >> 1), c0 = 3 * (q & 1);
-        const double *__restrict__ Hv = D.Hpl;
-        for (int t = D.rs_chunk_start[rs] + wv; t < D.rs_chunk_start[rs + 1]; t += RT / 64) {
-            const int ch = D.rs_chunk[t];
-            const int q0 = D.chunk_start[ch], q1 = D.chunk_start[ch + 1];
-            double acc[9];
-#pragma unroll
-            for (int k = 0; k < 9; k++) acc[k] = 0.0;
-            for (int qq = q0 + g; qq < q1; qq += 16) {
-                const int rank = D.pair_rank[qq] - rb;
-                const int b = D.pair_b[qq];
-                const double *BD = s_bd + 18 * rank + 3 * r0;  // rows r0..r0+2 of BD_i (6x3)
-                const double *Bj = Hv + 18 * (size_t)b + 3 * c0;  // rows c0..c0+2 of Hpl_j (6x3)
-                double av[9], bv[9];
-#pragma unroll
-                for (int k = 0; k < 9; k++) {
-                    av[k] = BD[k];
-                    bv[k] = Bj[k];
-                }
-#pragma unroll
-                for (int r = 0; r < 3; r++)
-#pragma unroll
-                    for (int c = 0; c < 3; c++)
-                        acc[3 * r + c] += av[3 * r] * bv[3 * c] + av[3 * r + 1] * bv[3 * c + 1] + av[3 * r + 2] * bv[3 * c + 2];
-            }
-#pragma unroll
-            for (int off = 4; off < 64; off <<= 1)
-#pragma unroll
-                for (int k = 0; k < 9; k++) acc[k] += __shfl_xor(acc[k], off);
-            if (g == 0) {
-                double *out = D.chunk_part + 36 * (size_t)ch;
-#pragma unroll
-                for (int r = 0; r < 3; r++)
-#pragma unroll
-                    for (int c = 0; c < 3; c++) out[6 * (r0 + r) + c0 + c] = acc[3 * r + c];
-            }
-        }
-        return;
-    }
-    if (DIRECT) {
-        // OSG_SCHUR_DIRECT=1: every lane loads its own element of Hpl_j straight from global memory
-        // (no LDS staging, no wave barrier), 16 contributions' loads issued before their MFMAs; the
-        // same operands in the same order as below, so the same sums
-        for (; t < t1; t += RT / 64) {
-            const i4 d2 = desc(t + 2 * (RT / 64));
-            const int nq = dc.z;
-            double acc0 = 0.0, acc1 = 0.0;
-            int v = 0;
-            for (; v + GC <= nq; v += GC) {
-                double bv[GC];
-#pragma unroll
-                for (int w = 0; w < GC; w++) {
-                    const int bj = __builtin_amdgcn_readlane(my_b, v + w);
-                    bv[w] = Hv[18 * (size_t)bj + boff];
-                }
-#pragma unroll
-                for (int w = 0; w < GC; w += 2) {
-                    const int r0 = __builtin_amdgcn_readlane(my_rank, v + w);
-                    const int r1 = __builtin_amdgcn_readlane(my_rank, v + w + 1);
-                    acc0 = __builtin_amdgcn_mfma_f64_4x4x4f64(s_bd[a_m * r0 + aoff], bv[w], acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f64_4x4x4f64(s_bd[a_m * r1 + aoff], bv[w + 1], acc1, 0, 0, 0);
-                }
-            }
-            for (; v < nq; v++) {  // the tail one at a time, even / odd contributions as above
-                const int bj = __builtin_amdgcn_readlane(my_b, v), rk = __builtin_amdgcn_readlane(my_rank, v);
-                const double b1 = Hv[18 * (size_t)bj + boff];
-                if (v & 1) acc1 = __builtin_amdgcn_mfma_f64_4x4x4f64(s_bd[a_m * rk + aoff], b1, acc1, 0, 0, 0);
-                else acc0 = __builtin_amdgcn_mfma_f64_4x4x4f64(s_bd[a_m * rk + aoff], b1, acc0, 0, 0, 0);
-            }
-            if (orow < 6 && ocol < 6) D.chunk_part[36 * (size_t)dc.x + 6 * orow + ocol] = acc0 + acc1;
-            dc = dn;
-            my_rank = n_rank;
-            my_b = n_b;
-            dn = d2;
-            contrib(dn, n_rank, n_b);
-        }
-        return;
     }
     // The descriptors and contributions (rank, block) of the wave's first two chunks were issued
     // before the BD staging above, so their latency overlaps it.  In the loop the descriptor two
@@ -923,7 +789,7 @@ __global__ __launch_bounds__(RT, 6) void k_schur_rows(const LbaDev *__restrict__
 }
 
 // The Schur product on the compact per-block factor (the default; see z_rows).  The same row segments,
-// chunks, MFMA layout, group pipeline and accumulation order as k_schur_rows<false>; what changes is what
+// chunks, MFMA layout, group pipeline and accumulation order as k_schur_rows; what changes is what
 // a contribution reads (the partner block's M', 48 B, instead of its Hpl, 144 B) and that the products
 // are summed in the world frame, k_schur_pairs rotating each pose pair's sum once.
 //   * BD staging: BD' = Z_a Dinv with Z_a = [[X + c_i]x M'_a ; M'_a] (pose i's c, the landmark's X from
@@ -934,9 +800,8 @@ __global__ __launch_bounds__(RT, 6) void k_schur_rows(const LbaDev *__restrict__
 //     one group ahead, as the whole-Hpl form's granules) and, at the group, writes column k of
 //     [[X]x M' ; M'] (X from LDS, 6 FMA, no pose) into the wave's LDS tile: the transposed operand
 //     [-M'[X]x | M'] of the product.  A chunk's partial is [B | A] of the comment above z_rows.
-// PF = 2 (the default): the gathers two groups ahead, a group pair at a time (see the loop); PF = 1
-// (OSG_SCHUR_PF=1) one group ahead
-// WPE: the waves per SIMD the register allocation must allow (6: 80 VGPRs; 5: 92)
+// The gathers run two groups ahead, a group pair at a time (see the loop).  The register allocation allows
+// 6 waves per SIMD (80 VGPRs, no spills).
 #ifdef OSG_SR_PROF
 // profiling builds only (make SR_PROF=1): per workgroup of graph 0, wall-clock ticks (100 MHz) at the start,
 // after the BD staging and at each wave's end, the segment's chunk count and blocks, the XCC / CU it ran on
@@ -947,11 +812,7 @@ __device__ unsigned long long g_sr_prof[SR_PROF_N][13];
 #else
 #define SR_PROF_AT(slot)
 #endif
-// HOIST (OSG_SCHUR_HOIST=1, A/B): the first group's gathers are issued between the staging's index loads and
-// its block loads, so their latency overlaps the staging instead of following it (15 VGPRs spilled in the
-// staging for it; without it the kernel allocates 80 VGPRs with none)
-template <int PF = 1, int WPE = 6, bool HOIST = false>
-__global__ __launch_bounds__(RT, WPE) void k_schur_rows_c(const LbaDev *__restrict__ Ds)
+__global__ __launch_bounds__(RT, 6) void k_schur_rows_c(const LbaDev *__restrict__ Ds)
 {
     LBA_GRAPH(M_ACT);
     if (bx >= D.n_rs) return;
@@ -1004,16 +865,11 @@ __global__ __launch_bounds__(RT, WPE) void k_schur_rows_c(const LbaDev *__restri
         }
     };
     i4 dc = desc(t), dn = desc(t + RT / 64);
-    // PF == 4: the wave's chunks t + 8 k, one descriptor per lane (k < 64), loaded before the staging, so no
-    // chunk waits for its descriptor (desc() of the chunk two ahead waited at the top of every iteration)
-    const int nchw = t < t1 ? (t1 - t + RT / 64 - 1) / (RT / 64) : 0;
-    i4 dl = i4{0, 0, 0, 0};
-    if (PF == 4 && lane < nchw) dl = cd[t + (RT / 64) * lane];
     int my_rank = 0, my_b = 0, n_rank = 0, n_b = 0;
     contrib(dc, my_rank, my_b);
     contrib(dn, n_rank, n_b);
     double cf[6] = {0, 0, 0, 0, 0, 0};
-    double M0[3] = {0, 0, 0}, M1[3] = {0, 0, 0};  // PF >= 2: the gathers of the wave's first group pair
+    double M0[3] = {0, 0, 0}, M1[3] = {0, 0, 0};  // the gathers of the wave's first group pair
     static_assert(2 * RS <= RT, "one block per thread pair in the staging");
     {
         const double *ci = D.hp_Rt + RT_STRIDE * (size_t)pi + 12;  // pose i's c = R^T t
@@ -1024,13 +880,12 @@ __global__ __launch_bounds__(RT, WPE) void k_schur_rows_c(const LbaDev *__restri
         const int r = threadIdx.x >> 1;
         const int a = st ? gbl(D.hp_b)[hb0 + rb + r] : 0;
         const int l = st ? gbl(D.hp_b_lm)[hb0 + rb + r] : 0;
-        if (HOIST) load_col(0, dc.z, my_b, M0);
         if (st) {
             // this thread's half of Z_a first (rows 3h .. 3h + 2: [X + c_i]x M' for h = 0, M' for h = 1), so
             // that M' is dead before Dinv is formed (the whole Z beside Dinv spilled)
             double Zh[3][3];
-            const double X0 = gbl(D.lmX)[D.ls_x * (size_t)l], X1 = gbl(D.lmX)[D.ls_x * (size_t)l + 1],
-                         X2 = gbl(D.lmX)[D.ls_x * (size_t)l + 2];
+            const double X0 = gbl(D.lmX)[3 * (size_t)l], X1 = gbl(D.lmX)[3 * (size_t)l + 1],
+                         X2 = gbl(D.lmX)[3 * (size_t)l + 2];
             {
                 const GLOBAL double *mp = Mv + 6 * (size_t)a;
                 const double m00 = mp[0], m01 = mp[1], m02 = mp[2], m11 = mp[3], m12 = mp[4], m22 = mp[5];
@@ -1049,12 +904,7 @@ __global__ __launch_bounds__(RT, WPE) void k_schur_rows_c(const LbaDev *__restri
                 s_xw[3 * r + 2] = X2;
             }
             double Di[9], db[3];
-            if (D.dinv_inline) {
-                landmark_dinv(D, l, lam, Di, db);
-            } else {
-                for (int k = 0; k < 9; k++) Di[k] = gbl(D.Dinv)[9 * (size_t)l + k];
-                for (int k = 0; k < 3; k++) db[k] = gbl(D.db)[3 * (size_t)l + k];
-            }
+            landmark_dinv(D, l, lam, Di, db);
             double *BD = s_bd + 18 * r + 9 * h;
             for (int rr = 0; rr < 3; rr++) {
                 const double *B = Zh[rr];
@@ -1075,7 +925,6 @@ __global__ __launch_bounds__(RT, WPE) void k_schur_rows_c(const LbaDev *__restri
         for (int w = 0; w < RT / 64; w++) tt += s_cf[w][threadIdx.x];
         D.bs_part[6 * (size_t)rs + threadIdx.x] = tt;
     }
-    double Mc[3] = {0, 0, 0};
     // one group of GC contributions: its operand rows into the tile, then its MFMAs
     auto run_group = [&](int u, int cnt, const double (&Mg)[3], double &acc0, double &acc1) {
         {
@@ -1116,187 +965,34 @@ __global__ __launch_bounds__(RT, WPE) void k_schur_rows_c(const LbaDev *__restri
         }
         __builtin_amdgcn_wave_barrier();
     };
-    if (PF >= 2) {
-        // group pairs (u, u + GC) of a chunk: the next pair's gathers (the rest of this chunk, else the
-        // next chunk's first pair) are issued before this pair's first group, so 2 GC contributions'
-        // loads are in flight while a pair runs; the same products in the same order
-        if (!HOIST) load_col(0, dc.z, my_b, M0);
-        load_col(GC, dc.z - GC, my_b, M1);
-        // PF == 3: a chunk is mostly one group, so the chain descriptor -> (rank, block) -> M' spans
-        // iterations: descriptors are loaded four chunks ahead (raw, in VGPRs) and made uniform three
-        // ahead, and a chunk's (rank, block) loads then never wait on a descriptor of the same iteration
-        auto desc_raw = [&](int tt) -> i4 { return tt < t1 ? cd[tt] : i4{0, 0, 0, 0}; };
-        auto uni = [&](const i4 &d) -> i4 {
-            return i4{__builtin_amdgcn_readfirstlane(d.x), __builtin_amdgcn_readfirstlane(d.y),
-                      __builtin_amdgcn_readfirstlane(d.z), 0};
-        };
-        if (PF == 4) {
-            // the descriptors come from dl by readlane; the (rank, block) loads of chunk k + 2 are issued at
-            // the top of chunk k and hold raw values until its end (the "- rb" right after a load made it wait
-            // at once), so every load has a whole chunk to land
-            auto dsc = [&](int k) -> i4 {
-                if (k >= nchw) return i4{0, 0, 0, 0};
-                if (k < 64)
-                    return i4{__builtin_amdgcn_readlane(dl.x, k), __builtin_amdgcn_readlane(dl.y, k),
-                              __builtin_amdgcn_readlane(dl.z, k), 0};
-                return desc(t + (RT / 64) * k);  // past 64 chunks of one wave (rare): a direct load
-            };
-            // loads without branches: a load under a lane guard is skipped by a branch when no lane needs
-            // it, and across such branches the compiler cannot count the loads in flight, so it waits for
-            // all of them (vmcnt(0)); a clamped index keeps every load in the straight line
-            auto contrib_raw = [&](const i4 &d, int &mr, int &mb) {
-                const int qi = d.y + min(lane, max(d.z - 1, 0));
-                const int vr = gbl(D.pair_rank)[qi], vb = gbl(D.pair_b)[qi];
-                mr = lane < d.z ? vr : rb;
-                mb = lane < d.z ? vb : 0;
-            };
-            auto load_col_u = [&](int u0, int cnt, int mb, double (&Mc)[3]) {
-                const int bs = __shfl(mb, (u0 + rc) & 63);  // every lane takes part: bpermute reads
-                const int bj = (rl && rc < cnt) ? bs : 0;     // nothing from lanes outside EXEC
-                const GLOBAL double *src = Mv + 6 * (size_t)bj;
-                Mc[0] = src[mo0];
-                Mc[1] = src[mo1];
-                Mc[2] = src[mo2];
-            };
-            int nrr = n_rank + rb;  // chunk k + 1's raw rank (n_rank came through contrib)
-            // one chunk: dcur's contributions in (my_rank, my_b); the next chunk's in (nrr, n_b)
-            auto chunk = [&](int k, int &la, int &lb) {
-                const i4 dcur = dsc(k), dnext = dsc(k + 1), dnn = dsc(k + 2);
-                contrib_raw(dnn, la, lb);
-                const int nq = dcur.z;
-                double acc0 = 0.0, acc1 = 0.0;
-                for (int u = 0; u < nq; u += 2 * GC) {
-                    double N0[3], N1[3];
-                    const bool inner = u + 2 * GC < nq;
-                    const int u2 = inner ? u + 2 * GC : 0, c2 = inner ? nq - u - 2 * GC : dnext.z;
-                    const int mbn = inner ? my_b : n_b;
-                    load_col_u(u2, c2, mbn, N0);
-                    load_col_u(u2 + GC, c2 - GC, mbn, N1);
-                    run_group(u, min(GC, nq - u), M0, acc0, acc1);
-                    if (u + GC < nq) run_group(u + GC, min(GC, nq - u - GC), M1, acc0, acc1);
-#pragma unroll
-                    for (int q = 0; q < 3; q++) {
-                        M0[q] = N0[q];
-                        M1[q] = N1[q];
-                    }
-                }
-                if (orow < 6 && ocol < 6) D.chunk_part[36 * (size_t)dcur.x + 6 * orow + ocol] = acc0 + acc1;
-                my_rank = nrr - rb;
-                my_b = n_b;
-            };
-            for (int k = 0; k < nchw; k++) {
-                int la = rb, lb = 0;
-                chunk(k, la, lb);  // chunk k + 2's loads into (la, lb) at its top
-                nrr = la;          // ... the next chunk's "next"
-                n_b = lb;
-            }
-#ifdef OSG_SR_PROF
-            SR_PROF_AT(2 + wv);
-#endif
-            return;
-        }
-        i4 dn2 = PF == 3 ? desc(t + 2 * (RT / 64)) : i4{0, 0, 0, 0};
-        i4 raw1 = PF == 3 ? desc_raw(t + 3 * (RT / 64)) : i4{0, 0, 0, 0};
-        for (; t < t1; t += RT / 64) {
-            const i4 d2 = PF == 3 ? i4{0, 0, 0, 0} : desc(t + 2 * (RT / 64));
-            const i4 raw0 = PF == 3 ? desc_raw(t + 4 * (RT / 64)) : i4{0, 0, 0, 0};
-            const int nq = dc.z;
-            double acc0 = 0.0, acc1 = 0.0;
-            for (int u = 0; u < nq; u += 2 * GC) {
-                // the next pair's gathers land in N0 / N1 and move into M0 / M1 after this pair's groups: a
-                // copy at the top (the loop-carried registers reused by the new loads) waited for the last
-                // pair's gathers before the next ones were even issued
-                double N0[3] = {0, 0, 0}, N1[3] = {0, 0, 0};
-                if (u + 2 * GC < nq) {
-                    load_col(u + 2 * GC, nq - u - 2 * GC, my_b, N0);
-                    load_col(u + 3 * GC, nq - u - 3 * GC, my_b, N1);
-                } else {
-                    load_col(0, dn.z, n_b, N0);
-                    load_col(GC, dn.z - GC, n_b, N1);
-                }
-                run_group(u, min(GC, nq - u), M0, acc0, acc1);
-                if (u + GC < nq) run_group(u + GC, min(GC, nq - u - GC), M1, acc0, acc1);
-#pragma unroll
-                for (int k = 0; k < 3; k++) {
-                    M0[k] = N0[k];
-                    M1[k] = N1[k];
-                }
-            }
-            if (orow < 6 && ocol < 6) D.chunk_part[36 * (size_t)dc.x + 6 * orow + ocol] = acc0 + acc1;
-            dc = dn;
-            my_rank = n_rank;
-            my_b = n_b;
-            if (PF == 3) {
-                dn = dn2;
-                dn2 = uni(raw1);
-                raw1 = raw0;
-            } else {
-                dn = d2;
-            }
-            contrib(dn, n_rank, n_b);
-        }
-#ifdef OSG_SR_PROF
-        SR_PROF_AT(2 + wv);
-        if (by == 0 && bx < SR_PROF_N && threadIdx.x == 0) {
-            g_sr_prof[bx][10] = (unsigned long long)(t1 - __builtin_amdgcn_readfirstlane(inf1.y));
-            g_sr_prof[bx][11] = (unsigned long long)nr;
-            // XCC_ID (hardware register 20, bits 0..3) and HW_ID (4) bits 8..15 (CU, SH, SE)
-            g_sr_prof[bx][12] = (unsigned long long)__builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) |
-                                ((unsigned long long)__builtin_amdgcn_s_getreg((7 << 11) | (8 << 6) | 4) << 32);
-        }
-#endif
-        return;
-    }
-    load_col(0, dc.z, my_b, Mc);
+    // group pairs (u, u + GC) of a chunk: the next pair's gathers (the rest of this chunk, else the
+    // next chunk's first pair) are issued before this pair's first group, so 2 GC contributions'
+    // loads are in flight while a pair runs
+    load_col(0, dc.z, my_b, M0);
+    load_col(GC, dc.z - GC, my_b, M1);
     for (; t < t1; t += RT / 64) {
         const i4 d2 = desc(t + 2 * (RT / 64));
         const int nq = dc.z;
         double acc0 = 0.0, acc1 = 0.0;
-        for (int u = 0; u < nq; u += GC) {
-            const int cnt = min(GC, nq - u);
-            {
-                // column rk of contribution u + rc's operand rows [[X]x M' ; M'] into the tile
-                const int rank = __shfl(my_rank, (u + rc) & 63);
-                const double x = s_xw[3 * rank], y = s_xw[3 * rank + 1], z = s_xw[3 * rank + 2];
-                if (rl && rc < cnt) {
-                    double *dst = hb + 18 * rc + rk;
-                    dst[0] = y * Mc[2] - z * Mc[1];
-                    dst[3] = z * Mc[0] - x * Mc[2];
-                    dst[6] = x * Mc[1] - y * Mc[0];
-                    dst[9] = Mc[0];
-                    dst[12] = Mc[1];
-                    dst[15] = Mc[2];
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
-            // next group: the rest of this chunk, else the first group of the next chunk
-            if (u + GC < nq) load_col(u + GC, nq - u - GC, my_b, Mc);
-            else load_col(0, dn.z, n_b, Mc);
-            if (cnt == GC) {
-#pragma unroll
-                for (int v = 0; v < GC; v += 2) {
-                    const int r0 = __builtin_amdgcn_readlane(my_rank, u + v);
-                    const int r1 = __builtin_amdgcn_readlane(my_rank, u + v + 1);
-                    acc0 = __builtin_amdgcn_mfma_f64_4x4x4f64(s_bd[a_m * r0 + aoff], hb[18 * v + boff], acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f64_4x4x4f64(s_bd[a_m * r1 + aoff], hb[18 * (v + 1) + boff], acc1, 0, 0,
-                                                              0);
-                }
+        for (int u = 0; u < nq; u += 2 * GC) {
+            // the next pair's gathers land in N0 / N1 and move into M0 / M1 after this pair's groups: a
+            // copy at the top (the loop-carried registers reused by the new loads) waited for the last
+            // pair's gathers before the next ones were even issued
+            double N0[3] = {0, 0, 0}, N1[3] = {0, 0, 0};
+            if (u + 2 * GC < nq) {
+                load_col(u + 2 * GC, nq - u - 2 * GC, my_b, N0);
+                load_col(u + 3 * GC, nq - u - 3 * GC, my_b, N1);
             } else {
-#pragma unroll
-                for (int v = 0; v < GC; v += 2) {
-                    if (v < cnt) {
-                        const int rank = __builtin_amdgcn_readlane(my_rank, u + v);
-                        acc0 = __builtin_amdgcn_mfma_f64_4x4x4f64(s_bd[a_m * rank + aoff], hb[18 * v + boff], acc0, 0, 0,
-                                                                  0);
-                    }
-                    if (v + 1 < cnt) {
-                        const int rank = __builtin_amdgcn_readlane(my_rank, u + v + 1);
-                        acc1 = __builtin_amdgcn_mfma_f64_4x4x4f64(s_bd[a_m * rank + aoff], hb[18 * (v + 1) + boff], acc1,
-                                                                  0, 0, 0);
-                    }
-                }
+                load_col(0, dn.z, n_b, N0);
+                load_col(GC, dn.z - GC, n_b, N1);
             }
-            __builtin_amdgcn_wave_barrier();
+            run_group(u, min(GC, nq - u), M0, acc0, acc1);
+            if (u + GC < nq) run_group(u + GC, min(GC, nq - u - GC), M1, acc0, acc1);
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                M0[k] = N0[k];
+                M1[k] = N1[k];
+            }
         }
         if (orow < 6 && ocol < 6) D.chunk_part[36 * (size_t)dc.x + 6 * orow + ocol] = acc0 + acc1;
         dc = dn;
@@ -1305,151 +1001,16 @@ __global__ __launch_bounds__(RT, WPE) void k_schur_rows_c(const LbaDev *__restri
         dn = d2;
         contrib(dn, n_rank, n_b);
     }
-}
-
-// The same product with the partner blocks staged (OSG_SCHUR_STAGE=1).  A row segment's contributions
-// (a, b) pair each of its blocks a (landmark l) with the blocks b >= a of l, and a landmark's blocks
-// are consecutive (numbered landmark-major, sorted by pose): the partners of rank r are the span
-// [a_r, end of l).  The workgroup copies every span of the segment into LDS once (contiguous global
-// reads, issued together), forms BD from the staged Hpl_a, and its 16 waves then run the chunk loop
-// on LDS operands only.  Slots past the LDS capacity (a segment whose landmarks are observed by
-// unusually many poses) read Hpl_b from global memory.  Same products, same accumulation order as
-// k_schur_rows<false>: the results are bit-identical.
-constexpr int RT2 = 1024;               // 16 waves: one workgroup per CU (its LDS)
-constexpr int SPAN_CAP = 880;           // staged blocks: 880 x 144 B = 124 KiB
-__global__ __launch_bounds__(RT2, 1) void k_schur_rows_st(const LbaDev *__restrict__ Ds)
-{
-    LBA_GRAPH(M_ACT);
-    if (bx >= D.n_rs) return;
-    typedef int i4 __attribute__((ext_vector_type(4)));
-    typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-    const i4 inf0 = ((const GLOBAL i4 *)gbl(D.rs_info))[2 * bx];
-    const i4 inf1 = ((const GLOBAL i4 *)gbl(D.rs_info))[2 * bx + 1];
-    const int rs = __builtin_amdgcn_readfirstlane(inf0.x);
-    const int rb = __builtin_amdgcn_readfirstlane(inf0.z), hb0 = __builtin_amdgcn_readfirstlane(inf0.w);
-    const int nr = __builtin_amdgcn_readfirstlane(inf1.x);
-    __shared__ __attribute__((aligned(16))) double s_span[SPAN_CAP * 18];
-    __shared__ double s_bd[RS * 18 + 2];
-    __shared__ int s_pre[RS + 1], s_a[RS];
-    __shared__ double s_cf[RT2 / 64][6];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const GLOBAL double *__restrict__ Hv = gbl(D.Hpl);
-    // 1. spans: first block and length per rank, exclusive prefix (wave 0: 4 ranks per lane)
-    if (wv == 0) {
-        int len[4], a4[4], tot = 0;
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int r = 4 * lane + u;
-            len[u] = 0;
-            a4[u] = 0;
-            if (r < nr) {
-                a4[u] = gbl(D.hp_b)[hb0 + rb + r];
-                const int l = gbl(D.hp_b_lm)[hb0 + rb + r];
-                len[u] = gbl(D.lm_b_start)[l + 1] - a4[u];
-            }
-            tot += len[u];
-        }
-        int inc = tot;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int v = __shfl_up(inc, off);
-            if (lane >= off) inc += v;
-        }
-        int run = inc - tot;
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int r = 4 * lane + u;
-            if (r < nr) {
-                s_pre[r] = run;
-                s_a[r] = a4[u];
-            }
-            run += len[u];
-        }
-        if (lane == 63) s_pre[nr] = inc;
-        if (threadIdx.x == 0) s_bd[RS * 18] = 0.0;
+#ifdef OSG_SR_PROF
+    SR_PROF_AT(2 + wv);
+    if (by == 0 && bx < SR_PROF_N && threadIdx.x == 0) {
+        g_sr_prof[bx][10] = (unsigned long long)(t1 - __builtin_amdgcn_readfirstlane(inf1.y));
+        g_sr_prof[bx][11] = (unsigned long long)nr;
+        // XCC_ID (hardware register 20, bits 0..3) and HW_ID (4) bits 8..15 (CU, SH, SE)
+        g_sr_prof[bx][12] = (unsigned long long)__builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) |
+                            ((unsigned long long)__builtin_amdgcn_s_getreg((7 << 11) | (8 << 6) | 4) << 32);
     }
-    __syncthreads();
-    // 2. stage the spans: wave w copies ranks w, w + 16, ...; a span is len x 9 16-byte granules,
-    // contiguous in global memory
-    for (int r = wv; r < nr; r += RT2 / 64) {
-        const int p0 = s_pre[r], n9 = 9 * (s_pre[r + 1] - p0), a = s_a[r];
-        for (int g = lane; g < n9; g += 64) {
-            const int slot = p0 + g / 9;
-            if (slot < SPAN_CAP)
-                *(u4 *)(s_span + 18 * (size_t)slot + 2 * (g % 9)) = *(const GLOBAL u4 *)(Hv + 18 * (size_t)a + 2 * g);
-        }
-    }
-    __syncthreads();
-    // 3. BD = Hpl_a Dinv_l into LDS with the segment's share of b_schur (as k_schur_rows)
-    double cf[6] = {0, 0, 0, 0, 0, 0};
-    {
-        const int h = threadIdx.x & 1;
-        double c3[3] = {0, 0, 0};
-        for (int r2 = threadIdx.x; r2 < 2 * nr; r2 += RT2) {
-            const int r = r2 >> 1;
-            const int l = gbl(D.hp_b_lm)[hb0 + rb + r];
-            const int p0 = s_pre[r];
-            double Di[9], db[3], B[9];
-            if (D.dinv_inline) {
-                landmark_dinv(D, l, D.ctl->lambda, Di, db);
-            } else {
-                for (int k = 0; k < 9; k++) Di[k] = gbl(D.Dinv)[9 * (size_t)l + k];
-                for (int k = 0; k < 3; k++) db[k] = gbl(D.db)[3 * (size_t)l + k];
-            }
-            if (p0 < SPAN_CAP)
-                for (int k = 0; k < 9; k++) B[k] = s_span[18 * (size_t)p0 + 9 * h + k];
-            else
-                for (int k = 0; k < 9; k++) B[k] = Hv[18 * (size_t)s_a[r] + 9 * h + k];
-            double *BD = s_bd + 18 * r + 9 * h;
-            for (int rr = 0; rr < 3; rr++) {
-                for (int c = 0; c < 3; c++)
-                    BD[3 * rr + c] = B[3 * rr] * Di[c] + B[3 * rr + 1] * Di[3 + c] + B[3 * rr + 2] * Di[6 + c];
-                c3[rr] += B[3 * rr] * db[0] + B[3 * rr + 1] * db[1] + B[3 * rr + 2] * db[2];
-            }
-        }
-        for (int k = 0; k < 6; k++) cf[k] = (k / 3 == h) ? c3[k % 3] : 0.0;
-    }
-    // the butterfly in the same lane order as k_schur_rows (RT = 512: waves 0..7 summed), then the
-    // 16 waves in order
-    for (int k = 0; k < 6; k++) cf[k] = wave_sum(cf[k]);
-    if (lane == 0)
-        for (int k = 0; k < 6; k++) s_cf[wv][k] = cf[k];
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        double t = 0.0;
-        for (int w = 0; w < RT2 / 64; w++) t += s_cf[w][threadIdx.x];
-        D.bs_part[6 * (size_t)rs + threadIdx.x] = t;
-    }
-    // 4. the chunks: per lane q (< count) the contribution's rank and its partner's slot
-    const int kk = lane >> 4, beta = (lane >> 2) & 3, ri = lane & 3;
-    const int arow = 4 * (beta >> 1) + ri, bcol = 4 * (beta & 1) + ri;
-    const int a_m = kk < 3 ? 18 : 0;
-    const int aoff = kk < 3 ? 3 * min(arow, 5) + kk : RS * 18;
-    const int boff = 3 * min(bcol, 5) + min(kk, 2);
-    const int orow = 4 * (beta >> 1) + kk, ocol = 4 * (beta & 1) + ri;
-    const int t1 = __builtin_amdgcn_readfirstlane(inf1.z);
-    const GLOBAL i4 *__restrict__ cd = (const GLOBAL i4 *)gbl(D.rs_cdesc);
-    for (int t = __builtin_amdgcn_readfirstlane(inf1.y) + wv; t < t1; t += RT2 / 64) {
-        const i4 d = cd[t];
-        const int ch = __builtin_amdgcn_readfirstlane(d.x), q0 = __builtin_amdgcn_readfirstlane(d.y);
-        const int nq = __builtin_amdgcn_readfirstlane(d.z);
-        int rank = 0, slot = 0, bblk = 0;
-        if (lane < nq) {
-            rank = gbl(D.pair_rank)[q0 + lane] - rb;
-            bblk = gbl(D.pair_b)[q0 + lane];
-            slot = s_pre[rank] + bblk - s_a[rank];
-        }
-        double acc0 = 0.0, acc1 = 0.0;
-        for (int v = 0; v < nq; v++) {
-            const int rk = __builtin_amdgcn_readlane(rank, v), sl = __builtin_amdgcn_readlane(slot, v);
-            const double av = s_bd[a_m * rk + aoff];
-            const double bv = sl < SPAN_CAP ? s_span[18 * sl + boff]
-                                            : Hv[18 * (size_t)__builtin_amdgcn_readlane(bblk, v) + boff];
-            if (v & 1) acc1 = __builtin_amdgcn_mfma_f64_4x4x4f64(av, bv, acc1, 0, 0, 0);
-            else acc0 = __builtin_amdgcn_mfma_f64_4x4x4f64(av, bv, acc0, 0, 0, 0);
-        }
-        if (orow < 6 && ocol < 6) D.chunk_part[36 * (size_t)ch + 6 * orow + ocol] = acc0 + acc1;
-    }
+#endif
 }
 
 __global__ __launch_bounds__(256) void k_schur_pairs(const LbaDev *__restrict__ Ds)
@@ -1766,13 +1327,13 @@ struct CholLds {
 //      m_c+1,m -= l10 m_c,m (m <= c): written one step later (other threads read row c + 1 now;
 //      nothing reads it in the next step).  Pivots go to s_d (the diagonal of G is read now).
 // An odd nb pairs its last column with padding column nb (identity: l10 = 0, d1 = 1).
-// GUARD: a workgroup of more than 256 threads (k_chol_dense), of which threads 0..255 eliminate and
+// Called by k_chol_dense's workgroup of more than 256 threads, of which threads 0..255 eliminate and
 // every thread takes the barriers.
-template <bool GUARD = false, class LDS>
+template <class LDS>
 __device__ __forceinline__ int chol_factor_diag(LDS &L, int nb)
 {
     const int tid = threadIdx.x;
-    const bool act = !GUARD || tid < 256;
+    const bool act = tid < 256;
     const int jj = tid & 31, ib = (tid >> 5) & 7;
     int ok = 1;
     double defer_val = 0.0;
@@ -1839,27 +1400,22 @@ __device__ __forceinline__ int chol_factor_diag(LDS &L, int nb)
     return ok;
 }
 
-// chol_factor_diag four columns per barrier (OSG_CHOL_ELIM=4): the 4 x 4 pivot block P = LP DP LP^T is
+// chol_factor_diag four columns per barrier, for k_chol_col's 256-thread workgroups (in k_chol_dense's
+// 1024-thread workgroup this form spills: 20-26 against 9 us per tile): the 4 x 4 pivot block P = LP DP LP^T is
 // factored redundantly in every thread (four reciprocals in sequence), a row's block entries B_i become
 // Y_i = B_i LP^-T by forward substitution, and then
 //   G: g_i,jj -= sum_p Y_ip Y_jj,p / d_p                           (c + 3 < jj <= i)
 //   M: m_i,m  -= sum_p Y_ip / d_p M'_p,m,  M'_blk = LP^-1 M_blk     (i > c + 3, m <= c + 3)
 // with the block rows M'_blk written one step later (other threads read M_blk now).  Eight barriers
 // instead of sixteen for a 32-column tile; the same factor to rounding.
-template <bool GUARD = false, class LDS>
-__device__ __forceinline__ int chol_factor_diag4(LDS &L, int nb)
+__device__ __forceinline__ int chol_factor_diag4(CholLds &L, int nb)
 {
     const int tid = threadIdx.x;
-    const bool act = !GUARD || tid < 256;
     const int jj = tid & 31, ib = (tid >> 5) & 7;
     int ok = 1;
     double defer_val = 0.0;
     int defer_at = -1;  // index into sM of the deferred block-row value
     for (int c = 0; c < nb; c += 4) {
-        if (!act) {
-            __syncthreads();
-            continue;
-        }
         if (defer_at >= 0) (&L.sM[0][0])[defer_at] = defer_val;
         defer_at = -1;
         const double P00 = L.sG[c][c], P10 = L.sG[c + 1][c], P20 = L.sG[c + 2][c], P30 = L.sG[c + 3][c];
@@ -1918,7 +1474,7 @@ __device__ __forceinline__ int chol_factor_diag4(LDS &L, int nb)
         }
         __syncthreads();
     }
-    if (act && defer_at >= 0) (&L.sM[0][0])[defer_at] = defer_val;
+    if (defer_at >= 0) (&L.sM[0][0])[defer_at] = defer_val;
     __syncthreads();
     if (tid < CB) {
         const double d = L.s_d[tid];
@@ -1984,15 +1540,14 @@ __device__ __forceinline__ void chol_offdiag_out(const LbaDev &D, CholLds &L, in
 //  1. T = A_jj - sum_{m < k0} L_jm L_jm^T (every workgroup) and, in workgroup t > 0,
 //     X = A_tj - sum_{m < k0} L_tm L_jm^T (tile_left_update2, FP64 MFMA); workgroup 0 also
 //     reduces b_j - sum_{m < k0} L_jm y_m from the same operand registers.
-//  2. chol_factor_diag: T = Lt D Lt^T, L_jj^-1 = D^-1/2 Lt^-1 without a triangular solve.
+//  2. chol_factor_diag4: T = Lt D Lt^T, L_jj^-1 = D^-1/2 Lt^-1 without a triangular solve.
 //  3. workgroup 0: chol_diag_out;  workgroup t > 0: chol_offdiag_out.  A_jj itself is never
 //     written (nothing downstream needs L_jj).
-template <int ELIM>
 __global__ __launch_bounds__(256) void k_chol_col(const LbaDev *__restrict__ Ds, int j)
 {
     LBA_GRAPH(M_ACT);
     if (j >= D.nblk_red || bx >= D.nblk_red - j) return;
-    if (D.chol_fused) return;  // factored by k_chol_dense / k_chol_env
+    if (D.chol_fused) return;  // factored by k_chol_dense
     // past CMAX workgroup 0 is the diagonal block and workgroup b >= 1 the b-th envelope row of the
     // column (col_rows): a row block outside the envelope has an all-zero tile here, and its L_tj
     // stays zero
@@ -2017,7 +1572,7 @@ __global__ __launch_bounds__(256) void k_chol_col(const LbaDev *__restrict__ Ds,
     if (tid < CB) L.sM[tid][tid] = 1.0;
     __syncthreads();
     if (ts) ts[1] = wall_clock64();
-    const int ok = ELIM == 4 ? chol_factor_diag4(L, nb) : chol_factor_diag(L, nb);
+    const int ok = chol_factor_diag4(L, nb);
     if (ts) ts[2] = wall_clock64();
     if (t == 0) chol_diag_out(D, L, k0, nb, n, bj, ok);
     else chol_offdiag_out(D, L, k0, R0, nb, n);
@@ -2037,10 +1592,10 @@ __global__ __launch_bounds__(256) void k_chol_col(const LbaDev *__restrict__ Ds,
 // unchanged.  Its sums are ordered differently from k_chol_col's (one MFMA chain per quadrant
 // instead of four K slices), so the two agree to rounding (OSG_CHOL_DENSE=0 selects the column
 // launches, tests/test_ba_gpu.py compares them).
-constexpr int CD_T = 1024;  // k_chol_env's workgroup; k_chol_dense takes its own as a template argument
-template <int CD_T, int RING, int ELIM>
+constexpr int CD_T = 1024;  // k_chol_dense's workgroup: 16 waves
 __global__ __launch_bounds__(CD_T) void k_chol_dense(const LbaDev *__restrict__ Ds)
 {
+    constexpr int RING = 2;  // 16-column operand steps in flight per wave
     LBA_GRAPH(M_ACT);
     const int n = 6 * D.nhp;
     if (n == 0 || n > CMAX || D.chol_fused != 1) return;
@@ -2180,7 +1735,7 @@ __global__ __launch_bounds__(CD_T) void k_chol_dense(const LbaDev *__restrict__ 
         if (tid < CB) s_m[tid][tid] = 1.0;
         __syncthreads();
         if (ts) ts[1] = wall_clock64();
-        const int ok = ELIM == 4 ? chol_factor_diag4<true>(L, nb) : chol_factor_diag<true>(L, nb);
+        const int ok = chol_factor_diag(L, nb);
         if (ts) ts[2] = wall_clock64();
         if (tid == 0 && !ok) D.flag[0] = 0;
         for (int e = tid; e < CB * CB; e += CD_T) {
@@ -2216,177 +1771,6 @@ __global__ __launch_bounds__(CD_T) void k_chol_dense(const LbaDev *__restrict__ 
         __syncthreads();  // L_tj, Linv and y_j of this column before the next column reads them
         if (ts) ts[3] = wall_clock64();
     }
-}
-
-// The right-looking envelope factorisation (past CMAX: BundleAdjustment) and its backward solve in one
-// 1024-thread workgroup per graph, for systems whose column blocks have at most ENV_T - 1 envelope rows
-// below the diagonal (a banded map: 7 for the 1500-KF open map, 13 closed into a loop) and n <= ENV_NX.
-// It replaces k_chol_col + k_chol_trail per column block (two launches of a few workgroups each) and
-// the backward solve's launches with one workgroup whose column steps follow each other in LDS:
-//   1. stage the diagonal tile and the column's envelope tiles (already trailing-updated) in LDS;
-//   2. chol_factor_diag; Linv and y_j out (y_j also kept in LDS);
-//   3. L_tj = X_t L_jj^-T per quadrant (FP64 MFMA), written over A_tj and kept in LDS;
-//   4. the trailing update A_tu -= L_tj L_uj^T of every envelope pair (t >= u) and b_t -= L_tj y_j.
-// The same products in the same order as k_chol_col (K = 0 past CMAX) and k_chol_trail, so the factor is
-// theirs bit for bit; the backward solve is k_chol_back_large's, with x in the tiles' LDS.
-constexpr int ENV_T = 16;                       // staged tiles: the diagonal + up to 15 envelope rows
-constexpr int ENV_NX = ENV_T * CB * (CB + 1);   // x of the backward solve in the same LDS (16 896)
-template <int ELIM>
-__global__ __launch_bounds__(CD_T) void k_chol_env(const LbaDev *__restrict__ Ds)
-{
-    LBA_GRAPH(M_ACT);
-    if (D.chol_fused != 2) return;
-    const int n = 6 * D.nhp;
-    __shared__ double s_x[ENV_T][CB][CB + 1];
-    __shared__ double s_m[CB][CB + 1];
-    __shared__ double s_part[CB][CB + 1];
-    __shared__ double s_rsq[CB], s_d[CB], s_rhs[CB], s_y[CB];
-    __shared__ int s_rb[ENV_T];
-    struct Lds {
-        double (&sG)[CB][CB + 1];
-        double (&sM)[CB][CB + 1];
-        double *s_rsq, *s_d;
-    } L{s_x[0], s_m, s_rsq, s_d};
-    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
-    double *A = D.Hs;
-    const int nblk = D.nblk_red;
-    for (int j = 0; j < nblk; j++) {
-        const int k0 = j * CB, nb = min(CB, n - k0);
-        const int r0 = D.col_rows_start[j], m = D.col_rows_start[j + 1] - r0;
-        if (tid <= m) s_rb[tid] = tid == 0 ? j : D.col_rows[r0 + tid - 1];
-        for (int e = tid; e < CB * (CB + 1); e += CD_T) (&s_m[0][0])[e] = 0.0;
-        if (tid < CB) s_rhs[tid] = tid < nb ? D.bs[k0 + tid] - 0.0 : 0.0;
-        __syncthreads();
-        // 1. the tiles as k_chol_trail left them (K = 0: nothing left to subtract)
-        for (int e = tid; e < (m + 1) * CB * CB; e += CD_T) {
-            const int t = e >> 10, r = (e >> 5) & 31, c = e & 31, rb = s_rb[t], R = rb * CB + r;
-            double v;
-            if (t == 0) v = (R < n && k0 + c < n) ? (c <= r ? A[hs_el(hs_blk(D, n, rb), r, k0 + c)] : 0.0) : (r == c ? 1.0 : 0.0);
-            else v = (R < n && k0 + c < n) ? A[hs_el(hs_blk(D, n, rb), r, k0 + c)] : 0.0;
-            s_x[t][r][c] = v;
-        }
-        __syncthreads();
-        if (tid < CB) s_m[tid][tid] = 1.0;
-        __syncthreads();
-        // 2.
-        const int ok = ELIM == 4 ? chol_factor_diag4<true>(L, nb) : chol_factor_diag<true>(L, nb);
-        if (tid == 0 && !ok) D.flag[0] = 0;
-        for (int e = tid; e < CB * CB; e += CD_T) {
-            const int r = e >> 5, c = e & 31;
-            if (k0 + r < n) D.Linv[(size_t)(k0 + r) * CB + c] = s_m[r][c];
-        }
-        if (tid < 256) {  // y_j = L_jj^-1 rhs, 8 threads per row (chol_diag_out's sums)
-            const int i = tid >> 3, p = tid & 7;
-            double acc = 0.0;
-#pragma unroll
-            for (int q = 0; q < 4; q++) acc += s_m[i][p + 8 * q] * s_rhs[p + 8 * q];
-            acc += __shfl_xor(acc, 1);
-            acc += __shfl_xor(acc, 2);
-            acc += __shfl_xor(acc, 4);
-            if (p == 0 && i < nb) D.x[k0 + i] = acc;
-            if (p == 0) s_y[i] = i < nb ? acc : 0.0;
-        }
-        // 3. L_tj = X_t L_jj^-T (chol_offdiag_out's products), at most 4 quadrants per wave
-        d4 lt[(4 * (ENV_T - 1) + CD_T / 64 - 1) / (CD_T / 64)];
-#pragma unroll
-        for (int k = 0; k < (int)(sizeof(lt) / sizeof(lt[0])); k++) {
-            const int task = w + (CD_T / 64) * k;
-            if (task >= 4 * m) break;
-            const int t = 1 + task / 4, qr = 16 * ((task >> 1) & 1), qc = 16 * (task & 1);
-            d4 acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int ks = 0; ks < CB / 4; ks++) {
-                const int kk = 4 * ks + (l >> 4);
-                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(s_x[t][qr + (l & 15)][kk], s_m[qc + (l & 15)][kk], acc, 0, 0, 0);
-            }
-            lt[k] = acc;
-            const int c = qc + (l & 15), rb = s_rb[t];
-            const HsBlk bR = hs_blk(D, n, rb);
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const int r = qr + (l >> 4) + 4 * q;
-                if (rb * CB + r < n && c < nb) A[hs_el(bR, r, k0 + c)] = acc[q];
-            }
-        }
-        __syncthreads();  // every read of the X tiles is done
-#pragma unroll
-        for (int k = 0; k < (int)(sizeof(lt) / sizeof(lt[0])); k++) {
-            const int task = w + (CD_T / 64) * k;
-            if (task >= 4 * m) break;
-            const int t = 1 + task / 4, qr = 16 * ((task >> 1) & 1), qc = 16 * (task & 1);
-            const int c = qc + (l & 15), rb = s_rb[t];
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const int r = qr + (l >> 4) + 4 * q;
-                s_x[t][r][c] = (rb * CB + r < n && c < nb) ? lt[k][q] : 0.0;  // k_chol_trail's staged L tile
-            }
-        }
-        __syncthreads();
-        // 4. trailing update of every envelope pair (a >= b) and the right-hand side
-        const int npr = m * (m + 1) / 2;
-        for (int task = w; task < 4 * npr; task += CD_T / 64) {
-            const int pr = task >> 2;
-            int a = (int)((sqrt(8.0 * pr + 1.0) - 1.0) * 0.5);  // pr = a (a + 1) / 2 + b, b <= a
-            while (a * (a + 1) / 2 > pr) a--;
-            while ((a + 1) * (a + 2) / 2 <= pr) a++;
-            const int b = pr - a * (a + 1) / 2;
-            const int ta = 1 + a, tb = 1 + b, qr = 16 * ((task >> 1) & 1), qc = 16 * (task & 1);
-            d4 acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int ks = 0; ks < CB / 4; ks++) {
-                const int kk = 4 * ks + (l >> 4);
-                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(s_x[ta][qr + (l & 15)][kk], s_x[tb][qc + (l & 15)][kk], acc, 0, 0, 0);
-            }
-            const int R0 = s_rb[ta] * CB, C0 = s_rb[tb] * CB, c = qc + (l & 15);
-            const HsBlk bt = hs_blk(D, n, s_rb[ta]);
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const int r = qr + (l >> 4) + 4 * q;
-                if (R0 + r < n && C0 + c < n) A[hs_el(bt, r, C0 + c)] -= acc[q];
-            }
-        }
-        if (tid < m * CB) {  // b_t -= L_tj y_j (k_chol_trail's diagonal-pair sums)
-            const int t = 1 + (tid >> 5), r = tid & 31, R = s_rb[t] * CB + r;
-            double sacc = 0.0;
-#pragma unroll 8
-            for (int k = 0; k < CB; k++) sacc += s_x[t][r][k] * s_y[k];
-            if (R < n) D.bs[R] -= sacc;
-        }
-        __syncthreads();  // the updated tiles and b before the next column stages them
-    }
-    // backward solve L^T x = y (k_chol_back_large's blocks and sums), x over the tiles' LDS
-    double *xv = &s_x[0][0][0];
-    for (int i = tid; i < n; i += CD_T) xv[i] = 0.0;
-    const int c = tid & 31, g = tid >> 5;
-    for (int bi = nblk - 1; bi >= 0; bi--) {
-        const int k0 = bi * CB, nb = min(CB, n - k0);
-        (&s_m[0][0])[tid] = D.Linv[(size_t)min(k0 + (tid >> 5), n - 1) * CB + (tid & 31)];  // s_li[r * CB + c]
-        __syncthreads();
-        double acc = 0.0;
-        if (c < nb) {
-            for (int q = D.col_rows_start[bi]; q < D.col_rows_start[bi + 1]; q++) {
-                const int rb = D.col_rows[q], row = rb * CB + g;
-                if (row < n) acc += A[hs_el(hs_blk(D, n, rb), g, k0 + c)] * xv[row];
-            }
-        }
-        s_part[c][g] = acc;
-        __syncthreads();
-        if (tid < CB) {
-            double sp = 0.0;
-#pragma unroll
-            for (int gg = 0; gg < 32; gg++) sp += s_part[tid][gg];
-            s_rhs[tid] = (tid < nb) ? D.x[k0 + tid] - sp : 0.0;
-        }
-        __syncthreads();
-        if (tid < nb) {
-            double xs = 0.0;
-#pragma unroll
-            for (int r = 0; r < CB; r++) xs += (&s_m[0][0])[r * CB + tid] * s_rhs[r];
-            xv[k0 + tid] = xs;
-        }
-        __syncthreads();
-    }
-    for (int i = tid; i < n; i += CD_T) D.x[i] = xv[i];
 }
 
 // Backward substitution L^T x = y (y in x after the column launches), one 1024-thread
@@ -2498,10 +1882,8 @@ __global__ __launch_bounds__(1024) void k_chol_back(const LbaDev *__restrict__ D
 // forward-substitution right-hand side b_t -= L_tj y_j.  The column launches then read their tiles as
 // they stand (K = 0): the O(n^3) work is spread over (nblk - j)^2 / 2 workgroups per step instead of
 // one K-long GEMM per row block (which left one CU per row block MFMA-bound at large n).
-// PRE (the default; OSG_TRAIL_PRE=0 for the previous order, bit-identical): the thread's four target
-// entries A_tu (and a diagonal tile's b_t / y_j) are loaded with the L tiles, before the MFMA, instead of
-// after it: one memory round trip per workgroup instead of two in a row.
-template <bool PRE>
+// The thread's four target entries A_tu (and a diagonal tile's b_t / y_j) are loaded with the L tiles,
+// before the MFMA, instead of after it: one memory round trip per workgroup instead of two in a row.
 __global__ __launch_bounds__(256) void k_chol_trail(const LbaDev *__restrict__ Ds, int j)
 {
     LBA_GRAPH(M_ACT);
@@ -2524,7 +1906,7 @@ __global__ __launch_bounds__(256) void k_chol_trail(const LbaDev *__restrict__ D
     const int w = tid >> 6, l = tid & 63;
     const int qr = (w >> 1) * 16, qc = (w & 1) * 16;
     double old[4], bsv = 0.0, yv[CB];
-    if (PRE) {
+    {
         const int c = qc + (l & 15);
 #pragma unroll
         for (int q = 0; q < 4; q++) {
@@ -2553,22 +1935,13 @@ __global__ __launch_bounds__(256) void k_chol_trail(const LbaDev *__restrict__ D
 #pragma unroll
     for (int q = 0; q < 4; q++) {
         const int r = qr + (l >> 4) + 4 * q;
-        if (R0 + r < n && C0 + c < n) {
-            if (PRE) D.Hs[hs_el(bt, r, C0 + c)] = old[q] - acc[q];
-            else D.Hs[hs_el(bt, r, C0 + c)] -= acc[q];
-        }
+        if (R0 + r < n && C0 + c < n) D.Hs[hs_el(bt, r, C0 + c)] = old[q] - acc[q];
     }
     if (t == u && tid < CB && R0 + tid < n) {  // block j is full (m > 0): y_j is 32 entries
         double s = 0.0;
-        if (PRE) {
 #pragma unroll
-            for (int k = 0; k < CB; k++) s += sLt[tid][k] * yv[k];
-            D.bs[R0 + tid] = bsv - s;
-        } else {
-#pragma unroll 8
-            for (int k = 0; k < CB; k++) s += sLt[tid][k] * D.x[K0 + k];
-            D.bs[R0 + tid] -= s;
-        }
+        for (int k = 0; k < CB; k++) s += sLt[tid][k] * yv[k];
+        D.bs[R0 + tid] = bsv - s;
     }
 }
 
@@ -2577,9 +1950,8 @@ __global__ __launch_bounds__(256) void k_chol_trail(const LbaDev *__restrict__ D
 // L_kk^-1 tile read from Linv when the block is reached instead of staged up front.
 constexpr int CMAX_LARGE = 6144;  // 1024 free poses
 
-// PRE (the default; OSG_BACKL_PRE=0 for the previous order, bit-identical): block bi - 1's Linv entry is
-// loaded while block bi is solved, so a block does not start with a global round trip.
-template <bool PRE>
+// Block bi - 1's Linv entry is loaded while block bi is solved, so a block does not start with a global
+// round trip.
 __global__ __launch_bounds__(1024) void k_chol_back_large(const LbaDev *__restrict__ Ds)
 {
     LBA_GRAPH(M_ACT);
@@ -2598,15 +1970,11 @@ __global__ __launch_bounds__(1024) void k_chol_back_large(const LbaDev *__restri
     }
     const int nblk = (n + CB - 1) / CB;
     const int c = tid & 31, g = tid >> 5;
-    double li_next = PRE ? D.Linv[(size_t)min((nblk - 1) * CB + (tid >> 5), n - 1) * CB + (tid & 31)] : 0.0;
+    double li_next = D.Linv[(size_t)min((nblk - 1) * CB + (tid >> 5), n - 1) * CB + (tid & 31)];
     for (int bi = nblk - 1; bi >= 0; bi--) {
         const int k0 = bi * CB, nb = min(CB, n - k0);
-        if (PRE) {
-            s_li[tid] = li_next;
-            if (bi > 0) li_next = D.Linv[(size_t)min(k0 - CB + (tid >> 5), n - 1) * CB + (tid & 31)];
-        } else {
-            s_li[tid] = D.Linv[(size_t)min(k0 + (tid >> 5), n - 1) * CB + (tid & 31)];
-        }
+        s_li[tid] = li_next;
+        if (bi > 0) li_next = D.Linv[(size_t)min(k0 - CB + (tid >> 5), n - 1) * CB + (tid & 31)];
         __syncthreads();
         // the rows below the block inside the envelope only (column block bi's envelope rows, ascending):
         // every other L entry of this column is zero, and is not stored (k_schur_pairs writes only the
@@ -2646,10 +2014,8 @@ __global__ __launch_bounds__(1024) void k_chol_back_large(const LbaDev *__restri
 // substitution) and k_back_copy moves it to x.  The work is the envelope's O(n bw), spread over the
 // chip, instead of one workgroup streaming the whole triangle through LDS.
 constexpr int BSC = 256;  // columns per workgroup of k_back_step
-// PRE (the default; OSG_BACK_PRE=0 for the previous order, bit-identical): the thread's 32 L entries and the
-// 32 x 32 Linv column are loaded before y'_bi, which the previous step wrote, so a step waits out one memory
-// round trip instead of three in a row (y', then Linv, then L); the sums are the same, in the same order.
-template <bool PRE>
+// The thread's 32 L entries and the 32 x 32 Linv column are loaded before y'_bi, which the previous step
+// wrote, so a step waits out one memory round trip instead of three in a row (y', then Linv, then L).
 __global__ __launch_bounds__(BSC) void k_back_step(const LbaDev *__restrict__ Ds, int step)
 {
     LBA_GRAPH(M_ACT);
@@ -2665,27 +2031,20 @@ __global__ __launch_bounds__(BSC) void k_back_step(const LbaDev *__restrict__ Ds
     const double *A = D.Hs;
     const int u = c0 + (bx - 1) * BSC + tid;
     double a[CB], li[CB];
-    if (PRE) {
-        if (bx > 0 && u < k0) {
-            const HsBlk bb = hs_blk(D, n, bi);
+    if (bx > 0 && u < k0) {
+        const HsBlk bb = hs_blk(D, n, bi);
 #pragma unroll
-            for (int r = 0; r < CB; r++) a[r] = r < nb ? A[hs_el(bb, r, u)] : 0.0;
-        }
-        if (tid < CB)
-#pragma unroll
-            for (int r = 0; r < CB; r++) li[r] = D.Linv[(size_t)min(k0 + r, n - 1) * CB + tid];
+        for (int r = 0; r < CB; r++) a[r] = r < nb ? A[hs_el(bb, r, u)] : 0.0;
     }
+    if (tid < CB)
+#pragma unroll
+        for (int r = 0; r < CB; r++) li[r] = D.Linv[(size_t)min(k0 + r, n - 1) * CB + tid];
     if (tid < CB) s_rhs[tid] = tid < nb ? D.x[k0 + tid] : 0.0;
     __syncthreads();
     if (tid < CB) {
         double xv = 0.0;
-        if (PRE) {
 #pragma unroll
-            for (int r = 0; r < CB; r++) xv += li[r] * s_rhs[r];
-        } else {
-#pragma unroll
-            for (int r = 0; r < CB; r++) xv += D.Linv[(size_t)min(k0 + r, n - 1) * CB + tid] * s_rhs[r];
-        }
+        for (int r = 0; r < CB; r++) xv += li[r] * s_rhs[r];
         s_x[tid] = tid < nb ? xv : 0.0;
         if (bx == 0 && tid < nb) D.bs[k0 + tid] = xv;
     }
@@ -2693,15 +2052,9 @@ __global__ __launch_bounds__(BSC) void k_back_step(const LbaDev *__restrict__ Ds
     if (bx == 0) return;  // workgroup 0 solved the block; 1.. update the columns
     if (u >= k0) return;
     double acc = 0.0;
-    if (PRE) {
 #pragma unroll
-        for (int r = 0; r < CB; r++)
-            if (r < nb) acc += a[r] * s_x[r];
-    } else {
-        const HsBlk bb = hs_blk(D, n, bi);
-#pragma unroll 8
-        for (int r = 0; r < nb; r++) acc += A[hs_el(bb, r, u)] * s_x[r];
-    }
+    for (int r = 0; r < CB; r++)
+        if (r < nb) acc += a[r] * s_x[r];
     D.x[u] -= acc;
 }
 __global__ __launch_bounds__(EB) void k_back_copy(const LbaDev *__restrict__ Ds)
@@ -2713,18 +2066,11 @@ __global__ __launch_bounds__(EB) void k_back_copy(const LbaDev *__restrict__ Ds)
     if (i < n) D.x[i] = D.bs[i];
 }
 
-// landmark back-substitution + new estimates + LM scale partials.  Each thread walks its landmark's
-// Hpl blocks (16-byte loads, many in flight per thread).  STAGE (OSG_UPDATE_STAGE=1, A/B runs,
-// bit-identical): the workgroup's Hpl blocks (its EB landmarks' blocks are consecutive) come through
-// LDS in UB-block pieces read with coalesced 16-byte loads; measured slower (2.34 against 2.08 ms per
-// 14 launches of 64 C4 windows, profiles/r04_lba_dinv_ab.txt): the pieces serialise load, barrier
-// and compute, where the per-thread walks keep more loads in flight.
-// COOP (the default; OSG_UPDATE_COOP=0 for the walks, bit-identical): one thread per block, EB consecutive blocks of the
-// workgroup's landmarks at a time (coalesced 144-byte blocks, no LDS copy of them): each thread forms its
-// block's Hplᵀ(−x_p) in registers and leaves the 3 values in LDS, then each landmark's thread adds its
-// blocks' values in block order, the per-thread walk's sums.
-constexpr int UB = 256;  // blocks per staged piece: 36 KiB of LDS
-template <bool STAGE, bool COOP = false>
+// landmark back-substitution + new estimates + LM scale partials on whole Hpl blocks (OSG_LBA_HPL=1; the
+// default is k_update_c).  One thread per block, EB consecutive blocks of the workgroup's landmarks at a
+// time (coalesced 144-byte blocks, no LDS copy of them): each thread forms its block's Hplᵀ(−x_p) in
+// registers and leaves the 3 values in LDS, then each landmark's thread adds its blocks' values in block
+// order, the sums of a per-landmark walk over its blocks.
 __global__ __launch_bounds__(EB) void k_update(const LbaDev *__restrict__ Ds)
 {
     LBA_GRAPH(M_ACT);
@@ -2738,82 +2084,42 @@ __global__ __launch_bounds__(EB) void k_update(const LbaDev *__restrict__ Ds)
     double sc = 0.0;
     double cl[3] = {0, 0, 0};
     if (t < D.nhl) {
-        cl[0] = D.bl[D.ls_b * (size_t)t];
-        cl[1] = D.bl[D.ls_b * (size_t)t + 1];
-        cl[2] = D.bl[D.ls_b * (size_t)t + 2];
+        cl[0] = D.bl[3 * (size_t)t];
+        cl[1] = D.bl[3 * (size_t)t + 1];
+        cl[2] = D.bl[3 * (size_t)t + 2];
     }
-    if (STAGE) {
-        __shared__ double s_b[UB * 18];
-        typedef int i4 __attribute__((ext_vector_type(4)));
-        const int l0 = bx * EB;
-        const int g0 = l0 < D.nhl ? D.lm_b_start[l0] : 0;
-        const int g1 = l0 < D.nhl ? D.lm_b_start[min(l0 + EB, D.nhl)] : 0;
-        const int mb0 = t < D.nhl ? D.lm_b_start[t] : 0, mb1 = t < D.nhl ? D.lm_b_start[t + 1] : 0;
-        for (int p0 = g0; p0 < g1; p0 += UB) {  // workgroup-uniform
-            const int nb = min(UB, g1 - p0);
-            const i4 *src = (const i4 *)(D.Hpl + 18 * (size_t)p0);
-            for (int k = threadIdx.x; k < 9 * nb; k += EB) ((i4 *)s_b)[k] = src[k];
-            __syncthreads();
-            const int a1 = min(mb1, p0 + nb);
-            for (int blk = max(mb0, p0); blk < a1; blk++) {
-                const int i1 = D.blk_pose[blk];
-                const double *B = s_b + 18 * (blk - p0);
-                for (int c = 0; c < 3; c++) {
-                    double s_ = 0;
-                    for (int r = 0; r < 6; r++) s_ += B[3 * r + c] * (-D.x[6 * i1 + r]);
-                    cl[c] += s_;
-                }
+    __shared__ double s_v[3][EB];
+    const int l0 = bx * EB;
+    const int g0 = l0 < D.nhl ? D.lm_b_start[l0] : 0;
+    const int g1 = l0 < D.nhl ? D.lm_b_start[min(l0 + EB, D.nhl)] : 0;
+    const int mb0 = t < D.nhl ? D.lm_b_start[t] : 0, mb1 = t < D.nhl ? D.lm_b_start[t + 1] : 0;
+    for (int p0 = g0; p0 < g1; p0 += EB) {  // workgroup-uniform
+        const int blk = p0 + (int)threadIdx.x;
+        if (blk < g1) {
+            const int i1 = D.blk_pose[blk];
+            const double *B = D.Hpl + 18 * (size_t)blk;
+            for (int c = 0; c < 3; c++) {
+                double s_ = 0;
+                for (int r = 0; r < 6; r++) s_ += B[3 * r + c] * (-D.x[6 * i1 + r]);
+                s_v[c][threadIdx.x] = s_;
             }
-            __syncthreads();
         }
-    }
-    if (COOP) {
-        __shared__ double s_v[3][EB];
-        const int l0 = bx * EB;
-        const int g0 = l0 < D.nhl ? D.lm_b_start[l0] : 0;
-        const int g1 = l0 < D.nhl ? D.lm_b_start[min(l0 + EB, D.nhl)] : 0;
-        const int mb0 = t < D.nhl ? D.lm_b_start[t] : 0, mb1 = t < D.nhl ? D.lm_b_start[t + 1] : 0;
-        for (int p0 = g0; p0 < g1; p0 += EB) {  // workgroup-uniform
-            const int blk = p0 + (int)threadIdx.x;
-            if (blk < g1) {
-                const int i1 = D.blk_pose[blk];
-                const double *B = D.Hpl + 18 * (size_t)blk;
-                for (int c = 0; c < 3; c++) {
-                    double s_ = 0;
-                    for (int r = 0; r < 6; r++) s_ += B[3 * r + c] * (-D.x[6 * i1 + r]);
-                    s_v[c][threadIdx.x] = s_;
-                }
-            }
-            __syncthreads();
-            const int a1 = min(mb1, p0 + EB);
-            for (int b2 = max(mb0, p0); b2 < a1; b2++)
-                for (int c = 0; c < 3; c++) cl[c] += s_v[c][b2 - p0];
-            __syncthreads();
-        }
+        __syncthreads();
+        const int a1 = min(mb1, p0 + EB);
+        for (int b2 = max(mb0, p0); b2 < a1; b2++)
+            for (int c = 0; c < 3; c++) cl[c] += s_v[c][b2 - p0];
+        __syncthreads();
     }
     if (t < D.nhl) {
         const int l = t;
-        if (!STAGE && !COOP)
-            for (int blk = D.lm_b_start[l]; blk < D.lm_b_start[l + 1]; blk++) {
-                const int i1 = D.blk_pose[blk];
-                const double *B = D.Hpl + 18 * (size_t)blk;
-                for (int c = 0; c < 3; c++) {
-                    double s_ = 0;
-                    for (int r = 0; r < 6; r++) s_ += B[3 * r + c] * (-D.x[6 * i1 + r]);
-                    cl[c] += s_;
-                }
-            }
-        // Dinv into registers from either source (a pointer to a local-or-global array put it in scratch)
         double Di[9];
-        if (D.dinv_inline) landmark_dinv(D, l, lambda, Di, nullptr);
-        else
-            for (int k = 0; k < 9; k++) Di[k] = D.Dinv[9 * (size_t)l + k];
+        landmark_dinv(D, l, lambda, Di, nullptr);
         const int p = D.hl_point[l];
         for (int r = 0; r < 3; r++) {
             const double xl = Di[3 * r] * cl[0] + Di[3 * r + 1] * cl[1] + Di[3 * r + 2] * cl[2];
             D.x[sp + 3 * l + r] = xl;
             point_new[3 * (size_t)p + r] = point_cur[3 * (size_t)p + r] + xl;
-            sc += xl * (lambda * xl + D.bl[D.ls_b * (size_t)l + r]);
+            sc += xl * (lambda * xl + D.bl[3 * (size_t)l + r]);
         }
     }
     if (t < D.np) {  // poses: exp(x) * T for free active poses, copy otherwise
@@ -2838,10 +2144,10 @@ __global__ __launch_bounds__(EB) void k_update(const LbaDev *__restrict__ Ds)
     if (threadIdx.x == 0) D.part[D.npart + bx] = tot;
 }
 
-// k_update on the compact per-block factor (the default): the COOP form's one thread per block, forming
+// k_update on the compact per-block factor (the default): k_update's one thread per block, forming
 // Hpl^T x_p from the block's M', its pose's R and c and its landmark's position (z_rows' algebra); each
 // workgroup's landmark positions and each piece's block -> landmark map come through LDS from the
-// landmarks' threads.  The per-landmark sums keep the COOP order.
+// landmarks' threads.  The per-landmark sums keep k_update's order.
 __global__ __launch_bounds__(EB) void k_update_c(const LbaDev *__restrict__ Ds)
 {
     LBA_GRAPH(M_ACT);
@@ -2863,9 +2169,9 @@ __global__ __launch_bounds__(EB) void k_update_c(const LbaDev *__restrict__ Ds)
     const int mb0 = t < D.nhl ? D.lm_b_start[t] : 0, mb1 = t < D.nhl ? D.lm_b_start[t + 1] : 0;
     int p = -1;
     if (t < D.nhl) {
-        cl[0] = D.bl[D.ls_b * (size_t)t];
-        cl[1] = D.bl[D.ls_b * (size_t)t + 1];
-        cl[2] = D.bl[D.ls_b * (size_t)t + 2];
+        cl[0] = D.bl[3 * (size_t)t];
+        cl[1] = D.bl[3 * (size_t)t + 1];
+        cl[2] = D.bl[3 * (size_t)t + 2];
         p = D.hl_point[t];
         for (int k = 0; k < 3; k++) s_xw[k][threadIdx.x] = point_cur[3 * (size_t)p + k];
     }
@@ -2918,16 +2224,13 @@ __global__ __launch_bounds__(EB) void k_update_c(const LbaDev *__restrict__ Ds)
     }
     if (t < D.nhl) {
         const int l = t;
-        // Dinv into registers from either source (a pointer to a local-or-global array put it in scratch)
         double Di[9];
-        if (D.dinv_inline) landmark_dinv(D, l, lambda, Di, nullptr);
-        else
-            for (int k = 0; k < 9; k++) Di[k] = D.Dinv[9 * (size_t)l + k];
+        landmark_dinv(D, l, lambda, Di, nullptr);
         for (int r = 0; r < 3; r++) {
             const double xl = Di[3 * r] * cl[0] + Di[3 * r + 1] * cl[1] + Di[3 * r + 2] * cl[2];
             D.x[sp + 3 * l + r] = xl;
             point_new[3 * (size_t)p + r] = point_cur[3 * (size_t)p + r] + xl;
-            sc += xl * (lambda * xl + D.bl[D.ls_b * (size_t)l + r]);
+            sc += xl * (lambda * xl + D.bl[3 * (size_t)l + r]);
         }
     }
     if (t < D.np) {  // poses: exp(x) * T for free active poses, copy otherwise
@@ -3023,17 +2326,16 @@ struct LbaHost {
     const osg_ba_graph *G = nullptr;
     osg_ba_result *R = nullptr;
     int np = 0, npt = 0, ne = 0, nhp = 0, nhl = 0, nblk = 0, npairs = 0, nchunks = 0;
-    int ge = 0, gl = 0, gll = 0, gu = 0, nblk_red = 0, npart = 64;
+    int ge = 0, gll = 0, gu = 0, nblk_red = 0, npart = 64;
     bool multi = false;  // a block with several edges (k_linearize<true>)
     std::vector<int32_t> blk_first, blk_last;  // envelope of the reduced system by row block (see LbaDev)
     std::vector<int32_t> col_rows_start, col_rows, live_pairs;  // envelope rows per column block, live pairs
     std::vector<int32_t> live_chunk, env_off;  // per live pair its chunk range; envelope tiles before each row block
-    int max_col_rows = 0;
     bool trivial = false;  // nothing to optimise: the estimates are returned unchanged
     int lm_e_ident = 0;
     std::vector<int32_t> pose_h, hp_pose, point_h, hl_point, lm_e_start, lm_e, lg_start, lg_lq, lm_b_start, blk_pose, edge_blk, blk_lm,
         hp_e_start, hp_e, hp_b_start, hp_b, pair_start, pair_b, chunk_start, pair_chunk,
-        pair_rank, rs_pose, rs_rank0, rs_chunk_start, rs_chunk, hp_rs_start, rs_order, rs_cdesc, rs_info, hp_b_lm;
+        pair_rank, rs_pose, rs_rank0, rs_chunk_start, rs_chunk, hp_rs_start, rs_cdesc, rs_info, hp_b_lm;
     int n_rs = 0;
     double t_struct = 0;
     // LM state (ref:Thirdparty/g2o/g2o/core/optimization_algorithm_levenberg.cpp:61-194 and
@@ -3050,7 +2352,7 @@ struct LbaHost {
         G = nullptr;
         R = nullptr;
         np = npt = ne = nhp = nhl = nblk = npairs = nchunks = n_rs = 0;
-        ge = gl = gll = gu = nblk_red = 0;
+        ge = gll = gu = nblk_red = 0;
         multi = false;
         npart = 64;
         blk_first.clear();
@@ -3060,14 +2362,12 @@ struct LbaHost {
         live_pairs.clear();
         live_chunk.clear();
         env_off.clear();
-        max_col_rows = 0;
         trivial = false;
         hp_pose.clear();
         hl_point.clear();
         blk_pose.clear();
         chunk_start.clear();
         rs_pose.clear();
-        rs_order.clear();
         rs_cdesc.clear();
         rs_info.clear();
         hp_b_lm.clear();
@@ -3191,9 +2491,7 @@ int build_structure(osg_ctx *ctx, const osg_ba_graph *G, LbaHost &H)
     {
         std::vector<int32_t> fill(H.lm_e_start.begin(), H.lm_e_start.end() - 1);
         for (int e = 0; e < ne; e++) H.lm_e[fill[point_h[G->e_point[e]]]++] = e;
-        // OSG_LBA_LMIDENT=0: always through lm_e (A/B runs, the same values)
-        static const bool ident_ok = !(getenv("OSG_LBA_LMIDENT") && atoi(getenv("OSG_LBA_LMIDENT")) == 0);
-        H.lm_e_ident = ident_ok ? 1 : 0;
+        H.lm_e_ident = 1;
         for (int q = 0; q < ne && H.lm_e_ident; q++) H.lm_e_ident = H.lm_e[q] == q;
         // k_linearize's landmark groups: consecutive landmarks with at most EB edges together, a
         // landmark with more alone
@@ -3463,8 +2761,6 @@ int build_structure(osg_ctx *ctx, const osg_ba_graph *G, LbaHost &H)
             std::vector<int32_t> fill(H.col_rows_start.begin(), H.col_rows_start.end() - 1);
             for (int t = 0; t < nb; t++)  // t ascending: each list comes out sorted
                 for (int j = H.blk_first[t]; j < t; j++) H.col_rows[fill[j]++] = t;
-            for (int j = 0; j < nb; j++)
-                H.max_col_rows = std::max(H.max_col_rows, H.col_rows_start[j + 1] - H.col_rows_start[j]);
             // the envelope tile store (hs_at): row block t keeps tiles blk_first[t] .. t
             H.env_off.assign(nb + 1, 0);
             for (int t = 0; t < nb; t++) H.env_off[t + 1] = H.env_off[t] + (t - H.blk_first[t] + 1);
@@ -3491,22 +2787,6 @@ int build_structure(osg_ctx *ctx, const osg_ba_graph *G, LbaHost &H)
         }
     }
     H.n_rs = H.hp_rs_start[nhp];
-    // launch order of the row segments: by the landmark at the middle of the segment (pose order on
-    // ties) when OSG_SCHUR_ORDER=1, so the segments in flight together read the Hpl blocks of one
-    // landmark range; identity otherwise.  Only which workgroup takes a segment changes: every sum
-    // keeps its order, the results are bit-identical.
-    H.rs_order.resize(H.n_rs);
-    for (int r = 0; r < H.n_rs; r++) H.rs_order[r] = r;
-    static const bool schur_order = getenv("OSG_SCHUR_ORDER") && atoi(getenv("OSG_SCHUR_ORDER")) == 1;
-    if (schur_order) {
-        std::vector<int32_t> key(H.n_rs);
-        for (int r = 0; r < H.n_rs; r++) {
-            const int i = H.rs_pose[r], hb0 = H.hp_b_start[i], nb = H.hp_b_start[i + 1] - hb0;
-            const int mid = std::min(nb - 1, H.rs_rank0[r] + std::min(RS, nb - H.rs_rank0[r]) / 2);
-            key[r] = nb > 0 ? H.blk_lm[H.hp_b[hb0 + mid]] : 0;
-        }
-        std::stable_sort(H.rs_order.begin(), H.rs_order.end(), [&](int a, int b) { return key[a] < key[b]; });
-    }
     STRUCT_CP(8);
     // chunks of <= SCH contributions, never spanning two pairs or two row segments; listed per row
     // segment (pair order, then contribution order).  A row's chunks belong to its own segments, so
@@ -3597,7 +2877,7 @@ int build_structure(osg_ctx *ctx, const osg_ba_graph *G, LbaHost &H)
     STRUCT_CP(9);
     H.rs_info.assign(8 * (size_t)std::max(H.n_rs, 1), 0);
     for (int w = 0; w < H.n_rs; w++) {
-        const int r = H.rs_order[w], i = H.rs_pose[r], hb0 = H.hp_b_start[i];
+        const int r = w, i = H.rs_pose[r], hb0 = H.hp_b_start[i];  // launched in segment order
         int32_t *f = &H.rs_info[8 * (size_t)w];
         f[0] = r;
         f[1] = i;
@@ -3619,7 +2899,6 @@ int build_structure(osg_ctx *ctx, const osg_ba_graph *G, LbaHost &H)
     }
     STRUCT_CP(10);
     H.ge = (ne + EB - 1) / EB;
-    H.gl = (nhl + EB - 1) / EB;
     H.gll = (int)H.lg_start.size() - 1;
     H.gu = (std::max(std::max(nhl, np), npt) + EB - 1) / EB;
     H.nblk_red = (6 * nhp + CB - 1) / CB;
@@ -3652,15 +2931,13 @@ void carve_state(char *base, size_t &off, const LbaHost &H, LbaDev *D, bool prof
     double *qA = carve<double>(base, off, 3 * (size_t)npt);
     double *qB = carve<double>(base, off, 3 * (size_t)npt);
     double *err = carve<double>(base, off, 3 * (size_t)ne);
-    static const bool lrec = getenv("OSG_LBA_LREC") && atoi(getenv("OSG_LBA_LREC")) == 1;
-    double *Hll = carve<double>(base, off, (lrec ? 16 : 9) * (size_t)nhl);
-    double *bl = lrec ? Hll + 9 : carve<double>(base, off, 3 * (size_t)nhl);
+    double *Hll = carve<double>(base, off, 9 * (size_t)nhl);
+    double *bl = carve<double>(base, off, 3 * (size_t)nhl);
     double *Hpl = carve<double>(base, off, (compact ? 6 : 18) * (size_t)nblk);  // the compact M, or Hpl
     double *hp_Rt = carve<double>(base, off, RT_STRIDE * (size_t)nhp);
-    double *lmX = lrec ? Hll + 12 : carve<double>(base, off, compact ? 3 * (size_t)nhl : 1);
+    double *lmX = carve<double>(base, off, compact ? 3 * (size_t)nhl : 1);
     double *Hpp = carve<double>(base, off, 36 * (size_t)nhp);
     double *bp = carve<double>(base, off, 6 * (size_t)nhp);
-    double *Dinv = carve<double>(base, off, 9 * (size_t)nhl);
     double *bs_part = carve<double>(base, off, 6 * (size_t)std::max(H.n_rs, 1));
     // dense up to CMAX; past it the envelope's tiles only (the dense n^2 capped maps at 7 723 free KeyFrames)
     double *Hs = carve<double>(base, off, H.env_off.empty() ? (size_t)sp * sp : (size_t)H.env_off.back() * CB * CB);
@@ -3668,7 +2945,6 @@ void carve_state(char *base, size_t &off, const LbaHost &H, LbaDev *D, bool prof
     double *x = carve<double>(base, off, (size_t)sp + 3 * (size_t)nhl);
     double *part = carve<double>(base, off, 4 * (size_t)H.npart + 64);
     double *chunk_part = carve<double>(base, off, 36 * (size_t)std::max(H.nchunks, 1));
-    double *db = carve<double>(base, off, 3 * (size_t)nhl);
     double *Linv = carve<double>(base, off, (size_t)sp * CB);
     int *flag = carve<int>(base, off, 16);
     unsigned long long *ts = prof_ts ? carve<unsigned long long>(base, off, 8 * 2 * 64 + 64) : nullptr;
@@ -3684,23 +2960,18 @@ void carve_state(char *base, size_t &off, const LbaHost &H, LbaDev *D, bool prof
     D->err = err;
     D->Hll = Hll;
     D->bl = bl;
-    D->ls_h = lrec ? 16 : 9;
-    D->ls_b = lrec ? 16 : 3;
-    D->ls_x = lrec ? 16 : 3;
     D->Hpl = Hpl;
     D->hp_Rt = hp_Rt;
     D->lmX = lmX;
     D->compact = compact ? 1 : 0;
     D->Hpp = Hpp;
     D->bp = bp;
-    D->Dinv = Dinv;
     D->bs_part = bs_part;
     D->Hs = Hs;
     D->bs = bs;
     D->x = x;
     D->part = part;
     D->chunk_part = chunk_part;
-    D->db = db;
     D->Linv = Linv;
     D->flag = flag;
     D->tstamp = ts;
@@ -3714,49 +2985,13 @@ int lba_batch(osg_ctx *ctx, const osg_ba_graph *graphs, osg_ba_result *results, 
     OSG_REQUIRE(ctx, B >= 0 && (B == 0 || (graphs && results)), "batch arguments");
     static const int prof_level = getenv("OSG_LBA_PROFILE") ? atoi(getenv("OSG_LBA_PROFILE")) : 0;
     const bool prof = prof_level > 0, prof_ts = prof_level >= 2 && B == 1;
-    // OSG_SCHUR_VALU=1: the VALU Schur product (A/B measurements); default FP64 MFMA
-    static const bool schur_valu = getenv("OSG_SCHUR_VALU") && atoi(getenv("OSG_SCHUR_VALU")) != 0;
-    // OSG_SCHUR_STAGE=1: partner spans staged in LDS (k_schur_rows_st), bit-identical
-    static const bool schur_stage = getenv("OSG_SCHUR_STAGE") && atoi(getenv("OSG_SCHUR_STAGE")) != 0;
-    // OSG_SCHUR_DIRECT=1: Hpl_j operands loaded per lane from global memory (k_schur_rows<false, true>)
-    static const bool schur_direct = getenv("OSG_SCHUR_DIRECT") && atoi(getenv("OSG_SCHUR_DIRECT")) != 0;
-    // OSG_POSE_RED_GATHER=1: k_pose_red gathers its edge inputs through hp_e (A/B runs), bit-identical
-    static const bool pose_red_gather = getenv("OSG_POSE_RED_GATHER") && atoi(getenv("OSG_POSE_RED_GATHER")) != 0;
-    // OSG_UPDATE_STAGE=1: k_update reads Hpl through LDS pieces (A/B runs), bit-identical
-    // OSG_SCHUR_POINT=1: Dinv and Dinv b_l from a kernel of their own (A/B runs), bit-identical
-    static const bool schur_point = getenv("OSG_SCHUR_POINT") && atoi(getenv("OSG_SCHUR_POINT")) != 0;
-    // OSG_LIN_WPE=4: k_linearize compiled for 4 waves per SIMD (A/B runs), bit-identical
-    static const bool lin_wpe4 = getenv("OSG_LIN_WPE") && atoi(getenv("OSG_LIN_WPE")) == 4;
-    static const bool update_stage = getenv("OSG_UPDATE_STAGE") && atoi(getenv("OSG_UPDATE_STAGE")) != 0;
-    // k_update with one thread per Hpl block (the default since the end of r05: 150 -> 143 us per 64-window
-    // step, profiles/r05_update_coop_ab.txt); OSG_UPDATE_COOP=0 restores the per-thread walks, bit-identical
-    static const bool update_coop = !(getenv("OSG_UPDATE_COOP") && atoi(getenv("OSG_UPDATE_COOP")) == 0);
-    // OSG_CHOL_DENSE=0: the per-column k_chol_col (+ k_chol_trail) launches for every system (A/B runs)
-    // instead of the one-workgroup factorisations k_chol_dense and k_chol_env
+    // OSG_CHOL_DENSE=0: the per-column k_chol_col launches for every system instead of the one-workgroup
+    // k_chol_dense (the tests compare the two shipped factorisations)
     static const bool chol_dense = !(getenv("OSG_CHOL_DENSE") && atoi(getenv("OSG_CHOL_DENSE")) == 0);
-    // OSG_CHOL_ENV=1: k_chol_env for narrow-envelope maps (A/B runs; measured slower than the column launches:
-    // one workgroup serialises each column's trailing update, which k_chol_trail spreads over the chip)
-    static const bool chol_env = getenv("OSG_CHOL_ENV") && atoi(getenv("OSG_CHOL_ENV")) == 1;
-    // OSG_CHOL_DENSE_NT=512: k_chol_dense with 8 waves (256 VGPRs, a 3-step operand ring) instead of 16 (A/B)
-    static const int chol_dense_nt = getenv("OSG_CHOL_DENSE_NT") ? atoi(getenv("OSG_CHOL_DENSE_NT")) : 1024;
-    // the column launches' (and k_chol_env's) diagonal tiles eliminated four columns per barrier
-    // (chol_factor_diag4: 7.3-8.0 against 9.0 us per tile, global_ba_map +6 %); OSG_CHOL_ELIM=2 for the
-    // two-column form.  k_chol_dense keeps two: in its 1024-thread workgroup the four-column form spills
-    // (20-26 us per tile, gpurun_out/elim4).
-    static const int chol_elim = getenv("OSG_CHOL_ELIM") ? atoi(getenv("OSG_CHOL_ELIM")) : 4;
     // the compact per-block factor (k_linearize<.., true>, k_schur_rows_c, k_update_c) unless OSG_LBA_HPL=1
-    // stores Hpl whole; the Hpl-reading A/B variants above run on the whole-Hpl form
-    static const bool hpl_full = (getenv("OSG_LBA_HPL") && atoi(getenv("OSG_LBA_HPL")) == 1) || schur_valu ||
-                                 schur_stage || schur_direct || update_stage || !update_coop;
+    // stores Hpl whole (k_linearize<.., false>, k_schur_rows, k_update): the independent check of the compact form
+    static const bool hpl_full = getenv("OSG_LBA_HPL") && atoi(getenv("OSG_LBA_HPL")) == 1;
     const bool compact = !hpl_full;
-    // k_schur_rows_c with its gathers two groups ahead (the default since late r06: 6.40 against 6.47 ms per
-    // 14 launches, gpurun_out/r06k); OSG_SCHUR_PF=1 one group ahead (A/B runs; the same sums)
-    // OSG_SCHUR_PF=3: also the chunk descriptors four chunks ahead (A/B)
-    static const int schur_pf = getenv("OSG_SCHUR_PF") ? std::min(4, std::max(1, atoi(getenv("OSG_SCHUR_PF")))) : 2;
-    // OSG_SCHUR_WPE=5: k_schur_rows_c allocated for 5 waves per SIMD (92 VGPRs, no spills) instead of 6 (A/B)
-    static const bool schur_wpe5 = getenv("OSG_SCHUR_WPE") && atoi(getenv("OSG_SCHUR_WPE")) == 5;
-    // OSG_SCHUR_HOIST=1: k_schur_rows_c's first gathers issued inside the staging (A/B)
-    static const bool schur_hoist = getenv("OSG_SCHUR_HOIST") && atoi(getenv("OSG_SCHUR_HOIST")) == 1;
     const auto tp0 = std::chrono::steady_clock::now();
     auto ms_since = [&](std::chrono::steady_clock::time_point t) {
         return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
@@ -3893,15 +3128,9 @@ int lba_batch(osg_ctx *ctx, const osg_ba_graph *graphs, osg_ba_result *results, 
     bool any_multi = false;
     int mx_nhe = 0;
     size_t mx_init = 0;  // k_init_state's extent: the largest 7 np / 3 npt of the batch
-    int mx_ge = 0, mx_gl = 1, mx_gu = 0, mx_nblk = 0, mx_nhp = 0, mx_chunks = 0, mx_pairs = 0, mx_red = 0, mx_rs = 0;
-    // XCD-aware graph placement (LBA_GRAPH) for batches of >= 8 graphs: OSG_LBA_XCD=1.  Off by
-    // default: measured slower (64 C4 windows: k_schur_rows 10.4 vs 8.9 ms, k_linearize 5.4 vs 4.4 ms
-    // per 14-step batch; profiles/r02_lba_xcd.txt)
-    static const bool xcd_env = getenv("OSG_LBA_XCD") && atoi(getenv("OSG_LBA_XCD")) == 1;
-    const bool xcd = xcd_env && NA >= 8;
+    int mx_ge = 0, mx_gu = 0, mx_nblk = 0, mx_nhp = 0, mx_chunks = 0, mx_pairs = 0, mx_red = 0, mx_rs = 0;
     bool large = false;  // some graph's reduced system is past CMAX
     bool any_dense = false;  // some graph is factored by k_chol_dense (n <= CMAX, at least one free pose)
-    bool any_env = false;    // ... by k_chol_env (past CMAX, a narrow envelope)
     bool any_col = false;    // ... by column launches (the others)
     bool huge_col = false;   // ... and past CMAX_LARGE (k_back_step)
     for (int a = 0; a < NA; a++) {
@@ -3918,7 +3147,6 @@ int lba_batch(osg_ctx *ctx, const osg_ba_graph *graphs, osg_ba_result *results, 
         D.npairs = h.npairs;
         D.n_cams = h.G->n_cams;
         D.n_graphs = NA;
-        D.xcd_map = xcd ? 1 : 0;
         D.pose_fixed = osg_dptr<uint8_t>(din, o.fixed);
         D.e_pose = osg_dptr<int32_t>(din, o.epose);
         D.e_point = osg_dptr<int32_t>(din, o.epoint);
@@ -3932,9 +3160,7 @@ int lba_batch(osg_ctx *ctx, const osg_ba_graph *graphs, osg_ba_result *results, 
         D.hub_stereo = h.G->huber_stereo > 0.f ? h.G->huber_stereo : (float)std::sqrt(7.815);
         large |= 6 * h.nhp > CMAX;
         if (chol_dense && h.nhp > 0 && 6 * h.nhp <= CMAX) D.chol_fused = 1;
-        else if (chol_env && 6 * h.nhp > CMAX && 6 * h.nhp <= ENV_NX && h.max_col_rows <= ENV_T - 1) D.chol_fused = 2;
         any_dense |= D.chol_fused == 1;
-        any_env |= D.chol_fused == 2;
         any_col |= h.nhp > 0 && D.chol_fused == 0;
         huge_col |= 6 * h.nhp > CMAX_LARGE && D.chol_fused == 0;
         D.pose_h = osg_dptr<int32_t>(din, o.poseh);
@@ -3974,12 +3200,10 @@ int lba_batch(osg_ctx *ctx, const osg_ba_graph *graphs, osg_ba_result *results, 
         D.rs_chunk = osg_dptr<int32_t>(din, o.rsc);
         D.hp_rs_start = osg_dptr<int32_t>(din, o.hprs);
         D.ge = h.ge;
-        D.gl = h.gl;
         D.gll = h.gll;
         D.gu = h.gu;
         D.nblk_red = h.nblk_red;
         D.user_lambda = h.G->user_lambda_init;
-        D.dinv_inline = schur_point ? 0 : 1;
         size_t off = 0;
         carve_state(dst + st_off[a], off, h, &D, prof_ts, compact);
         D.ctl = d_ctl + a;
@@ -3988,7 +3212,6 @@ int lba_batch(osg_ctx *ctx, const osg_ba_graph *graphs, osg_ba_result *results, 
         D.point0 = osg_dptr<double>(din, o.point0);
         mx_init = std::max(mx_init, std::max(7 * (size_t)h.np, 3 * (size_t)h.npt));
         mx_ge = std::max(mx_ge, h.ge);
-        mx_gl = std::max(mx_gl, h.gl);
         mx_gll = std::max(mx_gll, h.gll);
         any_multi |= h.multi;
         mx_gu = std::max(mx_gu, h.gu);
@@ -4003,12 +3226,9 @@ int lba_batch(osg_ctx *ctx, const osg_ba_graph *graphs, osg_ba_result *results, 
     OSG_HIP_CHECK(ctx, hipMemcpyAsync(d_dev, h_dev, dev_bytes, hipMemcpyHostToDevice, ctx->stream));
     {
         const int gi = (int)std::max<size_t>((mx_init + EB - 1) / EB, 1);
-        hipLaunchKernelGGL(k_init_state, xcd ? dim3(8 * gi, (NA + 7) / 8) : dim3(gi, NA), dim3(EB), 0, ctx->stream, d_dev);
+        hipLaunchKernelGGL(k_init_state, dim3(gi, NA), dim3(EB), 0, ctx->stream, d_dev);
     }
-    if (mx_nhe > 0 && !pose_red_gather) {
-        const dim3 g = xcd ? dim3(8 * ((mx_nhe + EB - 1) / EB), (NA + 7) / 8) : dim3((mx_nhe + EB - 1) / EB, NA);
-        hipLaunchKernelGGL(k_hp_rec, g, dim3(EB), 0, ctx->stream, d_dev);
-    }
+    if (mx_nhe > 0) hipLaunchKernelGGL(k_hp_rec, dim3((mx_nhe + EB - 1) / EB, NA), dim3(EB), 0, ctx->stream, d_dev);
     const double t_upload = ms_since(tp0) - t_struct;
     const auto tp1 = std::chrono::steady_clock::now();
 
@@ -4048,57 +3268,29 @@ int lba_batch(osg_ctx *ctx, const osg_ba_graph *graphs, osg_ba_result *results, 
         // the per-step control through a copy kernel in the stream's own queue (osg_upload), not the
         // copy engine: the first kernel of the step then does not wait for an SDMA completion signal
         OSG_RC(osg_upload(ctx, d_ctl, h_ctl, ctl_bytes));
-        const dim3 yb = xcd ? dim3(8, (NA + 7) / 8) : dim3(1, NA);
-        auto gx = [&](int n) { return xcd ? dim3(8 * std::max(n, 1), (NA + 7) / 8) : dim3(std::max(n, 1), NA); };
+        const dim3 yb(1, NA);  // one workgroup per graph
+        auto gx = [&](int n) { return dim3(std::max(n, 1), NA); };
         LBA_MARK(KT_ERR);
         hipLaunchKernelGGL(k_errors, gx(mx_ge), dim3(EB), 0, ctx->stream, d_dev, 1);
         LBA_MARK(KT_LIN);
-        if (compact) {
-            if (any_multi) hipLaunchKernelGGL((k_linearize<true, 1, true>), gx(mx_gll), dim3(EB), 0, ctx->stream, d_dev);
-            else if (lin_wpe4) hipLaunchKernelGGL((k_linearize<false, 4, true>), gx(mx_gll), dim3(EB), 0, ctx->stream, d_dev);
-            else hipLaunchKernelGGL((k_linearize<false, 1, true>), gx(mx_gll), dim3(EB), 0, ctx->stream, d_dev);
-        } else if (any_multi) hipLaunchKernelGGL(k_linearize<true>, gx(mx_gll), dim3(EB), 0, ctx->stream, d_dev);
-        else if (lin_wpe4) hipLaunchKernelGGL((k_linearize<false, 4>), gx(mx_gll), dim3(EB), 0, ctx->stream, d_dev);
-        else hipLaunchKernelGGL(k_linearize<false>, gx(mx_gll), dim3(EB), 0, ctx->stream, d_dev);
-        LBA_MARK(KT_POSE);
-        if (mx_nhp > 0) {
-            if (pose_red_gather) hipLaunchKernelGGL(k_pose_red<false>, gx(mx_nhp), dim3(EB), 0, ctx->stream, d_dev);
-            else hipLaunchKernelGGL(k_pose_red<true>, gx(mx_nhp), dim3(EB), 0, ctx->stream, d_dev);
+        {
+            auto lin = compact ? (any_multi ? k_linearize<true, true> : k_linearize<false, true>)
+                               : (any_multi ? k_linearize<true, false> : k_linearize<false, false>);
+            hipLaunchKernelGGL(lin, gx(mx_gll), dim3(EB), 0, ctx->stream, d_dev);
         }
+        LBA_MARK(KT_POSE);
+        if (mx_nhp > 0) hipLaunchKernelGGL(k_pose_red, gx(mx_nhp), dim3(EB), 0, ctx->stream, d_dev);
         LBA_MARK(KT_LINIT);
         hipLaunchKernelGGL(k_lambda_init, yb, dim3(64), 0, ctx->stream, d_dev);
-        LBA_MARK(KT_SPOINT);
-        if (schur_point) hipLaunchKernelGGL(k_schur_point, gx(mx_gl), dim3(EB), 0, ctx->stream, d_dev);
+        LBA_MARK(KT_SPOINT);  // the slot of the retired per-landmark Dinv kernel: brackets nothing
         if (mx_nhp > 0) {
             LBA_MARK(KT_SROWS);
-            if (compact) {
-                auto sr = schur_pf == 4 ? k_schur_rows_c<4, 6>
-                          : schur_pf == 3 ? (schur_wpe5 ? k_schur_rows_c<3, 5> : k_schur_rows_c<3, 6>)
-                          : schur_pf == 2 ? (schur_wpe5 ? k_schur_rows_c<2, 5>
-                                                        : (schur_hoist ? k_schur_rows_c<2, 6, true> : k_schur_rows_c<2, 6>))
-                                          : k_schur_rows_c<1, 6>;
-                hipLaunchKernelGGL(sr, gx(mx_rs), dim3(RT), 0, ctx->stream, d_dev);
-            }
-            else if (schur_valu) hipLaunchKernelGGL(k_schur_rows<true>, gx(mx_rs), dim3(RT), 0, ctx->stream, d_dev);
-            else if (schur_stage) hipLaunchKernelGGL(k_schur_rows_st, gx(mx_rs), dim3(RT2), 0, ctx->stream, d_dev);
-            else if (schur_direct)
-                hipLaunchKernelGGL((k_schur_rows<false, true>), gx(mx_rs), dim3(RT), 0, ctx->stream, d_dev);
-            else hipLaunchKernelGGL(k_schur_rows<false>, gx(mx_rs), dim3(RT), 0, ctx->stream, d_dev);
+            hipLaunchKernelGGL(compact ? k_schur_rows_c : k_schur_rows, gx(mx_rs), dim3(RT), 0, ctx->stream, d_dev);
             LBA_MARK(KT_SPAIRS);
             hipLaunchKernelGGL(k_schur_pairs, gx((int)(((size_t)mx_pairs * 64 + 255) / 256)), dim3(256), 0, ctx->stream, d_dev);
             LBA_MARK(KT_CHOL);
-            // dense systems (n <= CMAX) in one k_chol_dense workgroup per graph, narrow envelopes in one
-            // k_chol_env workgroup (with its backward solve), the others by column launches
-            if (any_dense) {
-                if (chol_dense_nt == 512) hipLaunchKernelGGL((k_chol_dense<512, 3, 2>), yb, dim3(512), 0, ctx->stream, d_dev);
-                else hipLaunchKernelGGL((k_chol_dense<1024, 2, 2>), yb, dim3(1024), 0, ctx->stream, d_dev);
-            }
-            if (any_env) {
-                if (chol_elim == 4) hipLaunchKernelGGL(k_chol_env<4>, yb, dim3(CD_T), 0, ctx->stream, d_dev);
-                else hipLaunchKernelGGL(k_chol_env<2>, yb, dim3(CD_T), 0, ctx->stream, d_dev);
-            }
-            const char *tp = getenv("OSG_TRAIL_PRE");  // tests pin the variant (read per call)
-            const bool trail_pre = !(tp && atoi(tp) == 0);
+            // dense systems (n <= CMAX) in one k_chol_dense workgroup per graph, the others by column launches
+            if (any_dense) hipLaunchKernelGGL(k_chol_dense, yb, dim3(CD_T), 0, ctx->stream, d_dev);
             if (any_col) for (int jb = 0; jb < mx_red; jb++) {  // row blocks at and below the diagonal block
                 // past CMAX only the envelope's rows: grids sized by the largest reach of any graph
                 int rows = 0, m = 0;
@@ -4112,25 +3304,14 @@ int lba_batch(osg_ctx *ctx, const osg_ba_graph *graphs, osg_ba_result *results, 
                     if (big) m = std::max(m, nr);
                 }
                 if (rows == 0) continue;
-                if (chol_elim == 4) hipLaunchKernelGGL(k_chol_col<4>, gx(rows), dim3(256), 0, ctx->stream, d_dev, jb);
-                else hipLaunchKernelGGL(k_chol_col<2>, gx(rows), dim3(256), 0, ctx->stream, d_dev, jb);
-                if (large && m > 0) {
-                    if (trail_pre)
-                        hipLaunchKernelGGL(k_chol_trail<true>, gx(m * (m + 1) / 2), dim3(256), 0, ctx->stream, d_dev, jb);
-                    else
-                        hipLaunchKernelGGL(k_chol_trail<false>, gx(m * (m + 1) / 2), dim3(256), 0, ctx->stream, d_dev, jb);
-                }
+                hipLaunchKernelGGL(k_chol_col, gx(rows), dim3(256), 0, ctx->stream, d_dev, jb);
+                if (large && m > 0)
+                    hipLaunchKernelGGL(k_chol_trail, gx(m * (m + 1) / 2), dim3(256), 0, ctx->stream, d_dev, jb);
             }
             LBA_MARK(KT_BACK);
             hipLaunchKernelGGL(k_chol_back, yb, dim3(1024), 0, ctx->stream, d_dev);
-            if (any_col) {
-                const char *lp = getenv("OSG_BACKL_PRE");  // tests pin the variant (read per call)
-                if (!(lp && atoi(lp) == 0)) hipLaunchKernelGGL(k_chol_back_large<true>, yb, dim3(1024), 0, ctx->stream, d_dev);
-                else hipLaunchKernelGGL(k_chol_back_large<false>, yb, dim3(1024), 0, ctx->stream, d_dev);
-            }
+            if (any_col) hipLaunchKernelGGL(k_chol_back_large, yb, dim3(1024), 0, ctx->stream, d_dev);
             if (huge_col) {
-                const char *bp = getenv("OSG_BACK_PRE");  // tests pin the variant (read per call)
-                const bool back_pre = !(bp && atoi(bp) == 0);
                 for (int step = 0; step < mx_red; step++) {
                     int cols = 0;
                     for (int a = 0; a < NA; a++) {
@@ -4138,19 +3319,13 @@ int lba_batch(osg_ctx *ctx, const osg_ba_graph *graphs, osg_ba_result *results, 
                         const int bi = h.nblk_red - 1 - step;
                         if (6 * h.nhp > CMAX_LARGE && bi >= 0) cols = std::max(cols, CB * (bi - h.blk_first[bi]));
                     }
-                    if (back_pre)
-                        hipLaunchKernelGGL(k_back_step<true>, gx(1 + (cols + BSC - 1) / BSC), dim3(BSC), 0, ctx->stream, d_dev, step);
-                    else
-                        hipLaunchKernelGGL(k_back_step<false>, gx(1 + (cols + BSC - 1) / BSC), dim3(BSC), 0, ctx->stream, d_dev, step);
+                    hipLaunchKernelGGL(k_back_step, gx(1 + (cols + BSC - 1) / BSC), dim3(BSC), 0, ctx->stream, d_dev, step);
                 }
                 hipLaunchKernelGGL(k_back_copy, gx((6 * mx_nhp + EB - 1) / EB), dim3(EB), 0, ctx->stream, d_dev);
             }
         }
         LBA_MARK(KT_UPD);
-        if (compact) hipLaunchKernelGGL(k_update_c, gx(mx_gu), dim3(EB), 0, ctx->stream, d_dev);
-        else if (update_stage) hipLaunchKernelGGL(k_update<true>, gx(mx_gu), dim3(EB), 0, ctx->stream, d_dev);
-        else if (update_coop) hipLaunchKernelGGL((k_update<false, true>), gx(mx_gu), dim3(EB), 0, ctx->stream, d_dev);
-        else hipLaunchKernelGGL(k_update<false>, gx(mx_gu), dim3(EB), 0, ctx->stream, d_dev);
+        hipLaunchKernelGGL(compact ? k_update_c : k_update, gx(mx_gu), dim3(EB), 0, ctx->stream, d_dev);
         LBA_MARK(KT_ERR);
         hipLaunchKernelGGL(k_errors, gx(mx_ge), dim3(EB), 0, ctx->stream, d_dev, 0);
         LBA_MARK(KT_RED);
@@ -4292,8 +3467,7 @@ int lba_batch(osg_ctx *ctx, const osg_ba_graph *graphs, osg_ba_result *results, 
     for (int a = 0; a < NA; a++) h_ctl[a] = LbaCtl{M_FIN, H[act[a]].sel, 0.0};
     OSG_HIP_CHECK(ctx, hipMemcpyAsync(d_ctl, h_ctl, ctl_bytes, hipMemcpyHostToDevice, ctx->stream));
     LBA_MARK(KT_CLASS);
-    hipLaunchKernelGGL(k_classify, xcd ? dim3(8 * std::max(mx_ge, 1), (NA + 7) / 8) : dim3(std::max(mx_ge, 1), NA),
-                       dim3(EB), 0, ctx->stream, d_dev);
+    hipLaunchKernelGGL(k_classify, dim3(std::max(mx_ge, 1), NA), dim3(EB), 0, ctx->stream, d_dev);
     LBA_MARK(KT_END);
 #undef LBA_MARK
     OSG_HIP_CHECK(ctx, hipGetLastError());

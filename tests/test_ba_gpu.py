@@ -285,18 +285,26 @@ def _gba_variant_graph():
     return op.synth_gba_graph(rng, n_kf=30, n_points=3000, bRobust=False, stereo_frac=0.3)
 
 
-def _variant_child(env):
-    """LocalBundleAdjustmentBatch of _lba_batch_graphs and BundleAdjustment of _gba_variant_graph in a
-    child process under `env` (the kernel knobs are read once per process)."""
+def _env_map_graphs():
+    """Reduced systems past CMAX (n = 894) with narrow envelopes: a 150-KF open map and one closed into a
+    loop (at most 7 envelope row blocks below a column block)."""
+    return [op.synth_map_graph(np.random.default_rng(71), n_kf=150, n_points=12000, loop=False),
+            op.synth_map_graph(np.random.default_rng(72), n_kf=150, n_points=12000, loop=True)]
+
+
+def _ba_child(env, maps=False):
+    """LocalBundleAdjustmentBatch of _lba_batch_graphs, then BundleAdjustment of _gba_variant_graph (or, with
+    maps, of each of _env_map_graphs) in a child process under `env` (the kernel knobs are read once per
+    process)."""
     import subprocess
     import sys
-    out = f"/tmp/_osg_lba_variant_{os.getpid()}_{abs(hash(tuple(sorted(env.items()))))}.npz"
+    out = f"/tmp/_osg_ba_child_{os.getpid()}_{abs(hash(tuple(sorted(env.items()))))}.npz"
     code = ("import numpy as np\n"
             "from orb_slam3_comments_ghr_amd import Context, optimizer as op\n"
-            "from tests.test_ba_gpu import _lba_batch_graphs\n"
-            "from tests.test_ba_gpu import _gba_variant_graph\n"
+            "from tests.test_ba_gpu import _lba_batch_graphs, _gba_variant_graph, _env_map_graphs\n"
             "o = op.Optimizer(Context(0))\n"
-            "res = o.LocalBundleAdjustmentBatch(_lba_batch_graphs()) + [o.BundleAdjustment(_gba_variant_graph())]\n"
+            f"gba = {'_env_map_graphs()' if maps else '[_gba_variant_graph()]'}\n"
+            "res = o.LocalBundleAdjustmentBatch(_lba_batch_graphs()) + [o.BundleAdjustment(G) for G in gba]\n"
             f"np.savez('{out}', **{{f'p{{i}}': r.pose for i, r in enumerate(res)}},\n"
             "         **{f'q{i}': r.point for i, r in enumerate(res)},\n"
             "         it=np.array([[r.iterations, r.trials] for r in res]),\n"
@@ -308,48 +316,6 @@ def _variant_child(env):
     got = dict(np.load(out))
     os.remove(out)
     return got
-
-
-# variants of the whole-Hpl form (OSG_LBA_HPL=1): each against that form's default, in two children
-_HPL_VARIANTS = [{"OSG_SCHUR_STAGE": "1"}, {"OSG_SCHUR_DIRECT": "1"}, {"OSG_UPDATE_STAGE": "1"}, {"OSG_UPDATE_COOP": "0"}]
-
-
-@pytest.mark.parametrize("env", [{"OSG_POSE_RED_GATHER": "1"}, {"OSG_SCHUR_POINT": "1"}, {"OSG_LIN_WPE": "4"},
-                                 {"OSG_SCHUR_PF": "1"}, {"OSG_SCHUR_PF": "3"}, {"OSG_SCHUR_PF": "4"},
-                                 {"OSG_SCHUR_WPE": "5"}, {"OSG_LBA_LREC": "1"},
-                                 {"OSG_SCHUR_HOIST": "1"}, {"OSG_LBA_LMIDENT": "0"}]
-                         + _HPL_VARIANTS,
-                         ids=lambda e: "-".join(f"{k[4:]}={v}" for k, v in e.items()))
-def test_lba_schur_variants_bit_identical(ctx, env):
-    """Kernel variants that read their inputs differently but compute the same products in the same
-    order give the same results bit for bit.  On the default compact per-block factor: k_pose_red's edge
-    inputs gathered through hp_e against the pose-major records (k_hp_rec), Dinv from k_schur_point
-    against Dinv formed by its readers, k_linearize compiled for 4 waves per SIMD, and k_schur_rows_c with
-    its gathers one group ahead (OSG_SCHUR_PF=1) against two (the default), with the chunk descriptors
-    four chunks ahead (OSG_SCHUR_PF=3), with its descriptors preloaded one per lane and branch-free loads
-    (OSG_SCHUR_PF=4), and allocated for 5 waves per SIMD (OSG_SCHUR_WPE=5); the landmark
-    terms in one 128-byte record per landmark (OSG_LBA_LREC=1) against three arrays, and k_schur_rows_c's first
-    gathers issued inside its staging (OSG_SCHUR_HOIST=1), and k_linearize through lm_e when the edges are in
-    landmark order (OSG_LBA_LMIDENT=0) against its identity shortcut.  On the whole-Hpl
-    form (OSG_LBA_HPL=1, which the Hpl-reading variants select): the Schur product's LDS-staged partner
-    spans (k_schur_rows_st) and per-lane loads against the per-group gathers (k_schur_rows), and
-    k_update's Hpl blocks through LDS pieces or per-thread walks against one thread per block.  The GBA
-    graph has per-edge robust flags off (bRobust = false)."""
-    got = _variant_child(env)
-    if env in _HPL_VARIANTS:
-        want = _variant_child({"OSG_LBA_HPL": "1"})
-    else:
-        o = op.Optimizer(ctx)
-        res = o.LocalBundleAdjustmentBatch(_lba_batch_graphs()) + [o.BundleAdjustment(_gba_variant_graph())]
-        want = {"it": np.array([[r.iterations, r.trials] for r in res]),
-                "chi": np.array([[r.chi2_initial, r.chi2_final] for r in res])}
-        for i, r in enumerate(res):
-            want[f"p{i}"], want[f"q{i}"] = r.pose, r.point
-    np.testing.assert_array_equal(got["it"], want["it"])
-    np.testing.assert_array_equal(got["chi"], want["chi"])
-    for i in range(len(got["it"])):
-        np.testing.assert_array_equal(got[f"p{i}"], want[f"p{i}"])
-        np.testing.assert_array_equal(got[f"q{i}"], want[f"q{i}"])
 
 
 def test_lba_compact_factor_vs_whole_hpl(ctx):
@@ -359,7 +325,7 @@ def test_lba_compact_factor_vs_whole_hpl(ctx):
     and the 5- to 50-KF windows) and the bRobust = false GBA graph."""
     o = op.Optimizer(ctx)
     res = o.LocalBundleAdjustmentBatch(_lba_batch_graphs()) + [o.BundleAdjustment(_gba_variant_graph())]
-    full = _variant_child({"OSG_LBA_HPL": "1"})
+    full = _ba_child({"OSG_LBA_HPL": "1"})
     np.testing.assert_array_equal(full["it"], [[r.iterations, r.trials] for r in res])
     np.testing.assert_allclose(full["chi"], [[r.chi2_initial, r.chi2_final] for r in res], rtol=1e-12, atol=0)
     for i, r in enumerate(res):
@@ -367,67 +333,24 @@ def test_lba_compact_factor_vs_whole_hpl(ctx):
         np.testing.assert_allclose(full[f"q{i}"], r.point, atol=1e-9, rtol=0)
 
 
-def _env_map_graphs():
-    """Reduced systems past CMAX (n = 894) with narrow envelopes (k_chol_env): a 150-KF open map and one
-    closed into a loop (at most 7 envelope row blocks below a column block)."""
-    return [op.synth_map_graph(np.random.default_rng(71), n_kf=150, n_points=12000, loop=False),
-            op.synth_map_graph(np.random.default_rng(72), n_kf=150, n_points=12000, loop=True)]
-
-
-def _chol_child(env):
-    """LocalBundleAdjustmentBatch of _lba_batch_graphs and BundleAdjustment of _env_map_graphs in a child
-    process under `env` (the factorisation knobs are read once per process)."""
-    import subprocess
-    import sys
-    out = f"/tmp/_osg_chol_{os.getpid()}.npz"
-    code = ("import numpy as np\n"
-            "from orb_slam3_comments_ghr_amd import Context, optimizer as op\n"
-            "from tests.test_ba_gpu import _lba_batch_graphs, _env_map_graphs\n"
-            "o = op.Optimizer(Context(0))\n"
-            "res = o.LocalBundleAdjustmentBatch(_lba_batch_graphs()) + [o.BundleAdjustment(G) for G in _env_map_graphs()]\n"
-            f"np.savez('{out}', **{{f'p{{i}}': r.pose for i, r in enumerate(res)}},\n"
-            "         **{f'q{i}': r.point for i, r in enumerate(res)},\n"
-            "         it=np.array([[r.iterations, r.trials] for r in res]),\n"
-            "         chi=np.array([[r.chi2_initial, r.chi2_final] for r in res]))\n")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-c", code], cwd=root, env=dict(os.environ, **env), capture_output=True,
-                       text=True, timeout=180)
-    assert r.returncode == 0, r.stderr[-2000:]
-    got = dict(np.load(out))
-    os.remove(out)
-    return got
-
-
 def test_lba_chol_fused_vs_column_launches(ctx):
-    """The one-workgroup factorisations against the per-column k_chol_col (+ k_chol_trail) launches:
-    * k_chol_dense (LocalBundleAdjustment windows, the default) against OSG_CHOL_DENSE=0: the same blocked
-      LL^T with its sums in another order, so identical iteration / trial counts and states equal to rounding;
-    * k_chol_env (OSG_CHOL_ENV=1: maps past CMAX with narrow envelopes, its own backward solve) against the
-      default column launches: the same products in the same order as k_chol_col / k_chol_trail /
-      k_chol_back_large, so bit-identical;
-    * the column launches with the two-column elimination (OSG_CHOL_ELIM=2) against the default four."""
+    """The one-workgroup factorisation k_chol_dense (LocalBundleAdjustment windows, the default) against the
+    per-column k_chol_col launches (OSG_CHOL_DENSE=0): the same blocked LL^T with its sums in another order,
+    so identical iteration / trial counts and states equal to rounding.  The maps past CMAX take the column
+    launches (k_chol_col + k_chol_trail, k_chol_back_large) in both processes: bit-identical."""
     o = op.Optimizer(ctx)
     lba = o.LocalBundleAdjustmentBatch(_lba_batch_graphs())
     maps = [o.BundleAdjustment(G) for G in _env_map_graphs()]
-    col = _chol_child({"OSG_CHOL_DENSE": "0"})
-    env = _chol_child({"OSG_CHOL_ENV": "1"})
-    two = _chol_child({"OSG_CHOL_ELIM": "2"})
-    # the column launches' diagonal tiles eliminated two columns per barrier instead of four: the same
-    # factor to rounding
-    np.testing.assert_array_equal(two["it"], [[r.iterations, r.trials] for r in lba + maps])
-    for i, r in enumerate(lba + maps):
-        np.testing.assert_allclose(two[f"p{i}"], r.pose, atol=1e-8, rtol=0)
-        np.testing.assert_allclose(two[f"q{i}"], r.point, atol=1e-8, rtol=0)
-    for got in (col, env):
-        np.testing.assert_array_equal(got["it"], [[r.iterations, r.trials] for r in lba + maps])
+    col = _ba_child({"OSG_CHOL_DENSE": "0"}, maps=True)
+    np.testing.assert_array_equal(col["it"], [[r.iterations, r.trials] for r in lba + maps])
     np.testing.assert_allclose(col["chi"][:len(lba)], [[r.chi2_initial, r.chi2_final] for r in lba], rtol=1e-12, atol=0)
     for i, r in enumerate(lba):
         np.testing.assert_allclose(col[f"p{i}"], r.pose, atol=1e-9, rtol=0)
         np.testing.assert_allclose(col[f"q{i}"], r.point, atol=1e-9, rtol=0)
-    for i, r in enumerate(lba + maps):  # k_chol_env's maps, and the dense windows under the same default
-        np.testing.assert_array_equal(env["chi"][i], [r.chi2_initial, r.chi2_final])
-        np.testing.assert_array_equal(env[f"p{i}"], r.pose)
-        np.testing.assert_array_equal(env[f"q{i}"], r.point)
+    for i, r in enumerate(maps, start=len(lba)):
+        np.testing.assert_array_equal(col["chi"][i], [r.chi2_initial, r.chi2_final])
+        np.testing.assert_array_equal(col[f"p{i}"], r.pose)
+        np.testing.assert_array_equal(col[f"q{i}"], r.point)
 
 
 def test_lba_batch_c4_windows(ctx, oracle):
@@ -495,27 +418,6 @@ def test_gba_map_loop_closed(ctx, oracle, n_kf, n_pts):
     assert first & last, "the loop joins the first and the last keyframes"
     got, ref = check_gba(ctx, oracle, G)
     assert got.chi2_final < 0.2 * got.chi2_initial and got.iterations >= 5
-
-
-@pytest.mark.parametrize("var,n_kf,n_pts", [("OSG_BACK_PRE", 1500, 150000), ("OSG_TRAIL_PRE", 1500, 150000),
-                                           ("OSG_BACKL_PRE", 400, 40000)])
-def test_gba_back_step_prefetch_bit_identical(ctx, monkeypatch, var, n_kf, n_pts):
-    """k_back_step (the back-substitution past 1024 free KeyFrames) with its L and Linv loads issued before
-    y' (default) and in the previous order (OSG_BACK_PRE=0); k_chol_trail with its target tile loaded
-    before the MFMA (default) and after it (OSG_TRAIL_PRE=0): the same sums in the same order, so the
-    1500-KF loop-closed map ends bit for bit the same.  k_chol_back_large (400 KF) with the next block's Linv
-    loaded during the current block (default) and at the block's start (OSG_BACKL_PRE=0): likewise."""
-    G = op.synth_map_graph(np.random.default_rng(4200 + n_kf), n_kf=n_kf, n_points=n_pts, loop=True)
-    res = {}
-    for v in ("0", "1"):
-        monkeypatch.setenv(var, v)
-        res[v] = op.Optimizer(ctx).BundleAdjustment(G)
-    a, b = res["0"], res["1"]
-    assert (a.iterations, a.trials) == (b.iterations, b.trials)
-    assert a.chi2_initial == b.chi2_initial and a.chi2_final == b.chi2_final
-    np.testing.assert_array_equal(a.pose, b.pose)
-    np.testing.assert_array_equal(a.point, b.point)
-    np.testing.assert_array_equal(a.edge_bad, b.edge_bad)
 
 
 def test_gba_loop_map_device_bytes_on_envelope():

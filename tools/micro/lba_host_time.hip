@@ -47,11 +47,11 @@ extern "C" unsigned long long lba_host_struct_hash(const osg_ba_graph *G)
                     &H.point_h, &H.hl_point, &H.lm_e_start, &H.lm_e, &H.lg_start, &H.lm_b_start, &H.blk_pose,
                     &H.edge_blk, &H.blk_lm, &H.hp_e_start, &H.hp_e, &H.hp_b_start, &H.hp_b, &H.pair_start,
                     &pb, &H.chunk_start, &H.pair_chunk, &H.pair_rank, &H.rs_pose, &H.rs_rank0,
-                    &H.rs_chunk_start, &H.rs_chunk, &H.hp_rs_start, &H.rs_order, &H.rs_cdesc, &H.rs_info, &H.hp_b_lm,
+                    &H.rs_chunk_start, &H.rs_chunk, &H.hp_rs_start, &H.rs_cdesc, &H.rs_info, &H.hp_b_lm,
                     &H.live_chunk, &H.env_off})
         mix(*v);
-    const int sc[] = {H.np, H.npt, H.ne, H.nhp, H.nhl, H.nblk, H.npairs, H.nchunks, H.ge, H.gl, H.gll, H.gu,
-                      H.nblk_red, H.npart, H.n_rs, H.max_col_rows, (int)H.multi};
+    const int sc[] = {H.np, H.npt, H.ne, H.nhp, H.nhl, H.nblk, H.npairs, H.nchunks, H.ge, H.gll, H.gu,
+                      H.nblk_red, H.npart, H.n_rs, (int)H.multi};
     for (int v : sc) h = (h ^ (unsigned)v) * 1099511628211ull;
     return h;
 }
@@ -95,5 +95,7 @@ extern "C" void lba_host_envelope(const osg_ba_graph *G, int *out3)
     if (build_structure(&ctx, G, H) != OSG_OK) return;
     out3[0] = 6 * H.nhp;
     out3[1] = H.nblk_red;
-    out3[2] = H.max_col_rows;
+    out3[2] = 0;
+    for (size_t j = 0; j + 1 < H.col_rows_start.size(); j++)
+        out3[2] = std::max(out3[2], H.col_rows_start[j + 1] - H.col_rows_start[j]);
 }
