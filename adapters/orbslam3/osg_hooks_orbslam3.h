@@ -7,6 +7,7 @@
 #include "Frame.h"
 #include "KeyFrame.h"
 #include "MapPoint.h"
+#include "Thirdparty/DBoW2/DUtils/Random.h"
 #include "Thirdparty/g2o/g2o/types/sim3.h"
 #include "osg_orbslam3.h"
 
@@ -289,6 +290,14 @@ struct OsgHooks {
         S = g2o::Sim3(Eigen::Quaterniond(q[3], q[0], q[1], q[2]), Eigen::Vector3d(t[0], t[1], t[2]), s);
     }
     static void zero_hessian(Eigen::Matrix<double, 7, 7> &H) { H = Eigen::MatrixXd::Zero(7, 7); }  // :4483
+    // Sim3Solver (ref:src/Sim3Solver.cc): the returned Eigen types and the reference's random source
+    using Matrix4f = Eigen::Matrix4f;
+    using Matrix3f = Eigen::Matrix3f;
+    using Vector3f = Eigen::Vector3f;
+    static Eigen::Matrix4f mat4(const float *m) { return Eigen::Map<const Eigen::Matrix<float, 4, 4, Eigen::RowMajor>>(m); }
+    static Eigen::Matrix3f mat3(const float *m) { return Eigen::Map<const Eigen::Matrix<float, 3, 3, Eigen::RowMajor>>(m); }
+    static Eigen::Vector3f vec3(const float *v) { return Eigen::Vector3f(v[0], v[1], v[2]); }
+    static int random_int(int min, int max) { return DUtils::Random::RandomInt(min, max); }  // :174
 };
 
 }  // namespace ORB_SLAM3

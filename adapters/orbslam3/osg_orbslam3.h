@@ -46,6 +46,8 @@
 #include "osg.h"
 #include "osg_ba.h"
 #include "osg_dbow.h"
+// the replay of Sim3Solver's sequential rule, shared with the library's selection launch
+#include "../../orb_slam3_comments_ghr_amd/csrc/sim3ransac_select.h"
 
 namespace osg_orbslam3 {
 
@@ -2143,6 +2145,216 @@ int optimize_sim3(KeyFrameT *pKF1, KeyFrameT *pKF2, std::vector<MapPointT *> &vp
     if (call(ctx, "osg_optimize_sim3", [&] { return osg_optimize_sim3(ctx, &g.p, &r); }) < 0) return 0;
     return apply_optimize_sim3<H>(g, r, vpMatches1, g2oS12, mAcumHessian);
 }
+
+// ------------------------------------------------------------------------------- Sim3Solver
+// Sim3Solver (ref:include/Sim3Solver.h, ref:src/Sim3Solver.cc) with the reference's public surface.  Hooks
+// (beside cam_point, index_in_keyframe and camera above):
+//   typename H::Matrix4f, H::Matrix3f, H::Vector3f                  what the reference returns (Eigen)
+//   static Matrix4f H::mat4(const float m[16])   row-major -> Matrix4f;  mat3(const float[9]), vec3(const float[3])
+//   static int H::random_int(int min, int max)                      DUtils::Random::RandomInt
+//
+// Sim3SolverGather is the constructor's slot filter (:38-118) as plain host code, in the reference's
+// order: no match -> skip; no MapPoint in KeyFrame 1 -> skip; either MapPoint bad -> skip; either
+// GetIndexInKeyFrame negative -> skip.  Kept as the reference computes them:
+//   * mvnMaxError1 / 2 are vectors of size_t: 9.210 * sigma2 (a double) is truncated to an integer;
+//   * the reference sets bDifferentKFs when vpKeyFrameMatchedMP is EMPTY (and then fills it with pKF2),
+//     so pKFm — whose keypoint and sigma belong to match 2 — is pKF2 in either case and a caller's
+//     vpKeyFrameMatchedMP is never read; mvX3Dc2 is in pKF2's frame;
+//   * no depth test.
+template <class H, class KeyFrameT, class MapPointT>
+struct Sim3SolverGather {
+    std::vector<float> p1c, p2c, max_err1, max_err2;
+    std::vector<size_t> mvnIndices1;
+    int mN1 = 0;
+    osg_camera cam1{}, cam2{};
+    void assign(KeyFrameT *pKF1, KeyFrameT *pKF2, const std::vector<MapPointT *> &vpMatched12,
+                std::vector<KeyFrameT *> vpKeyFrameMatchedMP)
+    {
+        bool bDifferentKFs = false;
+        if (vpKeyFrameMatchedMP.empty()) {
+            bDifferentKFs = true;
+            vpKeyFrameMatchedMP = std::vector<KeyFrameT *>(vpMatched12.size(), pKF2);
+        }
+        const std::vector<MapPointT *> vpKeyFrameMP1 = pKF1->GetMapPointMatches();
+        mN1 = (int)vpMatched12.size();
+        KeyFrameT *pKFm = pKF2;
+        for (int i1 = 0; i1 < mN1; i1++) {
+            if (!vpMatched12[i1]) continue;
+            MapPointT *pMP1 = vpKeyFrameMP1[i1];
+            MapPointT *pMP2 = vpMatched12[i1];
+            if (!pMP1) continue;
+            if (pMP1->isBad() || pMP2->isBad()) continue;
+            if (bDifferentKFs) pKFm = vpKeyFrameMatchedMP[i1];
+            const int indexKF1 = H::index_in_keyframe(pMP1, pKF1);
+            const int indexKF2 = H::index_in_keyframe(pMP2, pKFm);
+            if (indexKF1 < 0 || indexKF2 < 0) continue;
+            const auto &kp1 = pKF1->mvKeysUn[indexKF1];
+            const auto &kp2 = pKFm->mvKeysUn[indexKF2];
+            const float sigmaSquare1 = pKF1->mvLevelSigma2[kp1.octave];
+            const float sigmaSquare2 = pKFm->mvLevelSigma2[kp2.octave];
+            max_err1.push_back((float)(size_t)(9.210 * sigmaSquare1));
+            max_err2.push_back((float)(size_t)(9.210 * sigmaSquare2));
+            mvnIndices1.push_back((size_t)i1);
+            double x[3];
+            H::cam_point(pKF1, pMP1, x);
+            for (int k = 0; k < 3; k++) p1c.push_back((float)x[k]);
+            H::cam_point(pKF2, pMP2, x);
+            for (int k = 0; k < 3; k++) p2c.push_back((float)x[k]);
+        }
+        H::camera(*pKF1, false, cam1);
+        H::camera(*pKF2, false, cam2);
+    }
+};
+
+// The first iterate() / find() draws all mRansacMaxIts sample triples through H::random_int in the
+// reference's order (the reference stops drawing when it converges: the one observable difference) and
+// evaluates them in one osg_sim3_ransac call; that call and every later one replay their window with
+// osg_s3r_replay (csrc/sim3ransac_select.h), so mnIterations, mnBestInliers, bNoMore, bConverge and the
+// returned matrix are the reference's call by call.  On an ABI error the solver reports bNoMore.
+template <class H, class KeyFrameT, class MapPointT>
+class Sim3Solver {
+public:
+    using Matrix4f = typename H::Matrix4f;
+    using Matrix3f = typename H::Matrix3f;
+    using Vector3f = typename H::Vector3f;
+
+    Sim3Solver(KeyFrameT *pKF1, KeyFrameT *pKF2, const std::vector<MapPointT *> &vpMatched12,
+               const bool bFixScale = true, const std::vector<KeyFrameT *> vpKeyFrameMatchedMP = std::vector<KeyFrameT *>())
+        : mbFixScale(bFixScale)
+    {
+        g.assign(pKF1, pKF2, vpMatched12, vpKeyFrameMatchedMP);
+        set_best(nullptr);
+        SetRansacParameters();
+    }
+
+    void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300)
+    {
+        N = (int)g.mvnIndices1.size();
+        mRansacMinInliers = minInliers;
+        mRansacMaxIts = osg_s3r_iterations(probability, minInliers, N, maxIterations);
+        mnIterations = 0;
+        evaluated = false;
+    }
+
+    Matrix4f find(std::vector<bool> &vbInliers12, int &nInliers)
+    {
+        bool bFlag;
+        return iterate(mRansacMaxIts, bFlag, vbInliers12, nInliers);
+    }
+
+    Matrix4f iterate(int nIterations, bool &bNoMore, std::vector<bool> &vbInliers, int &nInliers)
+    {
+        bool bConverge;
+        const float eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+        const Matrix4f best = iterate(nIterations, bNoMore, vbInliers, nInliers, bConverge);
+        return bConverge ? best : H::mat4(eye);  // :212
+    }
+
+    Matrix4f iterate(int nIterations, bool &bNoMore, std::vector<bool> &vbInliers, int &nInliers, bool &bConverge)
+    {
+        const float eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+        bNoMore = false;
+        bConverge = false;
+        vbInliers = std::vector<bool>(g.mN1, false);
+        nInliers = 0;
+        if (N < mRansacMinInliers || N < 3 || !evaluate()) {  // fewer than 3 matches: nothing to draw
+            bNoMore = true;
+            return H::mat4(eye);
+        }
+        const osg_s3r_window w =
+            osg_s3r_replay(counts.data(), mRansacMaxIts, mRansacMinInliers, mnIterations, nIterations, mnBestInliers);
+        mnIterations = w.n_iterations;
+        mnBestInliers = w.n_best;
+        if (w.hyp >= 0) set_best(&sim3[13 * (size_t)w.hyp]);
+        if (w.converged) {
+            // the first hypothesis above min_inliers in draw order: the one the ABI call returned
+            nInliers = counts[w.hyp];
+            for (int i = 0; i < N; i++)
+                if (inlier[i]) vbInliers[g.mvnIndices1[i]] = true;
+            bConverge = true;
+            return H::mat4(mBestT12);
+        }
+        bNoMore = w.no_more != 0;
+        // the reference returns an uninitialised matrix when the window brought no new best: the current best
+        return H::mat4(mBestT12);
+    }
+
+    Matrix4f GetEstimatedTransformation() { return H::mat4(mBestT12); }
+    Matrix3f GetEstimatedRotation() { return H::mat3(mBestRotation); }
+    Vector3f GetEstimatedTranslation() { return H::vec3(mBestTranslation); }
+    float GetEstimatedScale() { return mBestScale; }
+
+    // state of the reference's members, for the tests
+    int iterations() const { return mnIterations; }
+    int best_inliers() const { return mnBestInliers; }
+    int max_iterations() const { return mRansacMaxIts; }
+    const Sim3SolverGather<H, KeyFrameT, MapPointT> &gather() const { return g; }
+
+private:
+    void set_best(const float *s)
+    {
+        const float id[13] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1};
+        if (!s) s = id;
+        for (int k = 0; k < 9; k++) mBestRotation[k] = s[k];
+        for (int k = 0; k < 3; k++) mBestTranslation[k] = s[9 + k];
+        mBestScale = s[12];
+        for (int i = 0; i < 3; i++) {
+            for (int j = 0; j < 3; j++) mBestT12[4 * i + j] = s[12] * s[3 * i + j];
+            mBestT12[4 * i + 3] = s[9 + i];
+        }
+        mBestT12[12] = mBestT12[13] = mBestT12[14] = 0.f;
+        mBestT12[15] = 1.f;
+    }
+
+    bool evaluate()
+    {
+        if (evaluated) return ok;
+        evaluated = true;
+        ok = false;
+        samples.resize(3 * (size_t)mRansacMaxIts);
+        std::vector<size_t> vAllIndices(N), vAvailableIndices;
+        for (int i = 0; i < N; i++) vAllIndices[i] = (size_t)i;
+        for (int it = 0; it < mRansacMaxIts; it++) {  // :169-183
+            vAvailableIndices = vAllIndices;
+            for (short i = 0; i < 3; ++i) {
+                const int randi = H::random_int(0, (int)vAvailableIndices.size() - 1);
+                samples[3 * (size_t)it + i] = (int32_t)vAvailableIndices[randi];
+                vAvailableIndices[randi] = vAvailableIndices.back();
+                vAvailableIndices.pop_back();
+            }
+        }
+        counts.assign(mRansacMaxIts, 0);
+        sim3.assign(13 * (size_t)mRansacMaxIts, 0.f);
+        inlier.assign(N, 0);
+        osg_sim3_ransac_problem p{};
+        p.n = N;
+        p.p1c = g.p1c.data();
+        p.p2c = g.p2c.data();
+        p.max_err1 = g.max_err1.data();
+        p.max_err2 = g.max_err2.data();
+        p.cam1 = g.cam1;
+        p.cam2 = g.cam2;
+        p.fix_scale = mbFixScale ? 1 : 0;
+        p.min_inliers = mRansacMinInliers;
+        p.n_hyp = mRansacMaxIts;
+        p.samples = samples.data();
+        osg_sim3_ransac_result r{};
+        r.inlier = inlier.data();
+        r.hyp_inliers = counts.data();
+        r.hyp_sim3 = sim3.data();
+        osg_ctx *ctx = thread_ctx();
+        ok = call(ctx, "osg_sim3_ransac", [&] { return osg_sim3_ransac(ctx, &p, &r); }) >= 0;
+        return ok;
+    }
+
+    Sim3SolverGather<H, KeyFrameT, MapPointT> g;
+    int N = 0, mnIterations = 0, mnBestInliers = 0, mRansacMinInliers = 6, mRansacMaxIts = 300;
+    bool mbFixScale, evaluated = false, ok = false;
+    std::vector<int32_t> samples, counts;
+    std::vector<float> sim3;
+    std::vector<uint8_t> inlier;
+    float mBestT12[16], mBestRotation[9], mBestTranslation[3], mBestScale = 1.f;
+};
 
 // ------------------------------------------------------------------------------ batched forms
 // B independent problems gathered from the reference's objects, solved in one launch (the

@@ -7,6 +7,8 @@
  *                                    outlier classification → estimates out)
  *   osg_bundle_adjustment          ← the g2o part of Optimizer::BundleAdjustment (global BA,
  *                                    ref:src/Optimizer.cc:2850-3237)
+ *   osg_optimize_sim3[_batch]      ← Optimizer::OptimizeSim3                   ref:src/Optimizer.cc:4213-4512
+ *   osg_sim3_ransac[_batch]        ← Sim3Solver::find / iterate                 ref:src/Sim3Solver.cc:146-433
  *
  * The caller (the ORB-SLAM3 side adapter) gathers the graph exactly as the
  * reference builds it — the same vertices, the same edges in the same insertion order, the same
@@ -120,6 +122,53 @@ int osg_optimize_sim3(struct osg_ctx *ctx, const osg_sim3_problem *p, osg_sim3_r
  * KeyFrame at once).  Returns the summed n_inliers or a negative OSG_E_* code.  No reference
  * counterpart. */
 int osg_optimize_sim3_batch(struct osg_ctx *ctx, const osg_sim3_problem *p, int32_t n, osg_sim3_result *r);
+
+/* ---- Sim3Solver ----------------------------------------------------------------------------
+ * Sim3Solver's RANSAC (ref:src/Sim3Solver.cc:146-433): every hypothesis — Horn's closed form on three
+ * sampled matches, then the two-way reprojection test of every match — is evaluated in parallel, and
+ * the reference's sequential rule (the first hypothesis in draw order with more than min_inliers
+ * inliers ends the search; otherwise the last one that attains the largest count is the best) is then
+ * replayed on the integer counts.  The caller applies the constructor's slot filter
+ * (ref:src/Sim3Solver.cc:38-118) and draws the sample triples. */
+typedef struct osg_sim3_ransac_problem {
+    int32_t n;                /* N: kept matches */
+    const float *p1c;         /* 3 per match: mvX3Dc1 */
+    const float *p2c;         /* 3 per match: mvX3Dc2 */
+    const float *max_err1;    /* mvnMaxError1: 9.210 sigma2 truncated to an integer, as a float */
+    const float *max_err2;    /* mvnMaxError2 */
+    osg_camera cam1, cam2;    /* pKF1->mpCamera, pKF2->mpCamera (type and p[] are read) */
+    int32_t fix_scale;        /* mbFixScale */
+    int32_t min_inliers;      /* mRansacMinInliers */
+    int32_t n_hyp;            /* H = mRansacMaxIts (>= 1) */
+    const int32_t *samples;   /* 3 per hypothesis, in draw order: distinct indices into [0, n) */
+} osg_sim3_ransac_problem;
+
+typedef struct osg_sim3_ransac_result {
+    int32_t converged;        /* a hypothesis with more than min_inliers inliers was found */
+    int32_t hyp;              /* that hypothesis, else the best one; -1 when n < min_inliers or n == 0
+                                 (nothing evaluated: identity and zeros out) */
+    int32_t n_iterations;     /* mnIterations after find() */
+    int32_t n_inliers;        /* nInliers: the count of hyp when converged, else 0 */
+    int32_t n_best;           /* mnBestInliers */
+    float R[9], t[3], s;      /* of hyp, R row-major */
+    float T12[16];            /* [sR | t; 0 0 0 1], row-major */
+    uint8_t *inlier;          /* n flags of hyp (mvbBestInliers) */
+    int32_t *hyp_inliers;     /* optional (NULL: not written), n_hyp: the count of every hypothesis */
+    float *hyp_sim3;          /* optional (NULL: not written), 13 per hypothesis: R[9] t[3] s */
+} osg_sim3_ransac_result;
+
+/* Returns n_inliers or a negative OSG_E_* code (sample indices outside [0, n) or repeated within a
+ * triple: OSG_E_INVALID). */
+int osg_sim3_ransac(struct osg_ctx *ctx, const osg_sim3_ransac_problem *p, osg_sim3_ransac_result *r);
+/* n independent problems in one pair of launches (e.g. every loop / merge candidate of a KeyFrame).
+ * Returns the number of converged problems or a negative OSG_E_* code.  No reference counterpart. */
+int osg_sim3_ransac_batch(struct osg_ctx *ctx, const osg_sim3_ransac_problem *p, int32_t n,
+                          osg_sim3_ransac_result *r);
+/* Sim3Solver::SetRansacParameters' mRansacMaxIts (ref:src/Sim3Solver.cc:120-144), host only: float
+ * epsilon = min_inliers / n, ceil(log(1 - prob) / log(1 - epsilon^3)) clamped to [1, max_its], 1 when
+ * min_inliers == n.  A quotient that is not finite or exceeds max_its gives max_its; n < min_inliers
+ * (the solver never iterates) gives 1. */
+int32_t osg_sim3_ransac_iterations(double prob, int32_t min_inliers, int32_t n, int32_t max_its);
 
 /* ---- LocalBundleAdjustment ------------------------------------------------------------------
  * Vertices are given sorted by g2o vertex id (KeyFrames: mnId; MapPoints: mnId + maxKFid + 1),

@@ -165,6 +165,21 @@ class OsgSim3Result(C.Structure):
     ]
 
 
+class OsgSim3RansacProblem(C.Structure):
+    _fields_ = [
+        ("n", i32), ("p1c", P), ("p2c", P), ("max_err1", P), ("max_err2", P), ("cam1", OsgCamera),
+        ("cam2", OsgCamera), ("fix_scale", i32), ("min_inliers", i32), ("n_hyp", i32), ("samples", P),
+    ]
+
+
+class OsgSim3RansacResult(C.Structure):
+    _fields_ = [
+        ("converged", i32), ("hyp", i32), ("n_iterations", i32), ("n_inliers", i32), ("n_best", i32),
+        ("R", f32 * 9), ("t", f32 * 3), ("s", f32), ("T12", f32 * 16), ("inlier", P), ("hyp_inliers", P),
+        ("hyp_sim3", P),
+    ]
+
+
 class OsgBaGraph(C.Structure):
     _fields_ = [
         ("n_poses", i32), ("pose", P), ("pose_fixed", P), ("n_points", i32), ("point", P),
@@ -207,6 +222,7 @@ EXPORTS = [
     "osg_match_last_stats", "osg_ctx_last_kernel_ms", "osg_ctx_device_bytes", "osg_pose_optimization", "osg_pose_optimization_batch",
     "osg_local_bundle_adjustment", "osg_local_bundle_adjustment_batch", "osg_bundle_adjustment",
     "osg_lba_kernel_times", "osg_optimize_sim3", "osg_optimize_sim3_batch",
+    "osg_sim3_ransac", "osg_sim3_ransac_batch", "osg_sim3_ransac_iterations",
     "osg_vocabulary_create", "osg_vocabulary_load_text", "osg_vocabulary_destroy", "osg_vocabulary_info",
     "osg_vocabulary_transform", "osg_vocabulary_transform_batch",
     "osg_fuse_search", "osg_fuse_search_batch", "osg_search_for_triangulation", "osg_search_for_triangulation_batch",
@@ -265,6 +281,10 @@ def declare(lib: C.CDLL) -> C.CDLL:
                                                 C.POINTER(OsgPoseResult)]
     lib.osg_optimize_sim3.argtypes = [vp, C.POINTER(OsgSim3Problem), C.POINTER(OsgSim3Result)]
     lib.osg_optimize_sim3_batch.argtypes = [vp, C.POINTER(OsgSim3Problem), i32, C.POINTER(OsgSim3Result)]
+    lib.osg_sim3_ransac.argtypes = [vp, C.POINTER(OsgSim3RansacProblem), C.POINTER(OsgSim3RansacResult)]
+    lib.osg_sim3_ransac_batch.argtypes = [vp, C.POINTER(OsgSim3RansacProblem), i32, C.POINTER(OsgSim3RansacResult)]
+    lib.osg_sim3_ransac_iterations.argtypes = [C.c_double, i32, i32, i32]
+    lib.osg_sim3_ransac_iterations.restype = i32
     lib.osg_local_bundle_adjustment.argtypes = [vp, C.POINTER(OsgBaGraph), C.POINTER(OsgBaResult),
                                                 vp]
     lib.osg_bundle_adjustment.argtypes = [vp, C.POINTER(OsgBaGraph), C.POINTER(OsgBaResult),
