@@ -412,7 +412,8 @@ __global__ __launch_bounds__(NW * 64) void k_top2_fp4(const uint32_t *__restrict
     // pairs per query (accumulator elements 0-7 and 8-15)
     i32x8 bq[QT][4];
     int ka1[QT], ka2[QT], kb1[QT], kb2[QT];
-    // PIPE == 3 (the default shape): one running top-2 pair per query (both accumulator halves into ka):
+    // PIPE == 3 (OSG_TOP2_MFMA_SHAPE=3, the default until k_top2_fp4q2): one running top-2 pair per query (both
+    // accumulator halves into ka):
     // two fewer rebasing subtractions per tile and no merge of the halves, a longer dependent chain per
     // lane; 852 -> 841 VALU ops, +1.8 % on the headline step (profiles/r05_top2_fp4_onechain.jsonl).
     // The two-pair form stays as OSG_TOP2_MFMA_SHAPE=7.
@@ -877,6 +878,237 @@ __global__ __launch_bounds__(NW * 64) void k_top2_fp4p(const uint32_t *__restric
     }
 }
 
+// Two 32-query tiles per wave (the default, also OSG_TOP2_MFMA_SHAPE=14): NW waves x 64 queries per workgroup,
+// so at 16 waves a 2000-query frame is two workgroups instead of four: half the train-row expansions per frame, half the
+// per-workgroup prologues and tails per CU, and every A fragment read from LDS feeds two MFMAs.  The same
+// keys, MX_* constants, LDS chunk layout and one-chain key_push2f update as k_top2_fp4<.., 3>; the two
+// smallest keys of a set do not depend on the order of the updates, so the output is bit-exact.
+// The pipeline runs across the two query tiles instead of across row tiles, which needs no second
+// accumulator pair: for row tile t the 4 MFMAs of query tile 0 (into acc0) issue beside the key updates of
+// query tile 1 on row tile t - 1 (acc1), then the 4 MFMAs of query tile 1 (into acc1) beside the updates of
+// acc0.  Both chains share a[0..3]; a[s] is refilled with row tile t + 1's granule right after query tile
+// 1's K-step s has consumed it, 4 MFMAs before its next use.  Registers: bq 32 + a 16 + acc 32 + crow 16.
+// A wave whose second tile starts at or past nq runs one tile per row tile, unpipelined; one whose first
+// tile does only takes part in the loads, stores and barriers.
+template <int NW, int CR>
+__global__ __launch_bounds__(NW * 64) void k_top2_fp4q2(const uint32_t *__restrict__ query, int nq,
+                                                         const uint32_t *__restrict__ train, int nt,
+                                                         int nqb, int32_t *__restrict__ out)
+{
+    constexpr int NT = NW * 64;
+    constexpr int BPT = CR * 32 / NT;        // packed bytes per thread per chunk
+    constexpr int WPT = BPT / 4;             // packed words per thread
+    constexpr int TPR = 32 / BPT;            // threads per row
+    constexpr int NTILE = CR / 32;           // 32-row tiles per chunk
+    static_assert(CR * 32 % NT == 0 && BPT % 8 == 0 && TPR >= 1, "chunk / workgroup shape");
+    __shared__ __attribute__((aligned(16))) unsigned char s_buf[2 * CR * MX_RS];   // [2][CR rows][144 B]
+    __shared__ uint32_t s_lut[256];          // train byte -> 8 nibbles (bit y -> nibble y: 0xC = -2 / 0)
+
+    const int t = threadIdx.x, lane = t & 63;
+    const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int G = gridDim.x, L = blockIdx.x;
+    const int logical = (G % 8 == 0) ? (L % 8) * (G / 8) + L / 8 : L;
+    const int b = logical / nqb, qb = logical % nqb;
+    const uint32_t *qf = query + (size_t)b * nq * 8;
+    const uint32_t *tf = train + (size_t)b * nt * 8;
+    int32_t *of = out + (size_t)b * nq * 3;
+
+    for (int e = t; e < 256; e += NT) s_lut[e] = spread_nib((uint32_t)e) * 0xCu;
+
+    const int r = lane & 31, h = lane >> 5;
+    const int qw0 = qb * (NW * 64) + w * 64;
+    const bool act0 = qw0 < nq, act1 = qw0 + 32 < nq;   // wave-uniform
+
+    i32x8 bq[2][4];
+    int k1[2], k2[2];
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+        const int q = min(qw0 + 32 * j + r, nq - 1);
+        const uint4 lo = *(const uint4 *)(qf + (size_t)q * 8), hi = *(const uint4 *)(qf + (size_t)q * 8 + 4);
+        const uint32_t wd[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        int pc = 0;
+#pragma unroll
+        for (int k = 0; k < 8; k++) pc += __popc(wd[k]);
+#pragma unroll
+        for (int s = 0; s < 4; s++) {
+            const uint32_t word = wd[2 * s + h];
+#pragma unroll
+            for (int d = 0; d < 4; d++)
+                bq[j][s][d] = (int)(0x22222222u | ((~spread_nib(word >> (8 * d)) & 0x11111111u) << 3));
+#pragma unroll
+            for (int d = 4; d < 8; d++) bq[j][s][d] = 0;
+        }
+        k1[j] = k2[j] = ((256 - pc) << MF_SHIFT) + MX_KEY0;   // |q| is taken again from the query at the end
+    }
+    f32x16 crow;
+#pragma unroll
+    for (int i = 0; i < 16; i++) crow[i] = MX_BIAS + (float)((i & 3) + 8 * (i >> 2) + 4 * h);
+    const int lbase = r * MX_RS + h * 16;
+
+    // thread t expands words epart * WPT .. of row t / TPR: word offset t * WPT into the chunk's packed rows
+    auto load_chunk = [&](int c0, uint32_t (&pw)[WPT]) {
+        if (c0 + t / TPR < nt) {
+            // a 32-bit byte offset from the frame's (wave-uniform) base: nt <= 8192 rows of 32 B
+            const char *src = (const char *)tf + (unsigned)((c0 * 8 + t * WPT) * 4);
+#pragma unroll
+            for (int i = 0; i < WPT; i += 2) {
+                const uint2 v = *(const uint2 *)(src + 4 * i);
+                pw[i] = v.x;
+                pw[i + 1] = v.y;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < WPT; i++) pw[i] = 0u;   // expands to zero nibbles: D = C exactly
+        }
+    };
+    auto store_chunk = [&](int buf, const uint32_t (&pw)[WPT]) {
+        unsigned char *dst = s_buf + buf * (CR * MX_RS) + (t / TPR) * MX_RS + (t % TPR) * (16 * WPT);
+#pragma unroll
+        for (int i = 0; i < WPT; i++) {
+            const uint32_t x = pw[i];
+            *(i32x4 *)(dst + 16 * i) =
+                i32x4{(int)s_lut[x & 0xFFu], (int)s_lut[(x >> 8) & 0xFFu], (int)s_lut[(x >> 16) & 0xFFu],
+                      (int)s_lut[x >> 24]};
+        }
+    };
+    auto frag = [&](const unsigned char *tb, int s) -> i32x8 {
+        const i32x4 v = *(const i32x4 *)(tb + lbase + 32 * s);
+        return i32x8{v[0], v[1], v[2], v[3], 0, 0, 0, 0};
+    };
+    auto mfma = [&](const i32x8 &a, const i32x8 &bb, const f32x16 &c) {
+        return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, bb, c, 4, 4, 0, MX_SCALE_TRAIN, 0, MX_SCALE_ONE);
+    };
+    // key pairs 2 s and 2 s + 1 of query tile j's accumulator; after the last pair the kept keys move to the
+    // next row tile's base
+    auto push = [&](int j, const f32x16 &acc, int s) {
+        key_push2f(k1[j], k2[j], __float_as_int(acc[2 * s]), __float_as_int(acc[2 * s + 1]));
+        key_push2f(k1[j], k2[j], __float_as_int(acc[8 + 2 * s]), __float_as_int(acc[9 + 2 * s]));
+        if (s == 3) {
+            k1[j] -= 32;
+            k2[j] -= 32;
+        }
+    };
+    // one row tile, unpipelined: both chains when the wave has two tiles, then their updates
+    auto tile = [&](const unsigned char *tb, const f32x16 &cin) {
+        i32x8 a[4];
+#pragma unroll
+        for (int s = 0; s < 4; s++) a[s] = frag(tb, s);
+        f32x16 acc0 = mfma(a[0], bq[0][0], cin);
+#pragma unroll
+        for (int s = 1; s < 4; s++) acc0 = mfma(a[s], bq[0][s], acc0);
+        if (act1) {
+            f32x16 acc1 = mfma(a[0], bq[1][0], cin);
+#pragma unroll
+            for (int s = 1; s < 4; s++) acc1 = mfma(a[s], bq[1][s], acc1);
+#pragma unroll
+            for (int s = 0; s < 4; s++) push(0, acc0, s);
+#pragma unroll
+            for (int s = 0; s < 4; s++) push(1, acc1, s);
+        } else {
+#pragma unroll
+            for (int s = 0; s < 4; s++) push(0, acc0, s);
+        }
+    };
+
+    const int nch = (nt + CR - 1) / CR;
+    {
+        uint32_t pw[WPT];
+        load_chunk(0, pw);
+        __syncthreads();   // the table
+        store_chunk(0, pw);
+    }
+    __syncthreads();
+    for (int c = 0; c < nch; c++) {
+        const int c0 = c * CR;
+        uint32_t pw[WPT];
+        const bool more = c + 1 < nch;
+        if (more) load_chunk(c0 + CR, pw);
+        if (act0) {
+            const unsigned char *sb = s_buf + (size_t)(c & 1) * CR * MX_RS;
+            const int nfull = min(NTILE, (nt - c0) / 32);
+            if (act1 && nfull == NTILE) {
+                i32x8 a[4];
+                f32x16 acc0, acc1;
+#pragma unroll
+                for (int s = 0; s < 4; s++) a[s] = frag(sb, s);
+                // row tile 0, query tile 0: no update is pending yet
+#pragma unroll
+                for (int s = 0; s < 4; s++) {
+                    acc0 = mfma(a[s], bq[0][s], s ? acc0 : crow);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+#pragma unroll
+                for (int tt = 0; tt < NTILE; tt++) {
+                    // query tile 1 of row tile tt beside the updates of query tile 0
+#pragma unroll
+                    for (int s = 0; s < 4; s++) {
+                        acc1 = mfma(a[s], bq[1][s], s ? acc1 : crow);
+                        if (tt + 1 < NTILE) a[s] = frag(sb + (tt + 1) * 32 * MX_RS, s);
+                        push(0, acc0, s);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    if (tt + 1 == NTILE) break;
+                    // query tile 0 of row tile tt + 1 beside the updates of query tile 1 on row tile tt
+#pragma unroll
+                    for (int s = 0; s < 4; s++) {
+                        acc0 = mfma(a[s], bq[0][s], s ? acc0 : crow);
+                        push(1, acc1, s);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+#pragma unroll
+                for (int s = 0; s < 4; s++) push(1, acc1, s);
+            } else {
+#pragma unroll 1
+                for (int tt = 0; tt < nfull; tt++) tile(sb + tt * 32 * MX_RS, crow);
+            }
+            const int lim = nt - (c0 + nfull * 32);
+            if (nfull < NTILE && lim > 0) {
+                f32x16 cin;
+#pragma unroll
+                for (int i = 0; i < 16; i++)
+                    cin[i] = crow[i] + (4 * h >= lim - ((i & 3) + 8 * (i >> 2)) ? MX_PAD : 0.f);
+                tile(sb + nfull * 32 * MX_RS, cin);
+            }
+        }
+        if (more) store_chunk((c + 1) & 1, pw);
+        __syncthreads();
+    }
+    if (!act0) return;
+    const int base = 32 * ((nt + 31) / 32);
+    // the lane id taken again here instead of kept in a register through the chunks
+    const int lane_end = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+        int m1 = k1[j], m2 = k2[j];
+        const int a1 = __shfl_xor(m1, 32), a2 = __shfl_xor(m2, 32);
+        key_merge(m1, m2, a1, a2);
+        const int q = qw0 + 32 * j + lane_end;
+        if (lane_end < 32 && q < nq) {
+            const uint4 lo = *(const uint4 *)(qf + (size_t)q * 8), hi = *(const uint4 *)(qf + (size_t)q * 8 + 4);
+            const int pc = __popc(lo.x) + __popc(lo.y) + __popc(lo.z) + __popc(lo.w) + __popc(hi.x) + __popc(hi.y) +
+                           __popc(hi.z) + __popc(hi.w);
+            const int t1 = m1 - MX_KEY0 + base, t2 = m2 - MX_KEY0 + base;
+            const int d1 = (t1 >> MF_SHIFT) + pc, d2 = (t2 >> MF_SHIFT) + pc;
+            of[3 * q + 0] = d1 < 256 ? (t1 & (MF_MAX_ROWS - 1)) : -1;
+            of[3 * q + 1] = min(d1, 256);
+            of[3 * q + 2] = min(d2, 256);
+        }
+    }
+}
+
+template <int NW, int CR>
+int launch_fp4q2(osg_ctx *ctx, const void *d_query, int nq, const void *d_train, int nt, int nb, void *d_out)
+{
+    const int nqb = (nq + NW * 64 - 1) / (NW * 64);
+    const long long g = (long long)nqb * nb;
+    OSG_REQUIRE(ctx, g <= 0x7FFFFFFF, "grid too large");
+    hipLaunchKernelGGL((k_top2_fp4q2<NW, CR>), dim3((unsigned)g), dim3(NW * 64), 0, ctx->stream,
+                       (const uint32_t *)d_query, nq, (const uint32_t *)d_train, nt, nqb, (int32_t *)d_out);
+    OSG_HIP_CHECK(ctx, hipGetLastError());
+    return OSG_OK;
+}
+
 template <int NW, int QT, int CR>
 int launch_fp4p(osg_ctx *ctx, const void *d_query, int nq, const void *d_train, int nt, int nb, void *d_out)
 {
@@ -927,7 +1159,8 @@ int launch(osg_ctx *ctx, const void *d_query, int nq, const void *d_train, int n
 int osg_top2_mfma_max_rows() { return MF_MAX_ROWS; }
 
 namespace {
-// the launch knobs, read once per process: OSG_TOP2_MFMA_SHAPE picks the workgroup shape,
+// the launch knobs, read once per process: OSG_TOP2_MFMA_SHAPE picks the workgroup shape (FP4: 0 and 14 the
+// two-tiles-per-wave kernel k_top2_fp4q2, 3 the previous default k_top2_fp4<16,1,256,3>, mfma_q2 below),
 // OSG_TOP2_FP4=0 the I8 form (k_top2_mfma) instead of the FP4 block-scaled one (k_top2_fp4, same keys,
 // the default since late r05: 8.3 against 6.0 M Mmatches/s, profiles/r05_top2_fp4_ab.jsonl)
 int mfma_shape()
@@ -951,6 +1184,11 @@ void mfma_shape_of(bool fp4, int shape, int *d)
                        : i8[(shape >= 1 && shape <= 4) ? shape : 0];
     for (int i = 0; i < 4; i++) d[i] = s[i];
 }
+// the FP4 form's two-tiles-per-wave kernel (k_top2_fp4q2<16,256>), outside the {NW, QT, CR, PIPE} tables: the
+// default since it replaced k_top2_fp4<16,1,256,3> (386.6 against 431.9 us per 1024-frame launch, alternating on
+// one box, profiles/top2_q2_ab.jsonl) and OSG_TOP2_MFMA_SHAPE=14; shapes 1-13 keep the table's kernels, 3 the
+// previous default
+bool mfma_q2(bool fp4, int shape) { return fp4 && !(shape >= 1 && shape <= 13); }
 }  // namespace
 
 int osg_hamming_top2_batch_plan(osg_ctx *ctx, int32_t nq, int32_t nt, int32_t nb, char *name, int32_t len)
@@ -959,6 +1197,10 @@ int osg_hamming_top2_batch_plan(osg_ctx *ctx, int32_t nq, int32_t nt, int32_t nb
     const bool mf = getenv("OSG_TOP2_BATCH_MFMA") == nullptr || atoi(getenv("OSG_TOP2_BATCH_MFMA")) != 0;
     if (nq <= 0 || nb <= 0 || nt <= 0 || !mf || nt > MF_MAX_ROWS) {
         snprintf(name, (size_t)len, "%s", nq <= 0 || nb <= 0 ? "none" : "k_top2_batch");
+        return OSG_OK;
+    }
+    if (mfma_q2(mfma_fp4(), mfma_shape())) {
+        snprintf(name, (size_t)len, "k_top2_fp4q2<16,256> grid=%lld x %d", (long long)((nq + 1023) / 1024) * nb, 1024);
         return OSG_OK;
     }
     int d[4];
@@ -976,6 +1218,7 @@ int osg_launch_top2_batch_mfma(osg_ctx *ctx, const void *d_query, int32_t nq, co
     OSG_REQUIRE(ctx, nt >= 1 && nt <= MF_MAX_ROWS, "nt=%d outside the MFMA path's 1..%d rows", nt, MF_MAX_ROWS);
     const int shape = mfma_shape();
     if (mfma_fp4()) {
+        if (mfma_q2(true, shape)) return launch_fp4q2<16, 256>(ctx, d_query, nq, d_train, nt, nb, d_out);
         switch (shape) {
         case 1: return launch_fp4<8, 2, 256, 1>(ctx, d_query, nq, d_train, nt, nb, d_out);
         case 2: return launch_fp4<16, 1, 256, 0>(ctx, d_query, nq, d_train, nt, nb, d_out);
