@@ -1,6 +1,6 @@
 // Optimizer_osg.cc — drop-in bodies for Optimizer::PoseOptimization, the g2o part of
 // Optimizer::LocalBundleAdjustment (both overloads), Optimizer::BundleAdjustment (global BA) and
-// Optimizer::OptimizeSim3 on the MI355X path (ORB-SLAM3 tree built with -DORB_SLAM3_OSG;
+// Optimizer::OptimizeSim3 and Optimizer::OptimizeEssentialGraph (the loop-closure overload) on the MI355X path (ORB-SLAM3 tree built with -DORB_SLAM3_OSG;
 // see INTEGRATION.md).  Signatures: ref:include/Optimizer.h:54-90.
 #include "Optimizer.h"
 #include "osg_hooks_orbslam3.h"
@@ -60,6 +60,16 @@ int Optimizer::OptimizeSim3(KeyFrame *pKF1, KeyFrame *pKF2, std::vector<MapPoint
 {  // ref:src/Optimizer.cc:4213-4512 (LoopClosing's Sim3 refinement of a loop / merge candidate)
     return osg_orbslam3::optimize_sim3<OsgHooks>(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale, mAcumHessian,
                                                  bAllPoints);
+}
+
+void Optimizer::OptimizeEssentialGraph(Map *pMap, KeyFrame *pLoopKF, KeyFrame *pCurKF,
+                                       const LoopClosing::KeyFrameAndPose &NonCorrectedSim3,
+                                       const LoopClosing::KeyFrameAndPose &CorrectedSim3,
+                                       const map<KeyFrame *, set<KeyFrame *>> &LoopConnections, const bool &bFixScale)
+{  // ref:src/Optimizer.cc:4527-4858 (LoopClosing::CorrectLoop's pose-graph optimisation); the lock of :4801 is
+   // taken inside, after the optimisation and before the write-back
+    osg_orbslam3::optimize_essential_graph<OsgHooks>(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3,
+                                                     LoopConnections, bFixScale);
 }
 
 }  // namespace ORB_SLAM3

@@ -290,6 +290,27 @@ struct OsgHooks {
         S = g2o::Sim3(Eigen::Quaterniond(q[3], q[0], q[1], q[2]), Eigen::Vector3d(t[0], t[1], t[2]), s);
     }
     static void zero_hessian(Eigen::Matrix<double, 7, 7> &H) { H = Eigen::MatrixXd::Zero(7, 7); }  // :4483
+    // OptimizeEssentialGraph, ref:src/Optimizer.cc:4595-4596, 4816-4817, 4848-4851
+    static void kf_pose_sim3(KeyFrame *pKF, double q[4], double t[3])
+    {
+        const Sophus::SE3d Tcw = pKF->GetPose().cast<double>();
+        const Eigen::Quaterniond r = Tcw.unit_quaternion();
+        q[0] = r.x(); q[1] = r.y(); q[2] = r.z(); q[3] = r.w();
+        for (int i = 0; i < 3; i++) t[i] = Tcw.translation()[i];
+    }
+    static void kf_set_pose_sim3(KeyFrame *pKF, const double q[4], const double t[3], double s)
+    {
+        const Eigen::Quaterniond r(q[3], q[0], q[1], q[2]);
+        const Eigen::Vector3d tr(t[0], t[1], t[2]);
+        Sophus::SE3f Tiw(r.cast<float>(), tr.cast<float>() / s);
+        pKF->SetPose(Tiw);
+    }
+    static void mp_world_pos(MapPoint *pMP, float x[3])
+    {
+        const Eigen::Vector3f p = pMP->GetWorldPos();
+        x[0] = p.x(); x[1] = p.y(); x[2] = p.z();
+    }
+    static void mp_set_world_pos(MapPoint *pMP, const float x[3]) { pMP->SetWorldPos(Eigen::Vector3f(x[0], x[1], x[2])); }
     // Sim3Solver (ref:src/Sim3Solver.cc): the returned Eigen types and the reference's random source
     using Matrix4f = Eigen::Matrix4f;
     using Matrix3f = Eigen::Matrix3f;

@@ -38,6 +38,7 @@
 #include <set>
 #include <string>
 #include <tuple>
+#include <type_traits>
 #include <utility>
 #include <unordered_map>
 #include <utility>
@@ -2144,6 +2145,277 @@ int optimize_sim3(KeyFrameT *pKF1, KeyFrameT *pKF2, std::vector<MapPointT *> &vp
     r.pair_state = g.state.data();
     if (call(ctx, "osg_optimize_sim3", [&] { return osg_optimize_sim3(ctx, &g.p, &r); }) < 0) return 0;
     return apply_optimize_sim3<H>(g, r, vpMatches1, g2oS12, mAcumHessian);
+}
+
+// ----------------------------------------------------------------------- OptimizeEssentialGraph
+// Optimizer::OptimizeEssentialGraph (ref:src/Optimizer.cc:4527-4858), the Sim3 pose-graph optimisation of
+// LoopClosing::CorrectLoop.  Hooks (sim3_get as for OptimizeSim3):
+//   static void H::kf_pose_sim3(KeyFrame*, double q[4], double t[3])     Tcw = GetPose().cast<double>():
+//                unit_quaternion() as (x y z w) and translation() (:4595-4596)
+//   static void H::kf_set_pose_sim3(KeyFrame*, const double q[4], const double t[3], double s)
+//                SetPose(SE3f(Quaterniond(q).cast<float>(), Vector3d(t).cast<float>() / s)) (:4816-4817)
+//   static void H::mp_world_pos(MapPoint*, float x[3]) / H::mp_set_world_pos(MapPoint*, const float x[3])
+//
+// EssentialGraphGather is the graph build of :4551-4793 as plain host code, literally: a vertex per non-bad
+// KeyFrame of GetAllKeyFrames() in that order (the ABI's vertex index; ids are sparse, index_of_id has
+// nMaxKFid + 1 slots), its estimate the CorrectedSim3 entry or Sim3(Tcw, 1.0), the init KeyFrame fixed; then
+// the edges in the reference's insertion order with its filters: the LoopConnections (weight >= minFeat
+// unless the pair is (pCurKF, pLoopKF); these fill sInsertedEdges), and per KeyFrame the spanning-tree edge,
+// the loop edges to smaller ids, the covisibility >= minFeat edges (not the parent, not a child, not bad,
+// smaller id, not in sInsertedEdges) and the bImu edge to mPrevKF.  Measurements are Sjw * Swi in double
+// with g2o::Sim3's own operators (osgs3 below), from NonCorrectedSim3 where the KeyFrame has an entry.
+//
+// An edge whose KeyFrame has no vertex (a bad KeyFrame: the reference's second loop does not skip one) is
+// DROPPED and counted in n_dropped: g2o's HyperGraph::addEdge would dereference the null vertex
+// (ref:Thirdparty/g2o/g2o/core/hyper_graph.cpp:99-109).  For the same reason the write-back skips a
+// KeyFrame without a vertex, where :4811-4812 would dereference null.
+namespace osgs3 {  // g2o::Sim3's operator* and inverse() (ref:Thirdparty/g2o/g2o/types/sim3.h:233-236, 266-272) in
+                   // double, the quaternion never renormalised; the same expressions as csrc/sim3_common.h
+struct Sim3 {
+    double q[4];  // x y z w
+    double t[3];
+    double s;
+};
+inline void q_mul(const double *a, const double *b, double *o)
+{
+    double r[4];
+    r[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
+    r[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
+    r[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
+    r[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
+    o[0] = r[0]; o[1] = r[1]; o[2] = r[2]; o[3] = r[3];
+}
+inline void q_rot(const double *q, const double *v, double *o)  // Eigen QuaternionBase::_transformVector
+{
+    double uv0 = q[1] * v[2] - q[2] * v[1], uv1 = q[2] * v[0] - q[0] * v[2], uv2 = q[0] * v[1] - q[1] * v[0];
+    uv0 += uv0; uv1 += uv1; uv2 += uv2;
+    const double c0 = q[1] * uv2 - q[2] * uv1, c1 = q[2] * uv0 - q[0] * uv2, c2 = q[0] * uv1 - q[1] * uv0;
+    const double r0 = v[0] + q[3] * uv0 + c0, r1 = v[1] + q[3] * uv1 + c1, r2 = v[2] + q[3] * uv2 + c2;
+    o[0] = r0; o[1] = r1; o[2] = r2;
+}
+inline Sim3 sim3_mul(const Sim3 &a, const Sim3 &b)
+{
+    Sim3 o;
+    double rt[3];
+    q_rot(a.q, b.t, rt);
+    for (int i = 0; i < 3; i++) o.t[i] = a.s * rt[i] + a.t[i];
+    q_mul(a.q, b.q, o.q);
+    o.s = a.s * b.s;
+    return o;
+}
+inline Sim3 sim3_inverse(const Sim3 &a)
+{
+    Sim3 o;
+    o.q[0] = -a.q[0]; o.q[1] = -a.q[1]; o.q[2] = -a.q[2]; o.q[3] = a.q[3];
+    const double k = -1. / a.s;
+    const double v[3] = {k * a.t[0], k * a.t[1], k * a.t[2]};
+    q_rot(o.q, v, o.t);
+    o.s = 1. / a.s;
+    return o;
+}
+}  // namespace osgs3
+
+template <class H, class MapT, class KeyFrameT, class MapPointT>
+struct EssentialGraphGather {
+    static constexpr int minFeat = 100;
+    std::vector<KeyFrameT *> vpKFs, vertex_kf;
+    std::vector<MapPointT *> vpMPs;
+    std::vector<int32_t> index_of_id;
+    std::vector<double> sim3, e_meas, out;
+    std::vector<uint8_t> fixed;
+    std::vector<int32_t> e_v0, e_v1;
+    int n_dropped = 0;
+    osg_essgraph_problem p{};
+
+    static osgs3::Sim3 from_g2o(const double *q, const double *t, double s)
+    {
+        osgs3::Sim3 S;
+        for (int i = 0; i < 4; i++) S.q[i] = q[i];
+        for (int i = 0; i < 3; i++) S.t[i] = t[i];
+        S.s = s;
+        return S;
+    }
+    template <class Sim3T>
+    static osgs3::Sim3 from_g2o(const Sim3T &g)
+    {
+        double q[4], t[3], s;
+        H::sim3_get(g, q, t, s);
+        return from_g2o(q, t, s);
+    }
+    void add_edge(unsigned long nIDi, unsigned long nIDj, const osgs3::Sim3 &Sji)
+    {
+        const int32_t a = nIDi < index_of_id.size() ? index_of_id[nIDi] : -1;
+        const int32_t b = nIDj < index_of_id.size() ? index_of_id[nIDj] : -1;
+        if (a < 0 || b < 0 || a == b) {
+            n_dropped++;
+            return;
+        }
+        e_v0.push_back(a);
+        e_v1.push_back(b);
+        const double m[8] = {Sji.q[0], Sji.q[1], Sji.q[2], Sji.q[3], Sji.t[0], Sji.t[1], Sji.t[2], Sji.s};
+        e_meas.insert(e_meas.end(), m, m + 8);
+    }
+    template <class KFAndPoseT, class LoopConnT>
+    void assign(MapT *pMap, KeyFrameT *pLoopKF, KeyFrameT *pCurKF, const KFAndPoseT &NonCorrectedSim3,
+                const KFAndPoseT &CorrectedSim3, const LoopConnT &LoopConnections, bool bFixScale)
+    {
+        p = osg_essgraph_problem{};
+        for (auto *v : {&sim3, &e_meas, &out}) v->clear();
+        for (auto *v : {&e_v0, &e_v1}) v->clear();
+        fixed.clear();
+        vertex_kf.clear();
+        n_dropped = 0;
+        vpKFs = pMap->GetAllKeyFrames();
+        vpMPs = pMap->GetAllMapPoints();
+        const unsigned int nMaxKFid = pMap->GetMaxKFid();
+        const double q1[4] = {0, 0, 0, 1}, t0[3] = {0, 0, 0};
+        std::vector<osgs3::Sim3> vScw(nMaxKFid + 1, from_g2o(q1, t0, 1.0));  // g2o::Sim3(): the identity
+        index_of_id.assign(nMaxKFid + 1, -1);
+        for (size_t i = 0, iend = vpKFs.size(); i < iend; i++) {  // :4575-4613
+            KeyFrameT *pKF = vpKFs[i];
+            if (pKF->isBad()) continue;
+            const unsigned long nIDi = pKF->mnId;
+            auto it = CorrectedSim3.find(pKF);
+            if (it != CorrectedSim3.end()) {
+                vScw[nIDi] = from_g2o(it->second);
+            } else {
+                double q[4], t[3];
+                H::kf_pose_sim3(pKF, q, t);
+                vScw[nIDi] = from_g2o(q, t, 1.0);
+            }
+            index_of_id[nIDi] = (int32_t)vertex_kf.size();
+            vertex_kf.push_back(pKF);
+            fixed.push_back(pKF->mnId == pMap->GetInitKFid() ? 1 : 0);
+            const osgs3::Sim3 &S = vScw[nIDi];
+            const double r[8] = {S.q[0], S.q[1], S.q[2], S.q[3], S.t[0], S.t[1], S.t[2], S.s};
+            sim3.insert(sim3.end(), r, r + 8);
+        }
+        std::set<std::pair<unsigned long, unsigned long>> sInsertedEdges;
+        for (auto mit = LoopConnections.begin(), mend = LoopConnections.end(); mit != mend; mit++) {  // :4623-4663
+            KeyFrameT *pKF = mit->first;
+            const unsigned long nIDi = pKF->mnId;
+            const auto &spConnections = mit->second;
+            const osgs3::Sim3 Swi = osgs3::sim3_inverse(vScw[nIDi]);
+            for (auto sit = spConnections.begin(), send = spConnections.end(); sit != send; sit++) {
+                const unsigned long nIDj = (*sit)->mnId;
+                if ((nIDi != pCurKF->mnId || nIDj != pLoopKF->mnId) && pKF->GetWeight(*sit) < minFeat) continue;
+                add_edge(nIDi, nIDj, osgs3::sim3_mul(vScw[nIDj], Swi));
+                sInsertedEdges.insert(std::make_pair(std::min(nIDi, nIDj), std::max(nIDi, nIDj)));
+            }
+        }
+        auto non_corrected = [&](KeyFrameT *k) {  // the NonCorrectedSim3 entry, else vScw
+            auto it = NonCorrectedSim3.find(k);
+            return it != NonCorrectedSim3.end() ? from_g2o(it->second) : vScw[k->mnId];
+        };
+        for (size_t i = 0, iend = vpKFs.size(); i < iend; i++) {  // :4667-4793
+            KeyFrameT *pKF = vpKFs[i];
+            const unsigned long nIDi = pKF->mnId;
+            const osgs3::Sim3 Swi = osgs3::sim3_inverse(non_corrected(pKF));
+            KeyFrameT *pParentKF = pKF->GetParent();
+            if (pParentKF) add_edge(nIDi, pParentKF->mnId, osgs3::sim3_mul(non_corrected(pParentKF), Swi));
+            const std::set<KeyFrameT *> sLoopEdges = pKF->GetLoopEdges();
+            for (auto sit = sLoopEdges.begin(), send = sLoopEdges.end(); sit != send; sit++) {
+                KeyFrameT *pLKF = *sit;
+                if (pLKF->mnId < pKF->mnId) add_edge(nIDi, pLKF->mnId, osgs3::sim3_mul(non_corrected(pLKF), Swi));
+            }
+            const std::vector<KeyFrameT *> vpConnectedKFs = pKF->GetCovisiblesByWeight(minFeat);
+            for (auto vit = vpConnectedKFs.begin(); vit != vpConnectedKFs.end(); vit++) {
+                KeyFrameT *pKFn = *vit;
+                if (pKFn && pKFn != pParentKF && !pKF->hasChild(pKFn)) {
+                    if (!pKFn->isBad() && pKFn->mnId < pKF->mnId) {
+                        if (sInsertedEdges.count(std::make_pair(std::min<unsigned long>(pKF->mnId, pKFn->mnId),
+                                                                std::max<unsigned long>(pKF->mnId, pKFn->mnId))))
+                            continue;
+                        add_edge(nIDi, pKFn->mnId, osgs3::sim3_mul(non_corrected(pKFn), Swi));
+                    }
+                }
+            }
+            if (pKF->bImu && pKF->mPrevKF)
+                add_edge(nIDi, pKF->mPrevKF->mnId, osgs3::sim3_mul(non_corrected(pKF->mPrevKF), Swi));
+        }
+        out.assign(sim3.size(), 0.0);
+        p.n_vertices = (int32_t)vertex_kf.size();
+        p.sim3 = sim3.data();
+        p.fixed = fixed.data();
+        p.fix_scale = bFixScale ? 1 : 0;
+        p.n_edges = (int32_t)e_v0.size();
+        p.e_v0 = e_v0.data();
+        p.e_v1 = e_v1.data();
+        p.e_meas = e_meas.data();
+        p.max_iterations = 0;      // optimize(20), :4799
+        p.lambda_init = 1e-16;     // setUserLambdaInit, :4547
+    }
+};
+
+// The MapPoint side of the write-back (:4822-4851) as arrays: the positions of the non-bad MapPoints and the
+// vertex of each one's reference KeyFrame (mnCorrectedReference when mnCorrectedByKF == pCurKF->mnId), -1
+// when that KeyFrame has no vertex (the reference then maps through two default Sim3s: the identity).
+template <class H, class MapT, class KeyFrameT, class MapPointT>
+void essential_graph_points(const EssentialGraphGather<H, MapT, KeyFrameT, MapPointT> &g, KeyFrameT *pCurKF,
+                            std::vector<MapPointT *> &mps, std::vector<float> &Xw, std::vector<int32_t> &ref)
+{
+    mps.clear();
+    Xw.clear();
+    ref.clear();
+    for (size_t i = 0, iend = g.vpMPs.size(); i < iend; i++) {
+        MapPointT *pMP = g.vpMPs[i];
+        if (pMP->isBad()) continue;
+        unsigned long nIDr;
+        if (pMP->mnCorrectedByKF == pCurKF->mnId) nIDr = pMP->mnCorrectedReference;
+        else nIDr = pMP->GetReferenceKeyFrame()->mnId;
+        float x[3];
+        H::mp_world_pos(pMP, x);
+        mps.push_back(pMP);
+        Xw.insert(Xw.end(), x, x + 3);
+        ref.push_back(nIDr < g.index_of_id.size() ? g.index_of_id[nIDr] : -1);
+    }
+}
+
+// :4805-4857 with the optimised Sim3s in g.out and the corrected positions in Xw_out: SetPose(R, t / s) per
+// vertex KeyFrame, SetWorldPos + UpdateNormalAndDepth per non-bad MapPoint, IncreaseChangeIndex.  The caller
+// holds the map's mMutexMapUpdate.
+template <class H, class MapT, class KeyFrameT, class MapPointT>
+void apply_essential_graph(const EssentialGraphGather<H, MapT, KeyFrameT, MapPointT> &g, MapT *pMap,
+                           const std::vector<MapPointT *> &mps, const std::vector<float> &Xw_out)
+{
+    for (size_t v = 0; v < g.vertex_kf.size(); v++) {
+        const double *S = g.out.data() + 8 * v;
+        H::kf_set_pose_sim3(g.vertex_kf[v], S, S + 4, S[7]);
+    }
+    for (size_t i = 0; i < mps.size(); i++) {
+        H::mp_set_world_pos(mps[i], Xw_out.data() + 3 * i);
+        mps[i]->UpdateNormalAndDepth();
+    }
+    pMap->IncreaseChangeIndex();
+}
+
+// The whole call.  On an ABI error nothing of the map is touched (LoopClosing then runs its global BA on the
+// uncorrected map, as if the pose graph had not moved anything).  Returns the ABI's code.
+template <class H, class MapT, class KeyFrameT, class KFAndPoseT, class LoopConnT>
+int optimize_essential_graph(MapT *pMap, KeyFrameT *pLoopKF, KeyFrameT *pCurKF, const KFAndPoseT &NonCorrectedSim3,
+                             const KFAndPoseT &CorrectedSim3, const LoopConnT &LoopConnections, bool bFixScale)
+{
+    using MapPointT = typename std::remove_pointer<typename std::decay<decltype(pMap->GetAllMapPoints()[0])>::type>::type;
+    osg_ctx *ctx = thread_ctx();
+    EssentialGraphGather<H, MapT, KeyFrameT, MapPointT> g;
+    g.assign(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, bFixScale);
+    osg_essgraph_result r{};
+    r.sim3 = g.out.data();
+    int rc = call(ctx, "osg_optimize_essential_graph", [&] { return osg_optimize_essential_graph(ctx, &g.p, &r); });
+    if (rc < 0) return rc;
+    std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);  // :4801
+    std::vector<MapPointT *> mps;
+    std::vector<float> Xw, Xw_out;
+    std::vector<int32_t> ref;
+    essential_graph_points<H>(g, pCurKF, mps, Xw, ref);
+    Xw_out.resize(Xw.size());
+    rc = call(ctx, "osg_essgraph_correct_points", [&] {
+        return osg_essgraph_correct_points(ctx, (int32_t)mps.size(), Xw.data(), ref.data(), g.p.n_vertices, g.sim3.data(),
+                                           g.out.data(), Xw_out.data());
+    });
+    if (rc < 0) return rc;
+    apply_essential_graph<H>(g, pMap, mps, Xw_out);
+    return rc;
 }
 
 // ------------------------------------------------------------------------------- Sim3Solver

@@ -170,6 +170,53 @@ int osg_sim3_ransac_batch(struct osg_ctx *ctx, const osg_sim3_ransac_problem *p,
  * (the solver never iterates) gives 1. */
 int32_t osg_sim3_ransac_iterations(double prob, int32_t min_inliers, int32_t n, int32_t max_its);
 
+/* ---- OptimizeEssentialGraph -----------------------------------------------------------------
+ * The g2o part of Optimizer::OptimizeEssentialGraph (ref:src/Optimizer.cc:4527-4858): a pose graph of
+ * VertexSim3Expmap vertices and EdgeSim3 edges (identity information, no robust kernel, numeric
+ * Jacobians), Levenberg-Marquardt with a user lambda, optimize(20).  The adapter gathers the vertices
+ * and the edge list in the reference's insertion order; the same pair may be listed several times and in
+ * both directions. */
+typedef struct osg_essgraph_problem {
+    int32_t n_vertices;       /* non-bad KeyFrames, caller's order; at most 65 535 */
+    const double *sim3;       /* 8 per vertex: q (x, y, z, w), t, s  (vScw) */
+    const uint8_t *fixed;     /* per vertex */
+    int32_t fix_scale;        /* bFixScale */
+    int32_t n_edges;
+    const int32_t *e_v0, *e_v1; /* vertex(0) = i, vertex(1) = j; i != j */
+    const double *e_meas;     /* 8 per edge: Sji */
+    int32_t max_iterations;   /* 0: the reference's 20 */
+    double lambda_init;       /* the reference passes 1e-16; >= 0 (0: g2o's 1e-5 max |diag H|) */
+} osg_essgraph_problem;
+
+typedef struct osg_essgraph_result {
+    double *sim3;             /* 8 per vertex out; a fixed vertex bit-equal to its input */
+    double chi2_initial, chi2_final;
+    int32_t lm_iterations, lm_trials;
+    double *edge_chi2;        /* optional (NULL: not written), per edge at the returned state */
+} osg_essgraph_result;
+
+/* Returns 0 or a negative OSG_E_* code.  OSG_E_INVALID (nothing written): an index outside
+ * [0, n_vertices), e_v0 == e_v1, a null array with a positive count, a negative count, lambda_init or
+ * max_iterations, a scale that is not positive, more than 65 535 vertices.  OSG_E_NOMEM: the matrix
+ * store (the lower 32 x 32 tiles inside the row-block envelope, twice) could not be allocated; the
+ * context stays usable.  n_edges == 0 or no free vertex: the output is the input, 0 iterations. */
+int osg_optimize_essential_graph(struct osg_ctx *ctx, const osg_essgraph_problem *p, osg_essgraph_result *r);
+/* The MapPoint correction of the write-back (ref:src/Optimizer.cc:4824-4851):
+ * Xw_out = float(inverse(sim3_after[r]).map(sim3_before[r].map(double(Xw)))) with r = ref_vertex of the
+ * point; r < 0: copied through.  Xw / Xw_out: 3 floats per point (may be the same array); sim3_before /
+ * sim3_after: 8 doubles per vertex.  Returns 0 or a negative OSG_E_* code (r >= n_vertices, a scale that
+ * is not positive: OSG_E_INVALID, nothing written). */
+int osg_essgraph_correct_points(struct osg_ctx *ctx, int32_t n_points, const float *Xw, const int32_t *ref_vertex,
+                                int32_t n_vertices, const double *sim3_before, const double *sim3_after,
+                                float *Xw_out);
+/* Diagnostics: per-phase device time of osg_optimize_essential_graph.  enable = 1: every later call
+ * brackets its launches with HIP events (one pair per phase and launch group, read after the call);
+ * 0 stops.  ms (may be NULL) receives the sums of the last timed call, in ms: linearise, assemble,
+ * factor (damping copy, factorisation, both substitutions), update, chi2, and as the sixth value the
+ * device bytes of the matrix store. */
+#define OSG_ESSGRAPH_NK 6
+int osg_essgraph_kernel_times(struct osg_ctx *ctx, int32_t enable, double *ms);
+
 /* ---- LocalBundleAdjustment ------------------------------------------------------------------
  * Vertices are given sorted by g2o vertex id (KeyFrames: mnId; MapPoints: mnId + maxKFid + 1),
  * which fixes the Hessian index order (ref:Thirdparty/g2o/g2o/core/sparse_optimizer.cpp:181-211,

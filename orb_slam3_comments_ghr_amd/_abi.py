@@ -180,6 +180,20 @@ class OsgSim3RansacResult(C.Structure):
     ]
 
 
+class OsgEssGraphProblem(C.Structure):
+    _fields_ = [
+        ("n_vertices", i32), ("sim3", P), ("fixed", P), ("fix_scale", i32), ("n_edges", i32), ("e_v0", P),
+        ("e_v1", P), ("e_meas", P), ("max_iterations", i32), ("lambda_init", f64),
+    ]
+
+
+class OsgEssGraphResult(C.Structure):
+    _fields_ = [
+        ("sim3", P), ("chi2_initial", f64), ("chi2_final", f64), ("lm_iterations", i32), ("lm_trials", i32),
+        ("edge_chi2", P),
+    ]
+
+
 class OsgBaGraph(C.Structure):
     _fields_ = [
         ("n_poses", i32), ("pose", P), ("pose_fixed", P), ("n_points", i32), ("point", P),
@@ -223,6 +237,7 @@ EXPORTS = [
     "osg_local_bundle_adjustment", "osg_local_bundle_adjustment_batch", "osg_bundle_adjustment",
     "osg_lba_kernel_times", "osg_optimize_sim3", "osg_optimize_sim3_batch",
     "osg_sim3_ransac", "osg_sim3_ransac_batch", "osg_sim3_ransac_iterations",
+    "osg_optimize_essential_graph", "osg_essgraph_correct_points", "osg_essgraph_kernel_times",
     "osg_vocabulary_create", "osg_vocabulary_load_text", "osg_vocabulary_destroy", "osg_vocabulary_info",
     "osg_vocabulary_transform", "osg_vocabulary_transform_batch",
     "osg_fuse_search", "osg_fuse_search_batch", "osg_search_for_triangulation", "osg_search_for_triangulation_batch",
@@ -285,6 +300,9 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.osg_sim3_ransac_batch.argtypes = [vp, C.POINTER(OsgSim3RansacProblem), i32, C.POINTER(OsgSim3RansacResult)]
     lib.osg_sim3_ransac_iterations.argtypes = [C.c_double, i32, i32, i32]
     lib.osg_sim3_ransac_iterations.restype = i32
+    lib.osg_optimize_essential_graph.argtypes = [vp, C.POINTER(OsgEssGraphProblem), C.POINTER(OsgEssGraphResult)]
+    lib.osg_essgraph_correct_points.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp]
+    lib.osg_essgraph_kernel_times.argtypes = [vp, i32, vp]
     lib.osg_local_bundle_adjustment.argtypes = [vp, C.POINTER(OsgBaGraph), C.POINTER(OsgBaResult),
                                                 vp]
     lib.osg_bundle_adjustment.argtypes = [vp, C.POINTER(OsgBaGraph), C.POINTER(OsgBaResult),

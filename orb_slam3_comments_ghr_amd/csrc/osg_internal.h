@@ -52,6 +52,7 @@ struct osg_ctx {
     double lba_kms[OSG_LBA_NK] = {};
     int64_t lba_kn[OSG_LBA_NK] = {};
     std::string last_error;
+    std::shared_ptr<void> essgraph_state;  // host structures and phase timing of essgraph.hip
 };
 
 int osg_set_error(osg_ctx *ctx, int code, const char *fmt, ...);

@@ -172,4 +172,99 @@ OSG_HD inline Sim3 sim3_oplus(const Sim3 &est, const double *upd, bool fix_scale
     return sim3_mul(sim3_exp(u), est);
 }
 
+// 3 x 3 PartialPivLU solve (Eigen's W.lu().solve(t)): the first largest |entry| of the column is the
+// pivot, the multipliers are quotients.  Rows are exchanged by value (a dynamic row index would send the
+// matrix to scratch on the device).
+OSG_HD inline void lu3_solve(const double W[3][3], const double *t, double *x)
+{
+    double a0[4] = {W[0][0], W[0][1], W[0][2], t[0]};
+    double a1[4] = {W[1][0], W[1][1], W[1][2], t[1]};
+    double a2[4] = {W[2][0], W[2][1], W[2][2], t[2]};
+    auto swap_rows = [](double *p, double *q) {
+        for (int i = 0; i < 4; i++) {
+            const double v = p[i];
+            p[i] = q[i];
+            q[i] = v;
+        }
+    };
+    if (fabs(a1[0]) > fabs(a0[0]) && !(fabs(a2[0]) > fabs(a1[0]))) swap_rows(a0, a1);
+    else if (fabs(a2[0]) > fabs(a0[0])) swap_rows(a0, a2);
+    const double l1 = a1[0] / a0[0], l2 = a2[0] / a0[0];
+    for (int i = 1; i < 4; i++) {
+        a1[i] -= l1 * a0[i];
+        a2[i] -= l2 * a0[i];
+    }
+    if (fabs(a2[1]) > fabs(a1[1])) swap_rows(a1, a2);
+    const double l21 = a2[1] / a1[1];
+    for (int i = 2; i < 4; i++) a2[i] -= l21 * a1[i];
+    const double x2 = a2[3] / a2[2];
+    const double x1 = (a1[3] - a1[2] * x2) / a1[1];
+    const double x0 = (a0[3] - a0[1] * x1 - a0[2] * x2) / a0[0];
+    x[0] = x0; x[1] = x1; x[2] = x2;
+}
+
+// Sim3::log (ref:Thirdparty/g2o/g2o/types/sim3.h:148-230): out = (omega, upsilon, sigma), the four
+// branches on |sigma| < 1e-5 and d > 1 - 1e-5.  R is Eigen's toRotationMatrix of the quaternion as it
+// is stored (not normalised), omega comes from deltaR(R).
+OSG_HD inline void sim3_log(const Sim3 &S, double *out)
+{
+    const double sigma = log(S.s);
+    const double tx = 2 * S.q[0], ty = 2 * S.q[1], tz = 2 * S.q[2];
+    const double twx = tx * S.q[3], twy = ty * S.q[3], twz = tz * S.q[3];
+    const double txx = tx * S.q[0], txy = ty * S.q[0], txz = tz * S.q[0];
+    const double tyy = ty * S.q[1], tyz = tz * S.q[1], tzz = tz * S.q[2];
+    const double R00 = 1 - (tyy + tzz), R01 = txy - twz, R02 = txz + twy;
+    const double R10 = txy + twz, R11 = 1 - (txx + tzz), R12 = tyz - twx;
+    const double R20 = txz - twy, R21 = tyz + twx, R22 = 1 - (txx + tyy);
+    const double d = 0.5 * (R00 + R11 + R22 - 1);
+    const double dR0 = R21 - R12, dR1 = R02 - R20, dR2 = R10 - R01;  // deltaR
+    const double eps = 0.00001;
+    double A, B, C, k;
+    if (fabs(sigma) < eps) {
+        C = 1;
+        if (d > 1 - eps) {
+            k = 0.5;
+            A = 1. / 2.;
+            B = 1. / 6.;
+        } else {
+            const double theta = acos(d);
+            const double theta2 = theta * theta;
+            double st, ct;
+            osgx::sincos_ref<false>(theta, st, ct);
+            k = theta / (2 * sqrt(1 - d * d));
+            A = (1 - ct) / (theta2);
+            B = (theta - st) / (theta2 * theta);
+        }
+    } else {
+        C = (S.s - 1) / sigma;
+        if (d > 1 - eps) {
+            const double sigma2 = sigma * sigma;
+            k = 0.5;
+            A = ((sigma - 1) * S.s + 1) / (sigma2);
+            B = ((0.5 * sigma2 - sigma + 1) * S.s) / (sigma2 * sigma);
+        } else {
+            const double theta = acos(d);
+            k = theta / (2 * sqrt(1 - d * d));
+            const double theta2 = theta * theta;
+            double st, ct;
+            osgx::sincos_ref<false>(theta, st, ct);
+            const double a = S.s * st;
+            const double b = S.s * ct;
+            const double c = theta2 + sigma * sigma;
+            A = (a * sigma + (1 - b) * theta) / (theta * c);
+            B = (C - ((b - 1) * sigma + a * theta) / (c)) * 1. / (theta2);
+        }
+    }
+    const double w0 = k * dR0, w1 = k * dR1, w2 = k * dR2;
+    const double Om[3][3] = {{0, -w2, w1}, {w2, 0, -w0}, {-w1, w0, 0}};
+    double W[3][3];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++)
+            W[i][j] = A * Om[i][j] + B * (Om[i][0] * Om[0][j] + Om[i][1] * Om[1][j] + Om[i][2] * Om[2][j]) +
+                      (i == j ? C : 0.0);
+    out[0] = w0; out[1] = w1; out[2] = w2;
+    lu3_solve(W, S.t, out + 3);
+    out[6] = sigma;
+}
+
 }  // namespace osgs3

@@ -287,6 +287,68 @@ class Sim3Result:
     early_return: bool
 
 
+@dataclass
+class EssentialGraphProblem:
+    """One ``Optimizer::OptimizeEssentialGraph`` call as the adapter gathers it (include/osg_ba.h): the
+    non-bad KeyFrames in the caller's order, the edges in the reference's insertion order."""
+    sim3: np.ndarray          # n x 8 double: q (x, y, z, w), t, s  (vScw)
+    fixed: np.ndarray         # n uint8
+    e_v0: np.ndarray          # E int32, vertex(0) = i
+    e_v1: np.ndarray          # E int32, vertex(1) = j
+    e_meas: np.ndarray        # E x 8 double, Sji
+    fix_scale: bool = False
+    max_iterations: int = 0   # 0: the reference's 20
+    lambda_init: float = 1e-16
+    truth: np.ndarray | None = None  # generator only (consistent=True): the Sim3s the measurements were built from
+
+    def __post_init__(self):
+        self.sim3 = np.ascontiguousarray(self.sim3, np.float64).reshape(-1, 8)
+        self.fixed = np.ascontiguousarray(self.fixed, np.uint8)
+        self.e_v0 = np.ascontiguousarray(self.e_v0, np.int32)
+        self.e_v1 = np.ascontiguousarray(self.e_v1, np.int32)
+        self.e_meas = np.ascontiguousarray(self.e_meas, np.float64).reshape(-1, 8)
+
+    @property
+    def n(self):
+        return len(self.sim3)
+
+    @property
+    def n_edges(self):
+        return len(self.e_v0)
+
+    def struct(self):
+        st = _abi.OsgEssGraphProblem()
+        st.n_vertices, st.sim3, st.fixed = self.n, _p(self.sim3), _p(self.fixed)
+        st.fix_scale = int(bool(self.fix_scale))
+        st.n_edges, st.e_v0, st.e_v1, st.e_meas = self.n_edges, _p(self.e_v0), _p(self.e_v1), _p(self.e_meas)
+        st.max_iterations = int(self.max_iterations)
+        st.lambda_init = float(self.lambda_init)
+        return st
+
+
+@dataclass
+class EssentialGraphResult:
+    sim3: np.ndarray          # n x 8, a fixed vertex bit-equal to its input
+    chi2_initial: float
+    chi2_final: float
+    lm_iterations: int
+    lm_trials: int
+    edge_chi2: np.ndarray     # per edge at the returned state
+
+    @property
+    def R(self):
+        q = self.sim3[:, :4] / np.linalg.norm(self.sim3[:, :4], axis=1)[:, None]
+        return np.stack([quat_to_rot(v) for v in q]) if len(q) else np.zeros((0, 3, 3))
+
+    @property
+    def t(self):
+        return self.sim3[:, 4:7]
+
+    @property
+    def s(self):
+        return self.sim3[:, 7]
+
+
 def run_pose(fn, problems, handle=None):
     """Call a PoseOptimization entry point on problems: the batch API (handle given) or a
     per-problem function fn(problem_structs, result_structs)."""
@@ -351,6 +413,37 @@ class Optimizer:
                           tuple(r.lm_iterations), tuple(r.lm_trials), r.chi2_final, c, bool(r.early_return))
                for r, st, c in zip(rs, state, chi2)]
         return out[0] if single else out
+
+    def optimize_essential_graph(self, P: EssentialGraphProblem) -> EssentialGraphResult:
+        """The g2o part of ``Optimizer::OptimizeEssentialGraph`` (ref:src/Optimizer.cc:4527-4858): the Sim3 pose
+        graph the adapter gathered, optimize(20) with the caller's lambda.  The caller writes the poses back
+        (``SetPose(R, t / s)``) and corrects the MapPoints with ``correct_map_points``."""
+        st = P.struct()
+        R = _abi.OsgEssGraphResult()
+        out, chi = np.zeros((P.n, 8), np.float64), np.zeros(P.n_edges, np.float64)
+        R.sim3, R.edge_chi2 = _p(out), _p(chi)
+        self.ctx.check(self.ctx.lib.osg_optimize_essential_graph(self.ctx.handle, C.byref(st), C.byref(R)),
+                       "OptimizeEssentialGraph")
+        return EssentialGraphResult(out, R.chi2_initial, R.chi2_final, R.lm_iterations, R.lm_trials, chi)
+
+    def correct_map_points(self, Xw, ref_vertex, sim3_before, sim3_after):
+        """``correctedSwr.map(Srw.map(X))`` of every MapPoint through its reference KeyFrame's vertex
+        (ref:src/Optimizer.cc:4824-4851); a point with ``ref_vertex < 0`` is copied through."""
+        Xw = np.ascontiguousarray(Xw, np.float32).reshape(-1, 3)
+        ref = np.ascontiguousarray(ref_vertex, np.int32)
+        b = np.ascontiguousarray(sim3_before, np.float64).reshape(-1, 8)
+        a = np.ascontiguousarray(sim3_after, np.float64).reshape(-1, 8)
+        assert len(ref) == len(Xw) and a.shape == b.shape
+        out = np.zeros_like(Xw)
+        self.ctx.check(self.ctx.lib.osg_essgraph_correct_points(self.ctx.handle, len(Xw), _p(Xw), _p(ref), len(b), _p(b),
+                                                                _p(a), _p(out)), "essgraph_correct_points")
+        return out
+
+    def essential_graph_kernel_times(self, enable=True):
+        """(ms by phase: linearise, assemble, factor, update, chi2; matrix store bytes) of the last timed call"""
+        ms = np.zeros(6, np.float64)
+        self.ctx.check(self.ctx.lib.osg_essgraph_kernel_times(self.ctx.handle, int(bool(enable)), _p(ms)), "kernel times")
+        return dict(zip(["linearise", "assemble", "factor", "update", "chi2"], ms[:5].tolist())), int(ms[5])
 
     def LocalBundleAdjustment(self, G: BAGraph, stop_flag: np.ndarray | None = None) -> BAResult:
         lib, h = self.ctx.lib, self.ctx.handle
@@ -568,6 +661,112 @@ def synth_sim3_problem(rng, n_pairs=100, outlier_frac=0.1, out_of_kf2_frac=0.0, 
     s0 = s if fix_scale else s * float(1 + rng.normal(0, 0.01))
     return Sim3Problem(rot_to_quat(R0), t0, s0, p1c.astype(np.float64), p2c.astype(np.float64), obs1, obs2, w1, w2,
                        fix_scale=bool(fix_scale), th2=th2, cam1=cam1, cam2=cam2, truth=(R, t, s))
+
+
+def rodrigues(w):
+    w = np.asarray(w, float)
+    a = np.linalg.norm(w)
+    if a < 1e-300:
+        return np.eye(3)
+    k = w / a
+    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    return np.eye(3) + np.sin(a) * K + (1 - np.cos(a)) * K @ K
+
+
+def s3_mul(a, b):
+    return a[0] @ b[0], a[2] * (a[0] @ b[1]) + a[1], a[2] * b[2]
+
+
+def s3_inv(a):
+    return a[0].T, a[0].T @ (-a[1] / a[2]), 1.0 / a[2]
+
+
+def s3_row(a):
+    return np.concatenate([rot_to_quat(a[0]), a[1], [a[2]]])
+
+
+def synth_essential_graph(rng, n_kf, n_loop=3, extra_loops=0, fix_scale=False, consistent=False,
+                          drift=(3.0, 0.2, 0.05), radius=0.8):
+    """The pose graph LoopClosing::CorrectLoop hands to OptimizeEssentialGraph after closing a loop: n_kf
+    KeyFrames on a closed trajectory (a circle of ``radius`` m, about 5 m long, cameras looking at its centre),
+    KeyFrame 0 fixed (the map's init KeyFrame), the last ``n_loop`` KeyFrames carrying a corrected Sim3.  Edges
+    in the reference's insertion order: the LoopConnections (corrected KeyFrame k -> the KeyFrames
+    k - (n_kf - n_loop) and k - (n_kf - n_loop) + 1 at the start), then per KeyFrame i its spanning-tree edge
+    (i -> i - 1), its earlier loop edges (``extra_loops`` of them between the middle of the map and its first
+    third, to the smaller id), and its covisibility edges (i -> i - 2, i -> i - 3).
+
+    The drift grows linearly along the trajectory to ``drift`` = (degrees, metres, relative scale) at its end
+    and is applied on the world side (S_i = G_i * D_i).
+      consistent=False: as the reference builds it.  The non-corrected poses N_i are the drifted ones with
+        scale 1, the corrected Sim3 of the last KeyFrames is N_i * D_end^-1 (with the drifted scale unless
+        ``fix_scale``), every non-loop measurement is N_j * N_i^-1 and every loop measurement S_j * S_i^-1 of
+        the initial estimates.
+      consistent=True: the measurements are G_j * G_i^-1 of a ground truth G (returned as ``truth``; scales
+        drawn in [0.95, 1.05] unless ``fix_scale``), the corrected KeyFrames start at the truth and the others
+        at G_i * D_i, so the optimum is the truth with chi2 = 0."""
+    n, m = int(n_kf), int(n_loop)
+    assert n >= 2 and 0 <= m < n
+    ang = 2 * np.pi * np.arange(n) / n
+    G = []
+    for i in range(n):
+        c = np.array([radius * np.cos(ang[i]), 0.05 * np.sin(3 * ang[i]), radius * np.sin(ang[i])])
+        R, t = look_at(c, [0.0, 0.3 * rng.normal(), 0.0])
+        s = 1.0 if (fix_scale or not consistent) else float(rng.uniform(0.95, 1.05))
+        G.append((R, s * t, s))
+    axis = rng.normal(size=3)
+    axis /= np.linalg.norm(axis)
+    tdir = rng.normal(size=3)
+    tdir /= np.linalg.norm(tdir)
+
+    def D(f):
+        return (rodrigues(np.deg2rad(drift[0]) * f * axis), drift[1] * f * tdir,
+                1.0 if fix_scale else float(np.exp(np.log1p(drift[2]) * f)))
+
+    frac = np.arange(n) / max(n - 1, 1)
+    corrected = np.zeros(n, bool)
+    corrected[n - m:] = True
+    if consistent:
+        est = [G[i] if corrected[i] or i == 0 else s3_mul(G[i], D(frac[i])) for i in range(n)]
+        base = G
+    else:
+        N = []
+        for i in range(n):
+            d = D(frac[i])
+            N.append(s3_mul(G[i], (d[0], d[1], 1.0)))
+        Dinv = s3_inv(D(1.0))
+        est = [s3_mul(N[i], Dinv) if corrected[i] else N[i] for i in range(n)]
+        base = N
+    loops = {}
+    for q in range(int(extra_loops)):
+        a = n // 2 + 3 * q + 1
+        b = n // 5 + 2 * q
+        if b < a - 3 and a < n - m:
+            loops.setdefault(a, []).append(b)
+    v0, v1, meas = [], [], []
+
+    def edge(i, j, src):
+        v0.append(i)
+        v1.append(j)
+        meas.append(s3_row(s3_mul(src[j], s3_inv(src[i]))))
+
+    loop_src = base if consistent else est
+    for k in range(n - m, n):
+        for j in (k - (n - m), k - (n - m) + 1):
+            if 0 <= j < n - m and j != k:
+                edge(k, j, loop_src)
+    for i in range(n):
+        if i >= 1:
+            edge(i, i - 1, base)
+        for b in loops.get(i, []):
+            edge(i, b, base)
+        for j in (i - 2, i - 3):
+            if j >= 0:
+                edge(i, j, base)
+    fixed = np.zeros(n, np.uint8)
+    fixed[0] = 1
+    return EssentialGraphProblem(np.array([s3_row(e) for e in est]), fixed, np.array(v0, np.int32), np.array(v1, np.int32),
+                                 np.array(meas).reshape(-1, 8), fix_scale=bool(fix_scale),
+                                 truth=np.array([s3_row(g) for g in G]) if consistent else None)
 
 
 def synth_lba_graph(rng, n_kf=50, n_points=10000, k_range=(2, 8), n_fixed=2, stereo_frac=0.0,
