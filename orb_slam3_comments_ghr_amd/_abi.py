@@ -224,6 +224,32 @@ class OsgBowOut(C.Structure):
     ]
 
 
+class OsgKfdbState(C.Structure):
+    _fields_ = [
+        ("place_query", C.c_int64), ("reloc_query", C.c_int64), ("place_words", i32), ("reloc_words", i32),
+        ("place_score", f32), ("reloc_score", f32),
+    ]
+
+
+class OsgKfdbQueryOut(C.Structure):
+    _fields_ = [
+        ("n_sharing", i32), ("max_common_words", i32), ("min_common_words", i32), ("n_scored", i32),
+        ("capacity", i32), ("entry", P), ("words", P), ("score", P), ("score_f64", P),
+    ]
+
+
+class OsgKfdbKf(C.Structure):
+    _fields_ = [
+        ("query", C.c_int64), ("score", f32), ("handle", i32), ("map_id", i32), ("bad", C.c_uint8),
+        ("map_bad", C.c_uint8), ("pad", C.c_uint8 * 2),
+    ]
+
+
+OSG_KFDB_PLACE = 0
+OSG_KFDB_RELOC = 1
+OSG_KFDB_MAX_NEIGH = 10
+
+
 # Every symbol include/osg.h, include/osg_ba.h and include/osg_dbow.h declare (checked by tests/test_abi.py).
 EXPORTS = [
     "osg_ctx_create", "osg_ctx_destroy", "osg_ctx_set_stream", "osg_ctx_stream",
@@ -240,6 +266,9 @@ EXPORTS = [
     "osg_optimize_essential_graph", "osg_essgraph_correct_points", "osg_essgraph_kernel_times",
     "osg_vocabulary_create", "osg_vocabulary_load_text", "osg_vocabulary_destroy", "osg_vocabulary_info",
     "osg_vocabulary_transform", "osg_vocabulary_transform_batch",
+    "osg_kfdb_create", "osg_kfdb_destroy", "osg_kfdb_size", "osg_kfdb_add", "osg_kfdb_erase",
+    "osg_kfdb_clear", "osg_kfdb_clear_map", "osg_kfdb_state_get", "osg_kfdb_state_set", "osg_kfdb_query",
+    "osg_kfdb_select_nbest", "osg_kfdb_select_reloc",
     "osg_fuse_search", "osg_fuse_search_batch", "osg_search_for_triangulation", "osg_search_for_triangulation_batch",
     "osg_compute_distinctive_descriptors", "osg_compute_distinctive_descriptors_dev",
     "osg_search_by_projection_sim3", "osg_search_by_projection_sim3_batch", "osg_search_by_sim3",
@@ -315,6 +344,18 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.osg_vocabulary_info.argtypes = [vp, vp]
     lib.osg_vocabulary_transform.argtypes = [vp, vp, vp, i32, i32, C.POINTER(OsgBowOut)]
     lib.osg_vocabulary_transform_batch.argtypes = [vp, vp, vp, vp, i32, i32, vp]
+    lib.osg_kfdb_create.argtypes = [vp, vp, C.POINTER(vp)]
+    lib.osg_kfdb_destroy.argtypes = [vp]
+    lib.osg_kfdb_size.argtypes = [vp, vp]
+    lib.osg_kfdb_add.argtypes = [vp, vp, i32, vp, vp, i32, C.POINTER(OsgKfdbState), C.POINTER(i32)]
+    lib.osg_kfdb_erase.argtypes = [vp, vp, i32]
+    lib.osg_kfdb_clear.argtypes = [vp, vp]
+    lib.osg_kfdb_clear_map.argtypes = [vp, vp, i32]
+    lib.osg_kfdb_state_get.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp]
+    lib.osg_kfdb_state_set.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp]
+    lib.osg_kfdb_query.argtypes = [vp, vp, i32, C.c_int64, i32, vp, vp, i32, vp, C.POINTER(OsgKfdbQueryOut)]
+    lib.osg_kfdb_select_nbest.argtypes = [i32, vp, vp, vp, C.c_int64, i32, i32, vp, vp, vp, vp]
+    lib.osg_kfdb_select_reloc.argtypes = [i32, vp, vp, vp, C.c_int64, i32, vp, vp]
     lib.osg_fuse_search.argtypes = [vp, C.POINTER(OsgFrame), C.POINTER(OsgFuseQueries), f32, C.c_int, C.c_int,
                                     vp, vp]
     lib.osg_fuse_search_batch.argtypes = [vp, vp, vp, i32, f32, C.c_int, C.c_int, vp, vp, vp]

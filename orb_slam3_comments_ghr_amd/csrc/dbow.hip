@@ -431,6 +431,13 @@ int voc_upload(osg_ctx *ctx, const osg_vocabulary_desc *V, osg_vocabulary **out)
 
 }  // namespace
 
+// for kfdb.hip: the word count and ScoringType a database is created against
+void osg_vocabulary_words_scoring(const osg_vocabulary *voc, int32_t *n_words, int32_t *scoring)
+{
+    *n_words = voc->n_words;
+    *scoring = voc->scoring;
+}
+
 extern "C" {
 
 int osg_vocabulary_create(osg_ctx *ctx, const osg_vocabulary_desc *v, osg_vocabulary **out)

@@ -121,6 +121,10 @@ int osg_detect_batch(osg_ctx *ctx, const osg_image_pyramid *raw0, int32_t B, int
                      int32_t min_th_fast, const int32_t *n_features_per_level, const float *scale_factors,
                      int32_t capacity, float *x, float *y, float *response, float *size, int32_t *level_start);
 
+// dbow.hip, for kfdb.hip
+struct osg_vocabulary;
+void osg_vocabulary_words_scoring(const osg_vocabulary *voc, int32_t *n_words, int32_t *scoring);
+
 // ---- host worker threads -------------------------------------------------------------------------
 // CPUs this process may run on at once: the smallest of the hardware threads, the affinity mask and
 // the cgroup CPU quota (a GPU box's container sees every core of the host but is granted a share),
