@@ -19,7 +19,7 @@ HIPFLAGS += -DOSG_SR_PROF
 endif
 HDRS = include/osg.h include/osg_ba.h $(CSRC)/osg_internal.h
 
-OBJS = $(OBJDIR)/runtime.o $(OBJDIR)/hamming.o $(OBJDIR)/hamming_mfma.o $(OBJDIR)/match.o $(OBJDIR)/pose.o $(OBJDIR)/sim3opt.o $(OBJDIR)/sim3ransac.o $(OBJDIR)/essgraph.o $(OBJDIR)/ba.o $(OBJDIR)/dbow.o $(OBJDIR)/kfdb.o $(OBJDIR)/fuse.o $(OBJDIR)/triang.o $(OBJDIR)/desc.o $(OBJDIR)/sim3.o $(OBJDIR)/init.o $(OBJDIR)/stereo.o $(OBJDIR)/orb.o $(OBJDIR)/fast.o $(OBJDIR)/pyramid.o
+OBJS = $(OBJDIR)/runtime.o $(OBJDIR)/hamming.o $(OBJDIR)/hamming_mfma.o $(OBJDIR)/match.o $(OBJDIR)/pose.o $(OBJDIR)/sim3opt.o $(OBJDIR)/sim3ransac.o $(OBJDIR)/twoview.o $(OBJDIR)/essgraph.o $(OBJDIR)/ba.o $(OBJDIR)/dbow.o $(OBJDIR)/kfdb.o $(OBJDIR)/fuse.o $(OBJDIR)/triang.o $(OBJDIR)/desc.o $(OBJDIR)/sim3.o $(OBJDIR)/init.o $(OBJDIR)/stereo.o $(OBJDIR)/orb.o $(OBJDIR)/fast.o $(OBJDIR)/pyramid.o
 
 WALL_BENCH = tools/adapter_wall_bench
 
@@ -41,6 +41,8 @@ $(OBJDIR)/pose.o: $(CSRC)/pose.hip $(HDRS) $(CSRC)/ba_common.h $(CSRC)/exact_mat
 $(OBJDIR)/sim3opt.o: $(CSRC)/sim3opt.hip $(HDRS) $(CSRC)/ba_common.h $(CSRC)/sim3_common.h $(CSRC)/exact_math.h $(CSRC)/glibc_math.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
 $(OBJDIR)/sim3ransac.o: $(CSRC)/sim3ransac.hip $(HDRS) $(CSRC)/sim3ransac_select.h $(CSRC)/glibc_math.h | $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
+$(OBJDIR)/twoview.o: $(CSRC)/twoview.hip $(HDRS) $(CSRC)/twoview_select.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
 $(OBJDIR)/essgraph.o: $(CSRC)/essgraph.hip $(HDRS) $(CSRC)/sim3_common.h $(CSRC)/exact_math.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@

@@ -319,6 +319,8 @@ struct OsgHooks {
     static Eigen::Matrix3f mat3(const float *m) { return Eigen::Map<const Eigen::Matrix<float, 3, 3, Eigen::RowMajor>>(m); }
     static Eigen::Vector3f vec3(const float *v) { return Eigen::Vector3f(v[0], v[1], v[2]); }
     static int random_int(int min, int max) { return DUtils::Random::RandomInt(min, max); }  // :174
+    // TwoViewReconstruction (ref:src/TwoViewReconstruction.cc:96)
+    static void seed_rand_once(int seed) { DUtils::Random::SeedRandOnce(seed); }
     // KeyFrameDatabase: the vocabulary on the device, set by System right after it loads ORBvoc
     // (osg_vocabulary_load_text) and before it constructs the database
     static const osg_vocabulary *&device_vocabulary()

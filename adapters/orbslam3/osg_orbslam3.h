@@ -2630,6 +2630,111 @@ private:
     float mBestT12[16], mBestRotation[9], mBestTranslation[3], mBestScale = 1.f;
 };
 
+// ------------------------------------------------------------------------- TwoViewReconstruction
+// TwoViewReconstruction::Reconstruct (ref:src/TwoViewReconstruction.cc:49-151) on osg_two_view_reconstruct.
+// Hooks (beside random_int above):
+//   static void H::seed_rand_once(int seed)                         DUtils::Random::SeedRandOnce
+// The body builds mvMatches12 / mvbMatched1 as the reference does, draws mvSets through H::random_int after
+// H::seed_rand_once(0) in the reference's call order (8 draws per iteration, mMaxIterations iterations), and
+// hands the kept matches, all keypoints of both frames (Normalize runs over them) and the sets to the
+// library.  R21 (row-major) / t21, vP3D and vbTriangulated are written only when the call returns true, as in
+// the reference; vP3D is then filled for a homography too (the reference's ReconstructH leaves it as it was,
+// and Tracking reads it).  Fewer than 8 matches (the reference draws from an empty list) and ABI errors
+// return false.  KannalaBrandt8::ReconstructWithTwoViews undistorts on the host and reaches this same body.
+template <class H, class KeyPointT, class PointT>
+class TwoViewReconstruction {
+public:
+    TwoViewReconstruction(float fx, float fy, float cx, float cy, float sigma = 1.0f, int iterations = 200)
+        : mSigma(sigma), mMaxIterations(iterations)
+    {
+        mK[0] = fx, mK[1] = fy, mK[2] = cx, mK[3] = cy;
+    }
+
+    bool Reconstruct(const std::vector<KeyPointT> &vKeys1, const std::vector<KeyPointT> &vKeys2,
+                     const std::vector<int> &vMatches12, float R21[9], float t21[3], std::vector<PointT> &vP3D,
+                     std::vector<bool> &vbTriangulated)
+    {
+        mvMatches12.clear();
+        mvMatches12.reserve(vKeys2.size());
+        mvbMatched1.resize(vKeys1.size());
+        for (size_t i = 0, iend = vMatches12.size(); i < iend; i++) {
+            if (vMatches12[i] >= 0) {
+                mvMatches12.push_back(std::make_pair((int)i, vMatches12[i]));
+                mvbMatched1[i] = true;
+            } else
+                mvbMatched1[i] = false;
+        }
+        const int N = (int)mvMatches12.size();
+        if (N < 8 || mMaxIterations < 1) return false;
+        mvSets.assign(8 * (size_t)mMaxIterations, 0);
+        std::vector<size_t> vAllIndices(N), vAvailableIndices;
+        for (int i = 0; i < N; i++) vAllIndices[i] = (size_t)i;
+        H::seed_rand_once(0);
+        for (int it = 0; it < mMaxIterations; it++) {
+            vAvailableIndices = vAllIndices;
+            for (size_t j = 0; j < 8; j++) {
+                const int randi = H::random_int(0, (int)vAvailableIndices.size() - 1);
+                mvSets[8 * (size_t)it + j] = (int32_t)vAvailableIndices[randi];
+                vAvailableIndices[randi] = vAvailableIndices.back();
+                vAvailableIndices.pop_back();
+            }
+        }
+        std::vector<float> keys1(2 * vKeys1.size()), keys2(2 * vKeys2.size()), kp1(2 * (size_t)N), kp2(2 * (size_t)N);
+        for (size_t i = 0; i < vKeys1.size(); i++) keys1[2 * i] = vKeys1[i].pt.x, keys1[2 * i + 1] = vKeys1[i].pt.y;
+        for (size_t i = 0; i < vKeys2.size(); i++) keys2[2 * i] = vKeys2[i].pt.x, keys2[2 * i + 1] = vKeys2[i].pt.y;
+        std::vector<int32_t> idx1(N), idx2(N);
+        for (int i = 0; i < N; i++) {
+            idx1[i] = mvMatches12[i].first, idx2[i] = mvMatches12[i].second;
+            if (idx2[i] >= (int)vKeys2.size()) return false;
+            kp1[2 * i] = keys1[2 * (size_t)idx1[i]], kp1[2 * i + 1] = keys1[2 * (size_t)idx1[i] + 1];
+            kp2[2 * i] = keys2[2 * (size_t)idx2[i]], kp2[2 * i + 1] = keys2[2 * (size_t)idx2[i] + 1];
+        }
+        std::vector<float> p3d(3 * vKeys1.size());
+        std::vector<uint8_t> tri(vKeys1.size()), inl_h(N), inl_f(N);
+        osg_two_view_problem p{};
+        for (int k = 0; k < 4; k++) p.K[k] = mK[k];
+        p.sigma = mSigma;
+        p.n_hyp = mMaxIterations;
+        p.n = N;
+        p.kp1 = kp1.data(), p.kp2 = kp2.data();
+        p.n_keys1 = (int32_t)vKeys1.size(), p.n_keys2 = (int32_t)vKeys2.size();
+        p.keys1 = keys1.data(), p.keys2 = keys2.data();
+        p.idx1 = idx1.data(), p.idx2 = idx2.data();
+        p.sets = mvSets.data();
+        p.min_parallax = 1.0f;   // :136
+        p.min_triangulated = 50;  // :144, :149
+        r = osg_two_view_result{};
+        r.p3d = p3d.data(), r.triangulated = tri.data(), r.inlier_h = inl_h.data(), r.inlier_f = inl_f.data();
+        osg_ctx *ctx = thread_ctx();
+        const int rc = call(ctx, "osg_two_view_reconstruct", [&] { return osg_two_view_reconstruct(ctx, &p, &r); });
+        r.p3d = nullptr, r.triangulated = nullptr, r.inlier_h = r.inlier_f = nullptr;
+        if (rc <= 0) return false;
+        for (int k = 0; k < 9; k++) R21[k] = r.R[k];
+        for (int k = 0; k < 3; k++) t21[k] = r.t[k];
+        vP3D.resize(vKeys1.size());
+        vbTriangulated.assign(vKeys1.size(), false);
+        for (size_t i = 0; i < vKeys1.size(); i++) {
+            vP3D[i].x = p3d[3 * i], vP3D[i].y = p3d[3 * i + 1], vP3D[i].z = p3d[3 * i + 2];
+            vbTriangulated[i] = tri[i] != 0;
+        }
+        return true;
+    }
+
+    // the reference's members, for the tests
+    const std::vector<std::pair<int, int>> &matches12() const { return mvMatches12; }
+    const std::vector<bool> &matched1() const { return mvbMatched1; }
+    const std::vector<int32_t> &sets() const { return mvSets; }
+    const osg_two_view_result &result() const { return r; }  // scalars of the last call (the array pointers are null)
+
+private:
+    float mK[4], mSigma;
+    int mMaxIterations;
+    std::vector<std::pair<int, int>> mvMatches12;
+    std::vector<bool> mvbMatched1;
+    std::vector<int32_t> mvSets;
+    osg_two_view_result r{};
+};
+
 // ------------------------------------------------------------------------------ batched forms
 // B independent problems gathered from the reference's objects, solved in one launch (the
 // osg_*_batch entry points: one workgroup or frame slice per problem), and written back exactly as

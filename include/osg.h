@@ -369,6 +369,64 @@ int osg_search_for_initialization_batch(osg_ctx *ctx, const osg_frame *F1, const
                                         float *prev_xy, int window_size, float nnratio, int check_orientation,
                                         int32_t *matches12, int32_t *nmatches);
 
+/* ---- TwoViewReconstruction::Reconstruct ------------------------------------------------------------
+ * ref:src/TwoViewReconstruction.cc:49-1223, ref:src/GeometricTools.cc:62-89 (monocular initialisation,
+ * ref:src/Tracking.cc:2970): every RANSAC hypothesis of FindHomography and FindFundamental is evaluated in
+ * one launch, the reference's sequential choice is replayed on the scores, the chosen model is decomposed
+ * into 8 (H) or 4 (F) motion hypotheses and each is checked against all inlier matches (CheckRT).
+ *
+ * The n kept matches are given in the order of mvMatches12 (increasing keypoint index in frame 1):
+ * kp1 / kp2 hold their (x, y) (kp1[i] is keys1[idx1[i]], kp2[i] is keys2[idx2[i]]); keys1 / keys2 are all
+ * n_keys1 / n_keys2 undistorted keypoints of the two frames, over which Normalize runs.  sets holds 8
+ * indices into [0, n) per hypothesis in draw order (mvSets); the draw stays with the caller.
+ * n < 8: the reference draws from an empty list, which is undefined; here nothing is evaluated, ok = 0,
+ * model = -1.  OSG_E_INVALID: a set index outside [0, n) or repeated within a set; idx1 not strictly increasing
+ * or outside [0, n_keys1) (two matches of one frame-1 keypoint would write the same vP3D entry); idx2 outside
+ * [0, n_keys2). */
+typedef struct {
+    float K[4];               /* fx fy cx cy */
+    float sigma;              /* mSigma: 1.0 */
+    int32_t n_hyp;            /* mMaxIterations: 200 */
+    int32_t n;                /* kept matches */
+    const float *kp1, *kp2;   /* n x 2 */
+    int32_t n_keys1, n_keys2;
+    const float *keys1, *keys2; /* n_keys x 2 */
+    const int32_t *idx1, *idx2; /* n: mvMatches12[i].first / .second */
+    const int32_t *sets;      /* n_hyp x 8 */
+    float min_parallax;       /* 1.0 */
+    int32_t min_triangulated; /* 50 */
+} osg_two_view_problem;
+
+typedef struct {
+    int32_t ok;               /* Reconstruct's return value */
+    int32_t model;            /* 0: H, 1: F, -1: SH + SF == 0 (or n < 8) */
+    float score_h, score_f;   /* SH, SF */
+    int32_t hyp_h, hyp_f;     /* the lowest hypothesis of maximal score (-1: every score is 0) */
+    float H21[9], F21[9];     /* row-major; zeros when hyp is -1 */
+    float R[9], t[3];         /* T21 (identity, 0 unless ok) */
+    int32_t cand;             /* the motion hypothesis the acceptance rule looked at (-1: none) */
+    int32_t n_inliers;        /* inliers of the chosen model: N of ReconstructF / ReconstructH */
+    int32_t n_good[8];        /* CheckRT's nGood per motion hypothesis (4 used for F) */
+    float parallax[8];
+    float cand_Rt[96];        /* the motion hypotheses: R[9] t[3] each */
+    float *p3d;               /* n_keys1 x 3: vP3D (0 where nothing was triangulated, and unless ok).  The
+                                 reference's ReconstructH leaves vP3D untouched; here it is written as for F */
+    uint8_t *triangulated;    /* n_keys1: vbTriangulated (0 unless ok) */
+    uint8_t *inlier_h, *inlier_f; /* n: vbMatchesInliersH / F */
+    float *hyp_score_h, *hyp_score_f; /* optional (NULL: not written): n_hyp scores.  A score that is not finite is
+                                 reported as 0: the reference's NaN never passes `currentScore > score` either */
+    float *hyp_models;        /* optional: n_hyp x 18, H21i then F21i */
+} osg_two_view_result;
+
+/* Returns ok (0 / 1) or a negative error. */
+int osg_two_view_reconstruct(osg_ctx *ctx, const osg_two_view_problem *p, osg_two_view_result *r);
+/* nb independent problems in the same launches.  Returns the number of problems with ok = 1. */
+int osg_two_view_reconstruct_batch(osg_ctx *ctx, const osg_two_view_problem *p, int32_t nb, osg_two_view_result *r);
+/* Measurement aid: enable != 0 makes this thread's later calls time each of their five launches (normalise,
+ * hypotheses, choice, CheckRT, acceptance) with HIP events of their own; ms (NULL: not read) receives the five
+ * times of the last timed call in milliseconds. */
+int osg_two_view_kernel_times(osg_ctx *ctx, int32_t enable, float *ms);
+
 /* ---- b5: the Sim3 projections of LoopClosing -------------------------------------------------------
  *   SearchByProjection(KeyFrame*, Sophus::Sim3f& Scw, const vector<MapPoint*>&, vector<MapPoint*>& vpMatched,
  *                      th, ratioHamming)                                  ref:src/ORBmatcher.cc:498-621

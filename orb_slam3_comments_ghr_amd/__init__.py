@@ -15,7 +15,7 @@ import numpy as np
 from . import _abi
 from ._abi import LIB_PATH
 
-__all__ = ["load_library", "Context", "OsgError", "LIB_PATH"]
+__all__ = ["load_library", "Context", "OsgError", "LIB_PATH", "TwoViewReconstruction", "draw_sets"]
 
 _lib = None
 
@@ -179,3 +179,11 @@ def descriptor_distance(a: np.ndarray, b: np.ndarray) -> int:
     a = np.ascontiguousarray(a, dtype=np.uint8).reshape(32)
     b = np.ascontiguousarray(b, dtype=np.uint8).reshape(32)
     return int(lib.osg_descriptor_distance(_ptr(a), _ptr(b)))
+
+
+def __getattr__(name):
+    # the monocular initialiser (twoview.py imports this module, so it is resolved on first use)
+    if name in ("TwoViewReconstruction", "draw_sets"):
+        from . import twoview
+        return getattr(twoview, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

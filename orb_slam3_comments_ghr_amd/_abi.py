@@ -180,6 +180,23 @@ class OsgSim3RansacResult(C.Structure):
     ]
 
 
+class OsgTwoViewProblem(C.Structure):
+    _fields_ = [
+        ("K", f32 * 4), ("sigma", f32), ("n_hyp", i32), ("n", i32), ("kp1", P), ("kp2", P), ("n_keys1", i32),
+        ("n_keys2", i32), ("keys1", P), ("keys2", P), ("idx1", P), ("idx2", P), ("sets", P), ("min_parallax", f32),
+        ("min_triangulated", i32),
+    ]
+
+
+class OsgTwoViewResult(C.Structure):
+    _fields_ = [
+        ("ok", i32), ("model", i32), ("score_h", f32), ("score_f", f32), ("hyp_h", i32), ("hyp_f", i32),
+        ("H21", f32 * 9), ("F21", f32 * 9), ("R", f32 * 9), ("t", f32 * 3), ("cand", i32), ("n_inliers", i32),
+        ("n_good", i32 * 8), ("parallax", f32 * 8), ("cand_Rt", f32 * 96), ("p3d", P), ("triangulated", P),
+        ("inlier_h", P), ("inlier_f", P), ("hyp_score_h", P), ("hyp_score_f", P), ("hyp_models", P),
+    ]
+
+
 class OsgEssGraphProblem(C.Structure):
     _fields_ = [
         ("n_vertices", i32), ("sim3", P), ("fixed", P), ("fix_scale", i32), ("n_edges", i32), ("e_v0", P),
@@ -273,6 +290,7 @@ EXPORTS = [
     "osg_compute_distinctive_descriptors", "osg_compute_distinctive_descriptors_dev",
     "osg_search_by_projection_sim3", "osg_search_by_projection_sim3_batch", "osg_search_by_sim3",
     "osg_search_for_initialization", "osg_search_for_initialization_batch",
+    "osg_two_view_reconstruct", "osg_two_view_reconstruct_batch", "osg_two_view_kernel_times",
     "osg_compute_stereo_matches", "osg_compute_stereo_matches_batch", "osg_compute_stereo_fisheye_matches",
     "osg_orb_describe", "osg_orb_detect", "osg_orb_extract_batch",
     "osg_debug_distribute_oct_tree", "osg_orb_pyramid_layout", "osg_orb_pyramid", "osg_debug_gaussian_kernel7",
@@ -328,6 +346,9 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.osg_sim3_ransac.argtypes = [vp, C.POINTER(OsgSim3RansacProblem), C.POINTER(OsgSim3RansacResult)]
     lib.osg_sim3_ransac_batch.argtypes = [vp, C.POINTER(OsgSim3RansacProblem), i32, C.POINTER(OsgSim3RansacResult)]
     lib.osg_sim3_ransac_iterations.argtypes = [C.c_double, i32, i32, i32]
+    lib.osg_two_view_reconstruct.argtypes = [vp, C.POINTER(OsgTwoViewProblem), C.POINTER(OsgTwoViewResult)]
+    lib.osg_two_view_reconstruct_batch.argtypes = [vp, C.POINTER(OsgTwoViewProblem), i32, C.POINTER(OsgTwoViewResult)]
+    lib.osg_two_view_kernel_times.argtypes = [vp, i32, vp]
     lib.osg_sim3_ransac_iterations.restype = i32
     lib.osg_optimize_essential_graph.argtypes = [vp, C.POINTER(OsgEssGraphProblem), C.POINTER(OsgEssGraphResult)]
     lib.osg_essgraph_correct_points.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp]

@@ -16,6 +16,7 @@ SEED_C4 = 0x0B5EED04
 EUROC_W, EUROC_H = 752, 480
 EUROC_FX, EUROC_FY, EUROC_CX, EUROC_CY = 458.654, 457.296, 367.215, 248.375
 EUROC_BF = 47.9
+EUROC_K = (EUROC_FX, EUROC_FY, EUROC_CX, EUROC_CY)
 
 
 def _flip_bits(rng: np.random.Generator, rows: np.ndarray, p: float) -> np.ndarray:
@@ -53,3 +54,47 @@ def descriptors_stream(nq: int = 4, nt: int = 1 << 24, seed: int = SEED_C2_STREA
         rows = rng.integers(0, nt, size=3)
         t[rows] = _flip_bits(rng, np.repeat(q[j:j + 1], 3, axis=0), 0.05)
     return q, t
+
+
+def two_view_scene(rng, n=100, scene="general", noise_px=0.5, outlier_frac=0.0, extra1=37, extra2=23, n_hyp=200,
+                   baseline=0.5, rot_deg=4.0, K=EUROC_K, depth=(2.0, 8.0)):
+    """Two monocular frames of one synthetic scene as the initialiser sees them: ``n`` matched keypoints (pixel
+    noise ``noise_px`` in both frames, ``outlier_frac`` of them with an unrelated frame-2 position) among
+    ``extra1`` / ``extra2`` unmatched ones, frame 2's keypoints in shuffled order.  ``scene``: "general" (points
+    at 2 .. 8 m), "planar" (a slanted plane), "rotation" (no baseline).  The sets are drawn as the reference
+    draws them, from a seeded stream."""
+    from .optimizer import small_rotation
+    from .twoview import TwoViewProblem, seeded_sets
+
+    fx, fy, cx, cy = K
+    R = small_rotation(rng, rot_deg)
+    t = np.zeros(3) if scene == "rotation" else baseline * np.array([1.0, 0.15, 0.1]) / np.linalg.norm([1.0, 0.15, 0.1])
+    k1, k2 = [], []
+    while len(k1) < n:
+        u = rng.uniform(20, EUROC_W - 20)
+        v = rng.uniform(20, EUROC_H - 20)
+        x, y = (u - cx) / fx, (v - cy) / fy
+        z = 5.0 / (1.0 + 0.3 * x + 0.2 * y) if scene == "planar" else rng.uniform(*depth)
+        X2 = R @ np.array([x * z, y * z, z]) + t
+        if X2[2] <= 0.1:
+            continue
+        u2, v2 = fx * X2[0] / X2[2] + cx, fy * X2[1] / X2[2] + cy
+        if not (20 < u2 < EUROC_W - 20 and 20 < v2 < EUROC_H - 20):
+            continue
+        k1.append((u, v))
+        k2.append((u2, v2))
+    k1 = np.array(k1).reshape(-1, 2) + rng.normal(0, noise_px, (n, 2))
+    k2 = np.array(k2).reshape(-1, 2) + rng.normal(0, noise_px, (n, 2))
+    out = rng.random(n) < outlier_frac
+    wrong = np.stack([rng.uniform(20, EUROC_W - 20, n), rng.uniform(20, EUROC_H - 20, n)], 1)
+    k2 = np.where(out[:, None], wrong, k2)
+    rand_keys = lambda m: np.stack([rng.uniform(0, EUROC_W, m), rng.uniform(0, EUROC_H, m)], 1)  # noqa: E731
+    n1, n2 = n + extra1, n + extra2
+    slot1 = np.sort(rng.choice(n1, n, replace=False))  # where the matched keypoints sit in frame 1
+    slot2 = rng.choice(n2, n, replace=False)
+    keys1, keys2 = rand_keys(n1), rand_keys(n2)
+    keys1[slot1], keys2[slot2] = k1, k2
+    m12 = np.full(n1, -1, np.int32)
+    m12[slot1] = slot2
+    sets = seeded_sets(n, n_hyp, int(rng.integers(1 << 30)))
+    return TwoViewProblem(keys1, keys2, m12, sets, K=tuple(K), truth=(R, t, out))
