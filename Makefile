@@ -17,9 +17,13 @@ endif
 ifdef SR_PROF
 HIPFLAGS += -DOSG_SR_PROF
 endif
+# make MLPNP_PROF=1: k_mlpnp_eval's per-stage clock stamps in place of the per-hypothesis poses (tools/mlpnp_prof.py)
+ifdef MLPNP_PROF
+HIPFLAGS += -DOSG_MLPNP_PROF
+endif
 HDRS = include/osg.h include/osg_ba.h $(CSRC)/osg_internal.h
 
-OBJS = $(OBJDIR)/runtime.o $(OBJDIR)/hamming.o $(OBJDIR)/hamming_mfma.o $(OBJDIR)/match.o $(OBJDIR)/pose.o $(OBJDIR)/sim3opt.o $(OBJDIR)/sim3ransac.o $(OBJDIR)/twoview.o $(OBJDIR)/essgraph.o $(OBJDIR)/ba.o $(OBJDIR)/dbow.o $(OBJDIR)/kfdb.o $(OBJDIR)/fuse.o $(OBJDIR)/triang.o $(OBJDIR)/desc.o $(OBJDIR)/sim3.o $(OBJDIR)/init.o $(OBJDIR)/stereo.o $(OBJDIR)/orb.o $(OBJDIR)/fast.o $(OBJDIR)/pyramid.o
+OBJS = $(OBJDIR)/runtime.o $(OBJDIR)/hamming.o $(OBJDIR)/hamming_mfma.o $(OBJDIR)/match.o $(OBJDIR)/pose.o $(OBJDIR)/sim3opt.o $(OBJDIR)/sim3ransac.o $(OBJDIR)/mlpnp.o $(OBJDIR)/twoview.o $(OBJDIR)/essgraph.o $(OBJDIR)/ba.o $(OBJDIR)/dbow.o $(OBJDIR)/kfdb.o $(OBJDIR)/fuse.o $(OBJDIR)/triang.o $(OBJDIR)/desc.o $(OBJDIR)/sim3.o $(OBJDIR)/init.o $(OBJDIR)/stereo.o $(OBJDIR)/orb.o $(OBJDIR)/fast.o $(OBJDIR)/pyramid.o
 
 WALL_BENCH = tools/adapter_wall_bench
 
@@ -41,6 +45,8 @@ $(OBJDIR)/pose.o: $(CSRC)/pose.hip $(HDRS) $(CSRC)/ba_common.h $(CSRC)/exact_mat
 $(OBJDIR)/sim3opt.o: $(CSRC)/sim3opt.hip $(HDRS) $(CSRC)/ba_common.h $(CSRC)/sim3_common.h $(CSRC)/exact_math.h $(CSRC)/glibc_math.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
 $(OBJDIR)/sim3ransac.o: $(CSRC)/sim3ransac.hip $(HDRS) $(CSRC)/sim3ransac_select.h $(CSRC)/glibc_math.h | $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
+$(OBJDIR)/mlpnp.o: $(CSRC)/mlpnp.hip $(HDRS) $(CSRC)/mlpnp_select.h $(CSRC)/glibc_math.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
 $(OBJDIR)/twoview.o: $(CSRC)/twoview.hip $(HDRS) $(CSRC)/twoview_select.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@

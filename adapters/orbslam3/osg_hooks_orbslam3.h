@@ -319,6 +319,12 @@ struct OsgHooks {
     static Eigen::Matrix3f mat3(const float *m) { return Eigen::Map<const Eigen::Matrix<float, 3, 3, Eigen::RowMajor>>(m); }
     static Eigen::Vector3f vec3(const float *v) { return Eigen::Vector3f(v[0], v[1], v[2]); }
     static int random_int(int min, int max) { return DUtils::Random::RandomInt(min, max); }  // :174
+    // MLPnPsolver (ref:src/MLPnPsolver.cpp:109): the Frame's own camera model
+    static void unproject(const Frame &F, float u, float v, float ray[3])
+    {
+        const cv::Point3f r = F.mpCamera->unproject(cv::Point2f(u, v));
+        ray[0] = r.x; ray[1] = r.y; ray[2] = r.z;
+    }
     // TwoViewReconstruction (ref:src/TwoViewReconstruction.cc:96)
     static void seed_rand_once(int seed) { DUtils::Random::SeedRandOnce(seed); }
     // KeyFrameDatabase: the vocabulary on the device, set by System right after it loads ORBvoc

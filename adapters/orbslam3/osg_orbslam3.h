@@ -49,6 +49,8 @@
 #include "osg_dbow.h"
 // the replay of Sim3Solver's sequential rule, shared with the library's selection launch
 #include "../../orb_slam3_comments_ghr_amd/csrc/sim3ransac_select.h"
+// the replay of MLPnPsolver's sequential rule and SetRansacParameters, likewise
+#include "../../orb_slam3_comments_ghr_amd/csrc/mlpnp_select.h"
 // step 3 of the KeyFrameDatabase detectors (groups, sort, choice of candidates), shared with the library
 #include "../../orb_slam3_comments_ghr_amd/csrc/kfdb_select.h"
 
@@ -2628,6 +2630,175 @@ private:
     std::vector<float> sim3;
     std::vector<uint8_t> inlier;
     float mBestT12[16], mBestRotation[9], mBestTranslation[3], mBestScale = 1.f;
+};
+
+// ------------------------------------------------------------------------------- MLPnPsolver
+// MLPnPsolver (ref:include/MLPnPsolver.h, ref:src/MLPnPsolver.cpp) with the reference's public surface.  Hooks
+// (beside camera, mat4 and random_int above):
+//   static void H::unproject(const FrameT &F, float u, float v, float ray[3])   F.mpCamera->unproject(kp.pt)
+//   static void H::mp_world_pos(MapPointT *p, float x[3])                         pMP->GetWorldPos()
+//
+// MLPnPGather is the constructor's slot filter (:68-133) as plain host code: a slot is kept when its MapPoint
+// is non-null, not bad, and i < mvKeysUn.size().  Kept per match: kp.pt, mvLevelSigma2[octave], the bearing
+// unproject(kp.pt) divided by its z in float (not normalised to unit length), the world point, the slot.
+template <class H, class FrameT, class MapPointT>
+struct MLPnPGather {
+    std::vector<float> bearing, p3dw, p2d, sigma2;
+    std::vector<size_t> mvKeyPointIndices;
+    size_t n_slots = 0;
+    osg_camera cam{};
+    void assign(const FrameT &F, const std::vector<MapPointT *> &vpMapPointMatches)
+    {
+        n_slots = vpMapPointMatches.size();
+        for (size_t i = 0, iend = vpMapPointMatches.size(); i < iend; i++) {
+            MapPointT *pMP = vpMapPointMatches[i];
+            if (!pMP) continue;
+            if (pMP->isBad()) continue;
+            if (i >= F.mvKeysUn.size()) continue;
+            const auto &kp = F.mvKeysUn[i];
+            p2d.push_back(kp.pt.x);
+            p2d.push_back(kp.pt.y);
+            sigma2.push_back(F.mvLevelSigma2[kp.octave]);
+            float br[3];
+            H::unproject(F, kp.pt.x, kp.pt.y, br);
+            const float z = br[2];
+            for (int k = 0; k < 3; k++) bearing.push_back(br[k] / z);  // cv_br /= cv_br.z
+            float x[3];
+            H::mp_world_pos(pMP, x);
+            for (int k = 0; k < 3; k++) p3dw.push_back(x[k]);
+            mvKeyPointIndices.push_back(i);
+        }
+        H::camera(F, false, cam);
+    }
+};
+
+// iterate(nIterations) consumes max(mRansacMaxIts - mnIterations, nIterations) hypotheses unless one of them
+// returns early (the reference's loop condition is an OR): the call draws exactly that many sample sets
+// through H::random_int in the reference's order, evaluates them in one osg_mlpnp_ransac call and replays the
+// window with osg_mlpnp_replay (csrc/mlpnp_select.h), mnIterations, mnBestInliers and the best hypothesis
+// carried from call to call.  The reference draws lazily and stops at the hypothesis that returns: the sets
+// drawn past it are the one observable difference (the process-wide rand() stream is further along).  On an
+// ABI error the solver reports bNoMore and false.
+template <class H, class FrameT, class MapPointT>
+class MLPnPsolver {
+public:
+    using Matrix4f = typename H::Matrix4f;
+
+    MLPnPsolver(const FrameT &F, const std::vector<MapPointT *> &vpMapPointMatches)
+    {
+        g.assign(F, vpMapPointMatches);
+        const float eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+        std::memcpy(mBestTcw, eye, sizeof eye);
+        SetRansacParameters();
+    }
+
+    void SetRansacParameters(double probability = 0.99, int minInliers = 8, int maxIterations = 300, int minSet = 6,
+                             float epsilon = 0.4, float th2 = 5.991)
+    {
+        N = (int)g.mvKeyPointIndices.size();
+        int32_t a = 0, b = 0;
+        osg_mlpnp_parameters(probability, minInliers, maxIterations, minSet, epsilon, N, &a, &b);
+        mRansacMinInliers = a;
+        mRansacMaxIts = b;
+        mRansacMinSet = minSet;
+        max_err.resize(g.sigma2.size());
+        for (size_t i = 0; i < g.sigma2.size(); i++) max_err[i] = g.sigma2[i] * th2;  // :353
+    }
+
+    bool iterate(int nIterations, bool &bNoMore, std::vector<bool> &vbInliers, int &nInliers, Matrix4f &Tout)
+    {
+        const float eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+        Tout = H::mat4(eye);
+        bNoMore = false;
+        vbInliers.clear();
+        nInliers = 0;
+        if (N < mRansacMinInliers) {
+            bNoMore = true;
+            return false;
+        }
+        const int len = osg_mlpnp_window_length(mnIterations, mRansacMaxIts, nIterations);
+        if (len < 1) return false;  // mnIterations >= mRansacMaxIts and nIterations <= 0: the loop does not run
+        if (mRansacMinSet != 6 || N < 6 || !evaluate(len)) {  // the library solves on sets of six
+            bNoMore = true;
+            return false;
+        }
+        const osg_mlpnp_window w = osg_mlpnp_replay(counts.data(), mRansacMinInliers, 0, len, mnBestInliers, -1);
+        mnIterations += w.n_iterations;
+        if (w.best_hyp >= 0) {  // a new best in this window: the hypothesis the ABI call returned
+            mnBestInliers = w.n_best;
+            mvbBestInliers = inlier;
+            std::memcpy(mBestTcw, Tcw, sizeof Tcw);
+        }
+        if (w.converged) {  // Refine() re-tests the current hypothesis: its own count, flags and pose
+            nInliers = counts[w.hyp];
+            vbInliers = std::vector<bool>(g.n_slots, false);
+            for (int i = 0; i < N; i++)
+                if (inlier[i]) vbInliers[g.mvKeyPointIndices[i]] = true;
+            Tout = H::mat4(Tcw);
+            return true;
+        }
+        bNoMore = true;  // the loop leaves mnIterations >= mRansacMaxIts behind
+        if (mnBestInliers >= mRansacMinInliers) {
+            nInliers = mnBestInliers;
+            vbInliers = std::vector<bool>(g.n_slots, false);
+            for (int i = 0; i < N; i++)
+                if (mvbBestInliers[i]) vbInliers[g.mvKeyPointIndices[i]] = true;
+            Tout = H::mat4(mBestTcw);
+            return true;
+        }
+        return false;
+    }
+
+    // state of the reference's members, for the tests
+    int iterations() const { return mnIterations; }
+    int best_inliers() const { return mnBestInliers; }
+    int max_iterations() const { return mRansacMaxIts; }
+    int min_inliers() const { return mRansacMinInliers; }
+    const std::vector<float> &max_errors() const { return max_err; }
+    const MLPnPGather<H, FrameT, MapPointT> &gather() const { return g; }
+
+private:
+    bool evaluate(int len)
+    {
+        samples.resize(6 * (size_t)len);
+        std::vector<size_t> vAllIndices(N), vAvailableIndices;
+        for (int i = 0; i < N; i++) vAllIndices[i] = (size_t)i;
+        for (int it = 0; it < len; it++) {  // :177-202
+            vAvailableIndices = vAllIndices;
+            for (short i = 0; i < 6; ++i) {
+                const int randi = H::random_int(0, (int)vAvailableIndices.size() - 1);
+                samples[6 * (size_t)it + i] = (int32_t)vAvailableIndices[randi];
+                vAvailableIndices[randi] = vAvailableIndices.back();
+                vAvailableIndices.pop_back();
+            }
+        }
+        counts.assign(len, 0);
+        inlier.assign(N, 0);
+        osg_mlpnp_problem p{};
+        p.n = N;
+        p.bearing = g.bearing.data();
+        p.p3dw = g.p3dw.data();
+        p.p2d = g.p2d.data();
+        p.max_err = max_err.data();
+        p.cam = g.cam;
+        p.min_inliers = mRansacMinInliers;
+        p.n_hyp = len;
+        p.samples = samples.data();
+        osg_mlpnp_result r{};
+        r.inlier = inlier.data();
+        r.hyp_inliers = counts.data();
+        osg_ctx *ctx = thread_ctx();
+        const bool ok = call(ctx, "osg_mlpnp_ransac", [&] { return osg_mlpnp_ransac(ctx, &p, &r); }) >= 0;
+        std::memcpy(Tcw, r.Tcw, sizeof Tcw);
+        return ok;
+    }
+
+    MLPnPGather<H, FrameT, MapPointT> g;
+    int N = 0, mnIterations = 0, mnBestInliers = 0, mRansacMinInliers = 8, mRansacMaxIts = 300, mRansacMinSet = 6;
+    std::vector<int32_t> samples, counts;
+    std::vector<float> max_err;
+    std::vector<uint8_t> inlier, mvbBestInliers;
+    float Tcw[16], mBestTcw[16];
 };
 
 // ------------------------------------------------------------------------- TwoViewReconstruction

@@ -9,6 +9,7 @@
  *                                    ref:src/Optimizer.cc:2850-3237)
  *   osg_optimize_sim3[_batch]      ← Optimizer::OptimizeSim3                   ref:src/Optimizer.cc:4213-4512
  *   osg_sim3_ransac[_batch]        ← Sim3Solver::find / iterate                 ref:src/Sim3Solver.cc:146-433
+ *   osg_mlpnp_ransac[_batch]       ← MLPnPsolver::iterate                       ref:src/MLPnPsolver.cpp:145-1160
  *
  * The caller (the ORB-SLAM3 side adapter) gathers the graph exactly as the
  * reference builds it — the same vertices, the same edges in the same insertion order, the same
@@ -169,6 +170,60 @@ int osg_sim3_ransac_batch(struct osg_ctx *ctx, const osg_sim3_ransac_problem *p,
  * min_inliers == n.  A quotient that is not finite or exceeds max_its gives max_its; n < min_inliers
  * (the solver never iterates) gives 1. */
 int32_t osg_sim3_ransac_iterations(double prob, int32_t min_inliers, int32_t n, int32_t max_its);
+
+/* ---- MLPnPsolver ---------------------------------------------------------------------------
+ * MLPnPsolver's RANSAC as Tracking::Relocalization runs it (ref:src/MLPnPsolver.cpp:145-1160): every
+ * hypothesis — computePose on six sampled matches (null-space linear solve, planar branch, sign choice,
+ * five-step Gauss-Newton, all in double), then the float reprojection test of every match — is evaluated
+ * in parallel, and the reference's sequential rule is replayed on the integer counts: the first
+ * hypothesis in draw order with more than min_inliers inliers ends the search and returns its own pose
+ * (Refine() re-tests the current hypothesis); otherwise the first one that attains the
+ * largest count >= min_inliers is the best.  The caller applies the constructor's slot filter
+ * (ref:src/MLPnPsolver.cpp:68-133) and draws the sample sets. */
+typedef struct osg_mlpnp_problem {
+    int32_t n;                /* N: kept matches */
+    const float *bearing;     /* 3 per match: unproject(kp.pt) / z, as the constructor leaves it */
+    const float *p3dw;        /* 3 per match: mvP3Dw */
+    const float *p2d;         /* 2 per match: mvP2D */
+    const float *max_err;     /* mvMaxError: sigma2 * th2, float */
+    osg_camera cam;           /* F.mpCamera (type and p[] are read) */
+    int32_t min_inliers;      /* mRansacMinInliers */
+    int32_t n_hyp;            /* H: the iterations one iterate() consumes (>= 1) */
+    const int32_t *samples;   /* 6 per hypothesis, in draw order: distinct indices into [0, n) */
+} osg_mlpnp_problem;
+
+typedef struct osg_mlpnp_result {
+    int32_t converged;        /* a hypothesis with more than min_inliers inliers ended the search */
+    int32_t hyp;              /* that hypothesis, else the first one that attains the largest count
+                                 >= min_inliers; -1 when there is none or nothing was evaluated
+                                 (n < min_inliers or n == 0): identity and zeros out */
+    int32_t n_iterations;     /* mnIterations after iterate() */
+    int32_t n_inliers;        /* nInliers: the count of hyp (0 when hyp is -1) */
+    int32_t n_best;           /* mnBestInliers */
+    float Tcw[16];            /* [R | t; 0 0 0 1] row-major, R and t rounded from double */
+    double R[9], t[3];        /* of hyp, R row-major */
+    uint8_t *inlier;          /* n flags of hyp */
+    int32_t *hyp_inliers;     /* optional (NULL: not written), n_hyp: the count of every hypothesis */
+    double *hyp_pose;         /* optional, 12 per hypothesis: R[9] t[3] */
+    int32_t *hyp_info;        /* optional, 3 per hypothesis: planar flag, Gauss-Newton linear solves,
+                                 how it ended (0 five iterations, 1 converged, 2 break) */
+} osg_mlpnp_result;
+
+/* Returns n_inliers or a negative OSG_E_* code (sample indices outside [0, n) or repeated within a
+ * set: OSG_E_INVALID, before anything is uploaded). */
+int osg_mlpnp_ransac(struct osg_ctx *ctx, const osg_mlpnp_problem *p, osg_mlpnp_result *r);
+/* n independent problems in one pair of launches (every relocalisation candidate of a frame).  Returns
+ * the number of problems with hyp >= 0 or a negative OSG_E_* code.  No reference counterpart. */
+int osg_mlpnp_ransac_batch(struct osg_ctx *ctx, const osg_mlpnp_problem *p, int32_t n, osg_mlpnp_result *r);
+/* The host check that both calls make before anything is uploaded: 0 when every sample set holds six distinct
+ * indices into [0, n), else OSG_E_INVALID.  Needs no context. */
+int osg_mlpnp_check_samples(const osg_mlpnp_problem *p);
+/* MLPnPsolver::SetRansacParameters (ref:src/MLPnPsolver.cpp:314-354), host only: nMin = int(n * epsilon)
+ * in float raised to min_inliers and min_set, epsilon raised to float(nMin) / n,
+ * ceil(log(1 - prob) / log(1 - epsilon^3)) clamped to [1, max_its], 1 when nMin == n.  A quotient that
+ * is not finite or not below max_its gives max_its. */
+void osg_mlpnp_ransac_parameters(double prob, int32_t min_inliers, int32_t max_its, int32_t min_set, float epsilon,
+                                 int32_t n, int32_t *min_inliers_out, int32_t *max_its_out);
 
 /* ---- OptimizeEssentialGraph -----------------------------------------------------------------
  * The g2o part of Optimizer::OptimizeEssentialGraph (ref:src/Optimizer.cc:4527-4858): a pose graph of

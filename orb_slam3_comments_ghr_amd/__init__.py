@@ -186,4 +186,8 @@ def __getattr__(name):
     if name in ("TwoViewReconstruction", "draw_sets"):
         from . import twoview
         return getattr(twoview, name)
+    # the relocalisation PnP solver, likewise
+    if name in ("MLPnPsolver", "MlpnpProblem"):
+        from . import mlpnpsolver
+        return getattr(mlpnpsolver, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -180,6 +180,21 @@ class OsgSim3RansacResult(C.Structure):
     ]
 
 
+class OsgMlpnpProblem(C.Structure):
+    _fields_ = [
+        ("n", i32), ("bearing", P), ("p3dw", P), ("p2d", P), ("max_err", P), ("cam", OsgCamera),
+        ("min_inliers", i32), ("n_hyp", i32), ("samples", P),
+    ]
+
+
+class OsgMlpnpResult(C.Structure):
+    _fields_ = [
+        ("converged", i32), ("hyp", i32), ("n_iterations", i32), ("n_inliers", i32), ("n_best", i32),
+        ("Tcw", f32 * 16), ("R", f64 * 9), ("t", f64 * 3), ("inlier", P), ("hyp_inliers", P), ("hyp_pose", P),
+        ("hyp_info", P),
+    ]
+
+
 class OsgTwoViewProblem(C.Structure):
     _fields_ = [
         ("K", f32 * 4), ("sigma", f32), ("n_hyp", i32), ("n", i32), ("kp1", P), ("kp2", P), ("n_keys1", i32),
@@ -280,6 +295,7 @@ EXPORTS = [
     "osg_local_bundle_adjustment", "osg_local_bundle_adjustment_batch", "osg_bundle_adjustment",
     "osg_lba_kernel_times", "osg_optimize_sim3", "osg_optimize_sim3_batch",
     "osg_sim3_ransac", "osg_sim3_ransac_batch", "osg_sim3_ransac_iterations",
+    "osg_mlpnp_ransac", "osg_mlpnp_ransac_batch", "osg_mlpnp_ransac_parameters", "osg_mlpnp_check_samples",
     "osg_optimize_essential_graph", "osg_essgraph_correct_points", "osg_essgraph_kernel_times",
     "osg_vocabulary_create", "osg_vocabulary_load_text", "osg_vocabulary_destroy", "osg_vocabulary_info",
     "osg_vocabulary_transform", "osg_vocabulary_transform_batch",
@@ -346,6 +362,11 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.osg_sim3_ransac.argtypes = [vp, C.POINTER(OsgSim3RansacProblem), C.POINTER(OsgSim3RansacResult)]
     lib.osg_sim3_ransac_batch.argtypes = [vp, C.POINTER(OsgSim3RansacProblem), i32, C.POINTER(OsgSim3RansacResult)]
     lib.osg_sim3_ransac_iterations.argtypes = [C.c_double, i32, i32, i32]
+    lib.osg_mlpnp_ransac.argtypes = [vp, C.POINTER(OsgMlpnpProblem), C.POINTER(OsgMlpnpResult)]
+    lib.osg_mlpnp_ransac_batch.argtypes = [vp, C.POINTER(OsgMlpnpProblem), i32, C.POINTER(OsgMlpnpResult)]
+    lib.osg_mlpnp_ransac_parameters.argtypes = [C.c_double, i32, i32, i32, C.c_float, i32, C.POINTER(i32), C.POINTER(i32)]
+    lib.osg_mlpnp_ransac_parameters.restype = None
+    lib.osg_mlpnp_check_samples.argtypes = [C.POINTER(OsgMlpnpProblem)]
     lib.osg_two_view_reconstruct.argtypes = [vp, C.POINTER(OsgTwoViewProblem), C.POINTER(OsgTwoViewResult)]
     lib.osg_two_view_reconstruct_batch.argtypes = [vp, C.POINTER(OsgTwoViewProblem), i32, C.POINTER(OsgTwoViewResult)]
     lib.osg_two_view_kernel_times.argtypes = [vp, i32, vp]

@@ -98,3 +98,75 @@ def two_view_scene(rng, n=100, scene="general", noise_px=0.5, outlier_frac=0.0, 
     m12[slot1] = slot2
     sets = seeded_sets(n, n_hyp, int(rng.integers(1 << 30)))
     return TwoViewProblem(keys1, keys2, m12, sets, K=tuple(K), truth=(R, t, out))
+
+
+def reloc_scene(rng, n=200, outlier_frac=0.3, noise_px=0.5, planar=False, kb8=False, behind_frac=0.0, n_levels=8):
+    """One relocalisation candidate as Tracking::Relocalization hands it to MLPnPsolver: a camera, its pose
+    Tcw, ``n`` world MapPoints (float32) and the keypoints they were matched to, with octaves drawn as the
+    pyramid populates them.  ``outlier_frac`` of the matches are wrong associations: the keypoint belongs to
+    another, unrelated point.  ``planar`` puts every MapPoint on the world plane z == 0 exactly;  ``kb8`` uses
+    a KannalaBrandt8 camera with rays out to ~70 degrees;  ``behind_frac`` of the MapPoints are mirrored to
+    the back of the camera (MLPnPsolver has no depth test).
+    -> dict(cam, R, t, Xw, kp, octave, outlier)."""
+    from . import optimizer as O
+
+    cam = O.kb8_camera() if kb8 else O.pinhole_camera()
+    n = int(n)
+
+    def rays(m):
+        if kb8:
+            th = rng.uniform(0.05, 1.25, m)
+            ps = rng.uniform(-np.pi, np.pi, m)
+            return np.stack([np.tan(th) * np.cos(ps), np.tan(th) * np.sin(ps), np.ones(m)], 1)
+        u = rng.uniform(40, EUROC_W - 40, m)
+        v = rng.uniform(40, EUROC_H - 40, m)
+        return np.stack([(u - EUROC_CX) / EUROC_FX, (v - EUROC_CY) / EUROC_FY, np.ones(m)], 1)
+
+    R = O.small_rotation(rng, 25.0)
+    t = rng.normal(0, 0.5, 3)
+    if planar:
+        # look at the plane z = 0 from 3 .. 5 m up, the optical axis 50 .. 58 degrees off the plane's normal (the
+        # reference takes the planar translation scale from rows of the rotation estimate, which fails for a
+        # camera that faces the plane squarely)
+        C = np.array([rng.normal(0, 0.3), rng.normal(0, 0.3), rng.uniform(3.0, 5.0)])
+        tilt = np.deg2rad(rng.uniform(50.0, 58.0))
+        az = rng.uniform(-np.pi, np.pi)
+        target = C + C[2] * np.array([np.tan(tilt) * np.cos(az), np.tan(tilt) * np.sin(az), -1.0])
+        R, t = O.look_at(C, target, up=(0, 0, -1))
+        R = O.small_rotation(rng, 3.0) @ R
+        t = -R @ C
+
+    def cloud(m):
+        d = rays(m)
+        if planar:
+            # intersect the rays with the world plane z = 0
+            dw = d @ R  # R^T d
+            C = -R.T @ t
+            lam = -C[2] / dw[:, 2]
+            Xc = d * lam[:, None]
+        else:
+            Xc = d * rng.uniform(2.0, 8.0, m)[:, None]
+        return Xc
+
+    Xc = cloud(n)
+    Xw = ((Xc - t) @ R).astype(np.float32)  # R^T (Xc - t)
+    if planar:
+        Xw[:, 2] = 0.0
+    Xc = Xw.astype(np.float64) @ R.T + t
+    def proj(X):
+        if kb8:
+            return np.stack(O.kb8_project(cam, X), 1)
+        return np.stack([EUROC_FX * X[:, 0] / X[:, 2] + EUROC_CX, EUROC_FY * X[:, 1] / X[:, 2] + EUROC_CY], 1)
+
+    pr = proj(Xc)
+    lev_p = np.array([1.2 ** -i for i in range(n_levels)])
+    lev_p /= lev_p.sum()
+    octave = rng.choice(n_levels, n, p=lev_p).astype(np.int32)
+    kp = pr + rng.normal(0, noise_px, (n, 2)) * (1.2 ** octave)[:, None]
+    out = rng.random(n) < outlier_frac
+    kp = np.where(out[:, None], proj(cloud(n)), kp).astype(np.float32)
+    if behind_frac > 0:
+        back = rng.random(n) < behind_frac
+        C = -R.T @ t
+        Xw = np.where(back[:, None], (2 * C - Xw.astype(np.float64)), Xw).astype(np.float32)
+    return dict(cam=cam, R=R, t=t, Xw=Xw, kp=kp, octave=octave, outlier=out)
