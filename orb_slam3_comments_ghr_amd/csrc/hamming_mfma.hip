@@ -44,14 +44,14 @@
 #include <cstdlib>
 
 #include "osg_internal.h"
+#include "top2_key.h"
 
 namespace {
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int MF_SHIFT = 13;                       // key = (H - |q|) << 13 | row
-constexpr int MF_MAX_ROWS = 1 << MF_SHIFT;         // rows per problem on this path
+// MF_SHIFT (key = (H - |q|) << 13 | row) and MF_MAX_ROWS (rows per problem on this path): top2_key.h
 constexpr int MF_PAD = 1 << 30;                    // rows past nt: above every real key
 constexpr int MF_RS = 272;                         // LDS row stride: 256 B of signed bytes + 16 B pad
 
@@ -364,7 +364,7 @@ constexpr int MX_RS = 144;                  // LDS row stride: 128 B of nibbles 
 constexpr int MX_SCALE_TRAIN = 127 + 12;    // E8M0 2^12 on the train operand
 constexpr int MX_SCALE_ONE = 127;           // E8M0 1.0
 constexpr float MX_BIAS = 10485760.0f;      // 2^23 + 2^21: keys of [-2^21, 2^21 + 32) land in [2^23, 2^24)
-constexpr int MX_KEY0 = 0x4B000000 + (1 << 21);   // bit pattern of MX_BIAS: bits = key + MX_KEY0
+// MX_KEY0, the bit pattern of MX_BIAS (bits = key + MX_KEY0): top2_key.h
 constexpr float MX_PAD = 1073741824.0f;     // rows past nt: above every real key (2^30)
 
 typedef int i32x8 __attribute__((ext_vector_type(8)));
@@ -888,6 +888,9 @@ __global__ __launch_bounds__(NW * 64) void k_top2_fp4p(const uint32_t *__restric
 // query tile 1 on row tile t - 1 (acc1), then the 4 MFMAs of query tile 1 (into acc1) beside the updates of
 // acc0.  Both chains share a[0..3]; a[s] is refilled with row tile t + 1's granule right after query tile
 // 1's K-step s has consumed it, 4 MFMAs before its next use.  Registers: bq 32 + a 16 + acc 32 + crow 16.
+// Within a chain the MFMA of a K-step issues first and the other tile's updates behind it, none behind K-step 0
+// and 3 / 3 / 2 pairs behind K-steps 1-3 (pushk), so that no update reads an accumulator right after the MFMA
+// that wrote it.  Only the first kept key is rebased from tile to tile; the second never is (top2_key.h).
 // A wave whose second tile starts at or past nq runs one tile per row tile, unpipelined; one whose first
 // tile does only takes part in the loads, stores and barriers.
 template <int NW, int CR>
@@ -978,15 +981,26 @@ __global__ __launch_bounds__(NW * 64) void k_top2_fp4q2(const uint32_t *__restri
     auto mfma = [&](const i32x8 &a, const i32x8 &bb, const f32x16 &c) {
         return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, bb, c, 4, 4, 0, MX_SCALE_TRAIN, 0, MX_SCALE_ONE);
     };
-    // key pairs 2 s and 2 s + 1 of query tile j's accumulator; after the last pair the kept keys move to the
-    // next row tile's base
+    // key pairs 2 s and 2 s + 1 of query tile j's accumulator; after the last pair the first key moves to the
+    // next row tile's base.  The second key is never rebased (only its distance is output; top2_key.h has the
+    // argument that its order and its decode do not need it): one VALU op less per row tile and query tile
     auto push = [&](int j, const f32x16 &acc, int s) {
         key_push2f(k1[j], k2[j], __float_as_int(acc[2 * s]), __float_as_int(acc[2 * s + 1]));
         key_push2f(k1[j], k2[j], __float_as_int(acc[8 + 2 * s]), __float_as_int(acc[9 + 2 * s]));
-        if (s == 3) {
-            k1[j] -= 32;
-            k2[j] -= 32;
+        if (s == 3) k1[j] -= TOP2_TILE_ROWS;
+    };
+    // the part of push() that the pipelined block runs behind K-step s of the other query tile's chain: nothing
+    // at step 0, whose MFMA issues right behind the chain these keys come from (an update there reads the
+    // accumulator one instruction after its last MFMA and waits out the whole MFMA -> VALU hazard), then pairs
+    // 0-2, 3-5 and 6-7 with the rebase.  The order of the pairs does not change the two smallest keys.
+    auto pushk = [&](int j, const f32x16 &acc, int s) {
+        const int lo = s == 0 ? 0 : 3 * (s - 1), hi = s == 0 ? 0 : (s == 3 ? 8 : 3 * s);
+#pragma unroll
+        for (int p = lo; p < hi; p++) {
+            const int e = (p & 1) * 8 + 2 * (p >> 1);
+            key_push2f(k1[j], k2[j], __float_as_int(acc[e]), __float_as_int(acc[e + 1]));
         }
+        if (s == 3) k1[j] -= TOP2_TILE_ROWS;
     };
     // one row tile, unpipelined: both chains when the wave has two tiles, then their updates
     auto tile = [&](const unsigned char *tb, const f32x16 &cin) {
@@ -1044,7 +1058,8 @@ __global__ __launch_bounds__(NW * 64) void k_top2_fp4q2(const uint32_t *__restri
                     for (int s = 0; s < 4; s++) {
                         acc1 = mfma(a[s], bq[1][s], s ? acc1 : crow);
                         if (tt + 1 < NTILE) a[s] = frag(sb + (tt + 1) * 32 * MX_RS, s);
-                        push(0, acc0, s);
+                        __builtin_amdgcn_sched_barrier(0);   // the MFMA first: its K-step, not the update, paces the wave
+                        pushk(0, acc0, s);
                         __builtin_amdgcn_sched_barrier(0);
                     }
                     if (tt + 1 == NTILE) break;
@@ -1052,7 +1067,8 @@ __global__ __launch_bounds__(NW * 64) void k_top2_fp4q2(const uint32_t *__restri
 #pragma unroll
                     for (int s = 0; s < 4; s++) {
                         acc0 = mfma(a[s], bq[0][s], s ? acc0 : crow);
-                        push(1, acc1, s);
+                        __builtin_amdgcn_sched_barrier(0);
+                        pushk(1, acc1, s);
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
@@ -1082,15 +1098,16 @@ __global__ __launch_bounds__(NW * 64) void k_top2_fp4q2(const uint32_t *__restri
     for (int j = 0; j < 2; j++) {
         int m1 = k1[j], m2 = k2[j];
         const int a1 = __shfl_xor(m1, 32), a2 = __shfl_xor(m2, 32);
-        key_merge(m1, m2, a1, a2);
+        // key_merge with the first keys' last rebase taken back where one of them becomes a second key
+        m2 = min(min(m2, a2), max(m1, a1) + TOP2_K2_LAST_REBASE);
+        m1 = min(m1, a1);
         const int q = qw0 + 32 * j + lane_end;
         if (lane_end < 32 && q < nq) {
             const uint4 lo = *(const uint4 *)(qf + (size_t)q * 8), hi = *(const uint4 *)(qf + (size_t)q * 8 + 4);
             const int pc = __popc(lo.x) + __popc(lo.y) + __popc(lo.z) + __popc(lo.w) + __popc(hi.x) + __popc(hi.y) +
                            __popc(hi.z) + __popc(hi.w);
-            const int t1 = m1 - MX_KEY0 + base, t2 = m2 - MX_KEY0 + base;
-            const int d1 = (t1 >> MF_SHIFT) + pc, d2 = (t2 >> MF_SHIFT) + pc;
-            of[3 * q + 0] = d1 < 256 ? (t1 & (MF_MAX_ROWS - 1)) : -1;
+            const int d1 = top2_k1_dist(m1, base) + pc, d2 = top2_k2_dist(m2) + pc;
+            of[3 * q + 0] = d1 < 256 ? top2_k1_row(m1, base) : -1;
             of[3 * q + 1] = min(d1, 256);
             of[3 * q + 2] = min(d2, 256);
         }
