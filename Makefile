@@ -36,7 +36,7 @@ $(OBJDIR)/runtime.o: $(CSRC)/runtime.hip $(HDRS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 $(OBJDIR)/hamming.o: $(CSRC)/hamming.hip $(HDRS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
-$(OBJDIR)/hamming_mfma.o: $(CSRC)/hamming_mfma.hip $(HDRS) $(CSRC)/top2_key.h | $(OBJDIR)
+$(OBJDIR)/hamming_mfma.o: $(CSRC)/hamming_mfma.hip $(HDRS) $(CSRC)/top2_key.h $(CSRC)/top2_ring.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 $(OBJDIR)/match.o: $(CSRC)/match.hip $(HDRS) $(CSRC)/match_common.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@

@@ -45,6 +45,7 @@
 
 #include "osg_internal.h"
 #include "top2_key.h"
+#include "top2_ring.h"
 
 namespace {
 
@@ -377,6 +378,16 @@ __device__ __forceinline__ uint32_t spread_nib(uint32_t x)
     x = (x | (x << 12)) & 0x000F000Fu;
     x = (x | (x << 6)) & 0x03030303u;
     return (x | (x << 3)) & 0x11111111u;
+}
+
+// 8 bits -> the sign bits of 8 nibbles without a 32-bit multiply: three copies of the byte 9 bits apart (a 24-bit
+// multiply) and a fourth at bit 27 put every bit of it once on a bit 4 n + 3: nibbles 0-7 take bits 3, 7, 2, 6, 1, 5,
+// 0, 4.  k_top2_fp4q2 uses this nibble order for both operands (a K permutation applied to both alike).
+__device__ __forceinline__ uint32_t spread_nib9(uint32_t x)   // x < 256
+{
+    uint32_t lo3 = x * 0x40201u;   // v_mul_u32_u24; the empty asm keeps the compiler from folding the fourth copy
+    asm("" : "+v"(lo3));           // into it as one 32-bit multiply by 0x08040201
+    return (lo3 | (x << 27)) & 0x88888888u;
 }
 
 template <int NW, int QT, int CR, int PIPE>
@@ -881,8 +892,9 @@ __global__ __launch_bounds__(NW * 64) void k_top2_fp4p(const uint32_t *__restric
 // Two 32-query tiles per wave (the default, also OSG_TOP2_MFMA_SHAPE=14): NW waves x 64 queries per workgroup,
 // so at 16 waves a 2000-query frame is two workgroups instead of four: half the train-row expansions per frame, half the
 // per-workgroup prologues and tails per CU, and every A fragment read from LDS feeds two MFMAs.  The same
-// keys, MX_* constants, LDS chunk layout and one-chain key_push2f update as k_top2_fp4<.., 3>; the two
-// smallest keys of a set do not depend on the order of the updates, so the output is bit-exact.
+// keys, MX_* constants, 144-byte LDS rows and one-chain key_push2f update as k_top2_fp4<.., 3>; the two
+// smallest keys of a set do not depend on the order of the updates, nor a dot product on the order of its
+// nibbles, so the output is bit-exact.
 // The pipeline runs across the two query tiles instead of across row tiles, which needs no second
 // accumulator pair: for row tile t the 4 MFMAs of query tile 0 (into acc0) issue beside the key updates of
 // query tile 1 on row tile t - 1 (acc1), then the 4 MFMAs of query tile 1 (into acc1) beside the updates of
@@ -891,8 +903,18 @@ __global__ __launch_bounds__(NW * 64) void k_top2_fp4p(const uint32_t *__restric
 // Within a chain the MFMA of a K-step issues first and the other tile's updates behind it, none behind K-step 0
 // and 3 / 3 / 2 pairs behind K-steps 1-3 (pushk), so that no update reads an accumulator right after the MFMA
 // that wrote it.  Only the first kept key is rebased from tile to tile; the second never is (top2_key.h).
-// A wave whose second tile starts at or past nq runs one tile per row tile, unpipelined; one whose first
-// tile does only takes part in the loads, stores and barriers.
+// The expanded chunks live in a ring of three LDS slots (top2_ring.h): chunk c in slot c % 3, chunks 0 and 1
+// stored by the prologue, and behind the one barrier at the top of block c every thread expands chunk c + 2 into
+// the slot chunk c - 1 has left and asks for chunk c + 3's packed words.  The barrier only guards the reuse of a
+// slot, so the pipeline runs through all full chunks without a drain: the last row tile of a chunk prefetches the
+// next slot's first fragments, and query tile 0's chain on them issues in front of the barrier beside query tile
+// 1's last updates of the chunk.  The chain's first step runs beside updates on pad keys (every step has one
+// form; a separate opening made the allocator spill), and query tile 1's updates close alone once, after the
+// last full chunk.  The partial last chunk, the row tile that nt cuts, and a wave whose second tile starts at or
+// past nq run one row tile at a time, unpipelined; a wave whose first tile starts at or past nq only takes part
+// in the loads, stores and barriers.  Every wave executes the same 2 + ceil(nt / CR) barriers, in wave-uniform
+// control flow that depends on nt alone.  The byte table sits at LDS address 0, the ring behind it; the nibble
+// order of both operands is spread_nib9's.
 template <int NW, int CR>
 __global__ __launch_bounds__(NW * 64) void k_top2_fp4q2(const uint32_t *__restrict__ query, int nq,
                                                          const uint32_t *__restrict__ train, int nt,
@@ -904,8 +926,11 @@ __global__ __launch_bounds__(NW * 64) void k_top2_fp4q2(const uint32_t *__restri
     constexpr int TPR = 32 / BPT;            // threads per row
     constexpr int NTILE = CR / 32;           // 32-row tiles per chunk
     static_assert(CR * 32 % NT == 0 && BPT % 8 == 0 && TPR >= 1, "chunk / workgroup shape");
-    __shared__ __attribute__((aligned(16))) unsigned char s_buf[2 * CR * MX_RS];   // [2][CR rows][144 B]
-    __shared__ uint32_t s_lut[256];          // train byte -> 8 nibbles (bit y -> nibble y: 0xC = -2 / 0)
+    constexpr int SLOTB = CR * MX_RS;        // bytes per ring slot
+    // the table first, at LDS address 0: its reads then need no base register
+    __shared__ __attribute__((aligned(16))) unsigned char s_mem[1024 + TOP2_RING_SLOTS * SLOTB];
+    uint32_t *const s_lut = (uint32_t *)s_mem;   // train byte -> 8 nibbles (spread_nib9's order: 0xC = -2 / 0)
+    unsigned char *const s_buf = s_mem + 1024;   // [3][CR rows][144 B]
 
     const int t = threadIdx.x, lane = t & 63;
     const int w = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -916,11 +941,32 @@ __global__ __launch_bounds__(NW * 64) void k_top2_fp4q2(const uint32_t *__restri
     const uint32_t *tf = train + (size_t)b * nt * 8;
     int32_t *of = out + (size_t)b * nq * 3;
 
-    for (int e = t; e < 256; e += NT) s_lut[e] = spread_nib((uint32_t)e) * 0xCu;
+    for (int e = t; e < 256; e += NT) {
+        const uint32_t x = spread_nib9((uint32_t)e);
+        s_lut[e] = x | (x >> 1);
+    }
 
     const int r = lane & 31, h = lane >> 5;
     const int qw0 = qb * (NW * 64) + w * 64;
     const bool act0 = qw0 < nq, act1 = qw0 + 32 < nq;   // wave-uniform
+
+    // thread t expands words epart * WPT .. of row t / TPR: word offset t * WPT into the chunk's packed rows
+    auto load_chunk = [&](int t, int c0, uint32_t (&pw)[WPT]) {
+        // a 32-bit byte offset from the frame's (wave-uniform) base: nt <= 8192 rows of 32 B, and a few chunks
+        // past them.  A row past nt reads the frame's first bytes instead (nt >= 1); store_chunk zeroes it.  A
+        // select, not a branch, and nothing here waits for the loaded words.
+        const char *src = (const char *)tf + (c0 + t / TPR < nt ? (unsigned)((c0 * 8 + t * WPT) * 4) : 0u);
+#pragma unroll
+        for (int i = 0; i < WPT; i += 2) {
+            const uint2 v = *(const uint2 *)(src + 4 * i);
+            pw[i] = v.x;
+            pw[i + 1] = v.y;
+        }
+    };
+    // chunks 0 and 1 are asked for first, so that they arrive behind the forming of the query fragments
+    uint32_t pw[WPT], p1[WPT];
+    load_chunk(t, 0, pw);
+    load_chunk(t, CR, p1);
 
     i32x8 bq[2][4];
     int k1[2], k2[2];
@@ -928,16 +974,16 @@ __global__ __launch_bounds__(NW * 64) void k_top2_fp4q2(const uint32_t *__restri
     for (int j = 0; j < 2; j++) {
         const int q = min(qw0 + 32 * j + r, nq - 1);
         const uint4 lo = *(const uint4 *)(qf + (size_t)q * 8), hi = *(const uint4 *)(qf + (size_t)q * 8 + 4);
-        const uint32_t wd[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-        int pc = 0;
-#pragma unroll
-        for (int k = 0; k < 8; k++) pc += __popc(wd[k]);
+        const int pc = __popc(lo.x) + __popc(lo.y) + __popc(lo.z) + __popc(lo.w) + __popc(hi.x) + __popc(hi.y) +
+                       __popc(hi.z) + __popc(hi.w);
+        // descriptor word 2 s + h of K-step s: one v_cndmask each (an array indexed by h costs a compare chain)
+        const uint32_t wsel[4] = {h ? lo.y : lo.x, h ? lo.w : lo.z, h ? hi.y : hi.x, h ? hi.w : hi.z};
 #pragma unroll
         for (int s = 0; s < 4; s++) {
-            const uint32_t word = wd[2 * s + h];
+            const uint32_t word = wsel[s];
 #pragma unroll
-            for (int d = 0; d < 4; d++)
-                bq[j][s][d] = (int)(0x22222222u | ((~spread_nib(word >> (8 * d)) & 0x11111111u) << 3));
+            for (int d = 0; d < 4; d++)   // set bit -> nibble 0x2 (+1), clear bit -> 0xA (-1)
+                bq[j][s][d] = (int)(spread_nib9((word >> (8 * d)) & 0xFFu) ^ 0xAAAAAAAAu);
 #pragma unroll
             for (int d = 4; d < 8; d++) bq[j][s][d] = 0;
         }
@@ -946,29 +992,15 @@ __global__ __launch_bounds__(NW * 64) void k_top2_fp4q2(const uint32_t *__restri
     f32x16 crow;
 #pragma unroll
     for (int i = 0; i < 16; i++) crow[i] = MX_BIAS + (float)((i & 3) + 8 * (i >> 2) + 4 * h);
-    const int lbase = r * MX_RS + h * 16;
+    int lbase = r * MX_RS + h * 16;
 
-    // thread t expands words epart * WPT .. of row t / TPR: word offset t * WPT into the chunk's packed rows
-    auto load_chunk = [&](int c0, uint32_t (&pw)[WPT]) {
-        if (c0 + t / TPR < nt) {
-            // a 32-bit byte offset from the frame's (wave-uniform) base: nt <= 8192 rows of 32 B
-            const char *src = (const char *)tf + (unsigned)((c0 * 8 + t * WPT) * 4);
-#pragma unroll
-            for (int i = 0; i < WPT; i += 2) {
-                const uint2 v = *(const uint2 *)(src + 4 * i);
-                pw[i] = v.x;
-                pw[i + 1] = v.y;
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < WPT; i++) pw[i] = 0u;   // expands to zero nibbles: D = C exactly
-        }
-    };
-    auto store_chunk = [&](int buf, const uint32_t (&pw)[WPT]) {
-        unsigned char *dst = s_buf + buf * (CR * MX_RS) + (t / TPR) * MX_RS + (t % TPR) * (16 * WPT);
+    // pw: what load_chunk(c0, pw) gave.  Rows past nt become zero nibbles: D = C exactly.
+    auto store_chunk = [&](int t, int buf, int c0, const uint32_t (&pw)[WPT]) {
+        const bool in = c0 + t / TPR < nt;
+        unsigned char *dst = s_buf + buf * SLOTB + ((t & (NT - 1)) / TPR) * MX_RS + (t % TPR) * (16 * WPT);
 #pragma unroll
         for (int i = 0; i < WPT; i++) {
-            const uint32_t x = pw[i];
+            const uint32_t x = in ? pw[i] : 0u;
             *(i32x4 *)(dst + 16 * i) =
                 i32x4{(int)s_lut[x & 0xFFu], (int)s_lut[(x >> 8) & 0xFFu], (int)s_lut[(x >> 16) & 0xFFu],
                       (int)s_lut[x >> 24]};
@@ -1024,40 +1056,72 @@ __global__ __launch_bounds__(NW * 64) void k_top2_fp4q2(const uint32_t *__restri
         }
     };
 
-    const int nch = (nt + CR - 1) / CR;
-    {
-        uint32_t pw[WPT];
-        load_chunk(0, pw);
-        __syncthreads();   // the table
-        store_chunk(0, pw);
-    }
+    const int nch = top2_ring_chunks(nt, CR), nfc = top2_ring_full_chunks(nt, CR);
+    __syncthreads();   // the table
+    store_chunk(t, top2_ring_slot(0), 0, pw);
+    store_chunk(t, top2_ring_slot(1), CR, p1);
+    load_chunk(t, TOP2_RING_AHEAD * CR, pw);
     __syncthreads();
-    for (int c = 0; c < nch; c++) {
-        const int c0 = c * CR;
-        uint32_t pw[WPT];
-        const bool more = c + 1 < nch;
-        if (more) load_chunk(c0 + CR, pw);
-        if (act0) {
-            const unsigned char *sb = s_buf + (size_t)(c & 1) * CR * MX_RS;
-            const int nfull = min(NTILE, (nt - c0) / 32);
-            if (act1 && nfull == NTILE) {
-                i32x8 a[4];
-                f32x16 acc0, acc1;
+    // the lane id taken again (as volatile asm, or it is hoisted and kept): returns it
+    auto lane_again = [&]() {
+        int ln;
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
+        return ln & 63;
+    };
+    // top of block c, the same for every wave: the barrier (every wave has finished chunk c - 1, and chunk c + 1 is
+    // visible), then chunk c + 2 into the slot chunk c - 1 leaves and the global load of chunk c + 3.  The two
+    // ds_write_b128 are waited for at the next barrier only, a whole block later.
+    // Without a branch (past the last chunk it stores zero rows into the free slot and loads nothing): the block
+    // stays one basic block, so the MFMA chain issued in front of the barrier stays there.
+    // The staging addresses are formed again from the lane id each time: a few VALU beside the MFMAs in flight
+    // instead of registers held through the block.
+    auto seam = [&](int c, int freed) {
+        __syncthreads();
+        const int ln = lane_again(), tv = w * 64 + ln;
+        store_chunk(tv, freed, (c + TOP2_RING_AHEAD) * CR, pw);
+        load_chunk(tv, (c + TOP2_RING_AHEAD + 1) * CR, pw);
+        return ln;
+    };
+    int slot = top2_ring_slot(0), freed = top2_ring_slot(TOP2_RING_SLOTS - 1);
+    if (act1) {
+        // both query tiles: one pipeline over the row tiles of all full chunks, which does not stop at a chunk's
+        // end.  Every step of it has the same form, a chain of one query tile beside the other tile's updates on the
+        // row tile before, so the first chain runs beside updates on an accumulator of pad keys (above every key:
+        // they change neither kept key) whose rebase of the first key is given back beforehand.  Query tile 1's
+        // last updates close alone after the last full chunk.
+        if (nfc > 0) {
+            i32x8 a[4];
+            f32x16 acc0, acc1;
 #pragma unroll
-                for (int s = 0; s < 4; s++) a[s] = frag(sb, s);
-                // row tile 0, query tile 0: no update is pending yet
+            for (int s = 0; s < 4; s++) a[s] = frag(s_buf + slot * SLOTB, s);
+#pragma unroll
+            for (int i = 0; i < 16; i++) acc1[i] = MX_PAD;
+            k1[1] += TOP2_TILE_ROWS;
+            for (int c = 0; c < nfc; c++) {
+                // query tile 0 on the first row tile of chunk c (its fragments came with the last row tile of
+                // chunk c - 1, or above) beside the updates of query tile 1 on the last row tile of chunk c - 1
 #pragma unroll
                 for (int s = 0; s < 4; s++) {
                     acc0 = mfma(a[s], bq[0][s], s ? acc0 : crow);
                     __builtin_amdgcn_sched_barrier(0);
+                    pushk(1, acc1, s);
+                    __builtin_amdgcn_sched_barrier(0);
                 }
+                const int ln = seam(c, freed);
+                const int next = top2_ring_next(slot);
+                // this chunk's fragment offset from the lane id of the seam; the next slot's is a scalar step away
+                lbase = (ln & 31) * MX_RS + (ln >> 5) * 16;
+                const unsigned char *sb = s_buf + slot * SLOTB, *sn = sb + (next - slot) * SLOTB;
 #pragma unroll
                 for (int tt = 0; tt < NTILE; tt++) {
-                    // query tile 1 of row tile tt beside the updates of query tile 0
+                    // query tile 1 of row tile tt beside the updates of query tile 0; the last row tile takes the
+                    // next row tile's fragments from the next slot (chunk c + 1, written one barrier ago; when
+                    // there is no such chunk, or it is not full, the fragments are not used)
+                    const unsigned char *nb = tt + 1 < NTILE ? sb + (tt + 1) * 32 * MX_RS : sn;
 #pragma unroll
                     for (int s = 0; s < 4; s++) {
                         acc1 = mfma(a[s], bq[1][s], s ? acc1 : crow);
-                        if (tt + 1 < NTILE) a[s] = frag(sb + (tt + 1) * 32 * MX_RS, s);
+                        a[s] = frag(nb, s);
                         __builtin_amdgcn_sched_barrier(0);   // the MFMA first: its K-step, not the update, paces the wave
                         pushk(0, acc0, s);
                         __builtin_amdgcn_sched_barrier(0);
@@ -1072,14 +1136,37 @@ __global__ __launch_bounds__(NW * 64) void k_top2_fp4q2(const uint32_t *__restri
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
-#pragma unroll
-                for (int s = 0; s < 4; s++) push(1, acc1, s);
-            } else {
-#pragma unroll 1
-                for (int tt = 0; tt < nfull; tt++) tile(sb + tt * 32 * MX_RS, crow);
+                freed = slot;
+                slot = next;
             }
+#pragma unroll
+            for (int s = 0; s < 4; s++) push(1, acc1, s);
+        }
+    } else {
+        for (int c = 0; c < nfc; c++) {
+            seam(c, freed);
+            if (act0) {
+                const int nfull = min(NTILE, (nt - c * CR) / 32);   // NTILE; a run-time bound keeps the loop rolled
+#pragma unroll 1
+                for (int tt = 0; tt < nfull; tt++) tile(s_buf + slot * SLOTB + tt * 32 * MX_RS, crow);
+            }
+            freed = slot;
+            slot = top2_ring_next(slot);
+        }
+    }
+    if (nfc < nch) {
+        // the partial last chunk, unpipelined: its full row tiles, then the row tile that nt cuts
+        seam(nfc, freed);
+        if (act0) {
+            // the lane's half and fragment offset formed again from the lane id, not kept through the pipeline
+            const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)), h = ln >> 5;
+            lbase = (ln & 31) * MX_RS + h * 16;
+            const unsigned char *sb = s_buf + slot * SLOTB;
+            const int c0 = nfc * CR, nfull = (nt - c0) / 32;
+#pragma unroll 1
+            for (int tt = 0; tt < nfull; tt++) tile(sb + tt * 32 * MX_RS, crow);
             const int lim = nt - (c0 + nfull * 32);
-            if (nfull < NTILE && lim > 0) {
+            if (lim > 0) {
                 f32x16 cin;
 #pragma unroll
                 for (int i = 0; i < 16; i++)
@@ -1087,8 +1174,6 @@ __global__ __launch_bounds__(NW * 64) void k_top2_fp4q2(const uint32_t *__restri
                 tile(sb + nfull * 32 * MX_RS, cin);
             }
         }
-        if (more) store_chunk((c + 1) & 1, pw);
-        __syncthreads();
     }
     if (!act0) return;
     const int base = 32 * ((nt + 31) / 32);
