@@ -42,6 +42,7 @@
 // (tools/micro/mfma_i8_rate.hip: the chip holds 18.6 ns per 32x32x32 MFMA per SIMD, not 13.3).
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "osg_internal.h"
 #include "top2_key.h"
@@ -904,8 +905,8 @@ __global__ __launch_bounds__(NW * 64) void k_top2_fp4p(const uint32_t *__restric
 // and 3 / 3 / 2 pairs behind K-steps 1-3 (pushk), so that no update reads an accumulator right after the MFMA
 // that wrote it.  Only the first kept key is rebased from tile to tile; the second never is (top2_key.h).
 // The expanded chunks live in a ring of three LDS slots (top2_ring.h): chunk c in slot c % 3, chunks 0 and 1
-// stored by the prologue, and behind the one barrier at the top of block c every thread expands chunk c + 2 into
-// the slot chunk c - 1 has left and asks for chunk c + 3's packed words.  The barrier only guards the reuse of a
+// stored by the prologue, and behind the one barrier at the top of block c every thread expands chunk c + 2 (where
+// there is one) into the slot chunk c - 1 has left and asks for chunk c + 3's packed words.  The barrier only guards the reuse of a
 // slot, so the pipeline runs through all full chunks without a drain: the last row tile of a chunk prefetches the
 // next slot's first fragments, and query tile 0's chain on them issues in front of the barrier beside query tile
 // 1's last updates of the chunk.  The chain's first step runs beside updates on pad keys (every step has one
@@ -915,6 +916,16 @@ __global__ __launch_bounds__(NW * 64) void k_top2_fp4p(const uint32_t *__restric
 // in the loads, stores and barriers.  Every wave executes the same 2 + ceil(nt / CR) barriers, in wave-uniform
 // control flow that depends on nt alone.  The byte table sits at LDS address 0, the ring behind it; the nibble
 // order of both operands is spread_nib9's.
+// Vector issue is what the chunk loop runs on.  Per two-tile wave and 256-row chunk it has 64 MFMAs, which hold the
+// SIMD's one vector issue port for 8 cycles each, and 346 VALU at 4: the 336 key updates (21 per row tile and
+// query tile, their floor with three-input ops) and 10 in the seam behind the barrier, 8 byte shifts for the table
+// addresses and the adds of the two slot bases.  Four waves share the port: 4 x (4 x 346 + 8 x 64) = 7584 cycles of
+// issue against the 4 x 64 x 32 = 8192 the matrix pipe needs, 0.93 of it (0.97 with the 33 seam VALU this kernel
+// had while it formed its offsets again from the lane id at every seam and selected zero for rows past nt).  So
+// the seam holds no offset arithmetic: the staging and fragment offsets live in registers through the blocks,
+// the packed rows come through a buffer descriptor whose range check returns zero past row nt, chunk and slot
+// bases are scalar, and both MFMA scales share one register.  The last two blocks of a workgroup, which have no
+// chunk left to expand, are copies of the block without the expansion.
 template <int NW, int CR>
 __global__ __launch_bounds__(NW * 64) void k_top2_fp4q2(const uint32_t *__restrict__ query, int nq,
                                                          const uint32_t *__restrict__ train, int nt,
@@ -950,23 +961,29 @@ __global__ __launch_bounds__(NW * 64) void k_top2_fp4q2(const uint32_t *__restri
     const int qw0 = qb * (NW * 64) + w * 64;
     const bool act0 = qw0 < nq, act1 = qw0 + 32 < nq;   // wave-uniform
 
-    // thread t expands words epart * WPT .. of row t / TPR: word offset t * WPT into the chunk's packed rows
-    auto load_chunk = [&](int t, int c0, uint32_t (&pw)[WPT]) {
-        // a 32-bit byte offset from the frame's (wave-uniform) base: nt <= 8192 rows of 32 B, and a few chunks
-        // past them.  A row past nt reads the frame's first bytes instead (nt >= 1); store_chunk zeroes it.  A
-        // select, not a branch, and nothing here waits for the loaded words.
-        const char *src = (const char *)tf + (c0 + t / TPR < nt ? (unsigned)((c0 * 8 + t * WPT) * 4) : 0u);
+    // thread t expands words (t % TPR) * WPT .. of row t / TPR.  Its three lane-dependent offsets are formed once
+    // and held through the chunks: the packed source offset within a chunk (src8), the staging destination
+    // within a slot (stg) and, below, the fragment offset (lbase).  Chunk and slot bases are wave-uniform.
+    const unsigned src8 = (unsigned)t * (WPT * 4);
+    const int stg = (t / TPR) * MX_RS + (t % TPR) * (16 * WPT);
+    // the packed words of chunk c0 / CR through a buffer descriptor over what the frame has left from row c0
+    // on (formed on the scalar unit): a row past nt is out of range and reads as zero words, which expand to
+    // zero nibbles (D = C exactly), with no compare or select in the vector stream and no address arithmetic
+    // but the held offset.  nt <= 8192 rows of 32 B; nothing here waits for the loaded words.
+    auto load_chunk = [&](unsigned src8, int c0, uint32_t (&pw)[WPT]) {
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+            (void *)((const char *)tf + (size_t)c0 * 32), 0, max(nt - c0, 0) * 32, 0x00020000);
 #pragma unroll
         for (int i = 0; i < WPT; i += 2) {
-            const uint2 v = *(const uint2 *)(src + 4 * i);
+            const uint2 v = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rs, (int)src8 + 4 * i, 0, 0));
             pw[i] = v.x;
             pw[i + 1] = v.y;
         }
     };
     // chunks 0 and 1 are asked for first, so that they arrive behind the forming of the query fragments
     uint32_t pw[WPT], p1[WPT];
-    load_chunk(t, 0, pw);
-    load_chunk(t, CR, p1);
+    load_chunk(src8, 0, pw);
+    load_chunk(src8, CR, p1);
 
     i32x8 bq[2][4];
     int k1[2], k2[2];
@@ -992,26 +1009,32 @@ __global__ __launch_bounds__(NW * 64) void k_top2_fp4q2(const uint32_t *__restri
     f32x16 crow;
 #pragma unroll
     for (int i = 0; i < 16; i++) crow[i] = MX_BIAS + (float)((i & 3) + 8 * (i >> 2) + 4 * h);
-    int lbase = r * MX_RS + h * 16;
+    int lbase = r * MX_RS + h * 16;   // the fragment offset within a slot
 
-    // pw: what load_chunk(c0, pw) gave.  Rows past nt become zero nibbles: D = C exactly.
-    auto store_chunk = [&](int t, int buf, int c0, const uint32_t (&pw)[WPT]) {
-        const bool in = c0 + t / TPR < nt;
-        unsigned char *dst = s_buf + buf * SLOTB + ((t & (NT - 1)) / TPR) * MX_RS + (t % TPR) * (16 * WPT);
+    // the table's word shift as a scalar register the compiler cannot see through: the byte-select shifts that form
+    // the table addresses then take it as their scalar operand, where a literal 2 would sit in a vector register
+    int two;
+    asm("s_mov_b32 %0, 2" : "=s"(two));
+    // pw: what load_chunk gave (zero words for rows past nt)
+    auto store_chunk = [&](int buf, const uint32_t (&pw)[WPT]) {
+        unsigned char *dst = s_buf + buf * SLOTB + stg;
 #pragma unroll
         for (int i = 0; i < WPT; i++) {
-            const uint32_t x = in ? pw[i] : 0u;
-            *(i32x4 *)(dst + 16 * i) =
-                i32x4{(int)s_lut[x & 0xFFu], (int)s_lut[(x >> 8) & 0xFFu], (int)s_lut[(x >> 16) & 0xFFu],
-                      (int)s_lut[x >> 24]};
+            const uint32_t x = pw[i];
+            auto lut = [&](uint32_t byte) { return *(const int *)(s_mem + (byte << two)); };
+            *(i32x4 *)(dst + 16 * i) = i32x4{lut(x & 0xFFu), lut((x >> 8) & 0xFFu), lut((x >> 16) & 0xFFu), lut(x >> 24)};
         }
     };
-    auto frag = [&](const unsigned char *tb, int s) -> i32x8 {
-        const i32x4 v = *(const i32x4 *)(tb + lbase + 32 * s);
+    // the 16 bytes of K-step s at byte offset `off` from the lane's fragment offset
+    auto frag = [&](int off, int s) -> i32x8 {
+        const i32x4 v = *(const i32x4 *)(s_buf + lbase + off + 32 * s);
         return i32x8{v[0], v[1], v[2], v[3], 0, 0, 0, 0};
     };
+    // both E8M0 scales in one register: the train operand's in byte 0 (byte select 0), the query operand's 1.0 in
+    // byte 1 (byte select 1, op_sel:[0,1,0] in the ISA) and once more in byte 2
+    constexpr int MX_SCALES = MX_SCALE_TRAIN | (MX_SCALE_ONE << 8) | (MX_SCALE_ONE << 16);
     auto mfma = [&](const i32x8 &a, const i32x8 &bb, const f32x16 &c) {
-        return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, bb, c, 4, 4, 0, MX_SCALE_TRAIN, 0, MX_SCALE_ONE);
+        return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, bb, c, 4, 4, 0, MX_SCALES, 1, MX_SCALES);
     };
     // key pairs 2 s and 2 s + 1 of query tile j's accumulator; after the last pair the first key moves to the
     // next row tile's base.  The second key is never rebased (only its distance is output; top2_key.h has the
@@ -1035,7 +1058,7 @@ __global__ __launch_bounds__(NW * 64) void k_top2_fp4q2(const uint32_t *__restri
         if (s == 3) k1[j] -= TOP2_TILE_ROWS;
     };
     // one row tile, unpipelined: both chains when the wave has two tiles, then their updates
-    auto tile = [&](const unsigned char *tb, const f32x16 &cin) {
+    auto tile = [&](int tb, const f32x16 &cin) {
         i32x8 a[4];
 #pragma unroll
         for (int s = 0; s < 4; s++) a[s] = frag(tb, s);
@@ -1057,30 +1080,26 @@ __global__ __launch_bounds__(NW * 64) void k_top2_fp4q2(const uint32_t *__restri
     };
 
     const int nch = top2_ring_chunks(nt, CR), nfc = top2_ring_full_chunks(nt, CR);
+    // the full chunks whose block expands a chunk that exists (chunk c + 2 < nch)
+    const int nex = min(nfc, max(nch - TOP2_RING_AHEAD, 0));
     __syncthreads();   // the table
-    store_chunk(t, top2_ring_slot(0), 0, pw);
-    store_chunk(t, top2_ring_slot(1), CR, p1);
-    load_chunk(t, TOP2_RING_AHEAD * CR, pw);
+    store_chunk(top2_ring_slot(0), pw);
+    store_chunk(top2_ring_slot(1), p1);
+    load_chunk(src8, TOP2_RING_AHEAD * CR, pw);
     __syncthreads();
-    // the lane id taken again (as volatile asm, or it is hoisted and kept): returns it
-    auto lane_again = [&]() {
-        int ln;
-        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
-        return ln & 63;
-    };
     // top of block c, the same for every wave: the barrier (every wave has finished chunk c - 1, and chunk c + 1 is
-    // visible), then chunk c + 2 into the slot chunk c - 1 leaves and the global load of chunk c + 3.  The two
-    // ds_write_b128 are waited for at the next barrier only, a whole block later.
-    // Without a branch (past the last chunk it stores zero rows into the free slot and loads nothing): the block
-    // stays one basic block, so the MFMA chain issued in front of the barrier stays there.
-    // The staging addresses are formed again from the lane id each time: a few VALU beside the MFMAs in flight
-    // instead of registers held through the block.
-    auto seam = [&](int c, int freed) {
+    // visible), then, where chunk c + 2 exists (expand), that chunk into the slot chunk c - 1 leaves and the load
+    // of chunk c + 3.  The two ds_write_b128 are waited for at the next barrier only, a whole block later.
+    // Whether a block expands is a compile-time argument, not a branch: either form of the block stays one basic
+    // block, so the MFMA chain issued in front of the barrier stays there.  The last two blocks of a workgroup have
+    // no chunk to expand and only pass the barrier; every wave still executes 2 + nch barriers.
+    // What the expansion costs in vector issue: 8 shifts for the table addresses and one add of the slot base.
+    auto seam = [&](int c, int freed, auto expand) {
         __syncthreads();
-        const int ln = lane_again(), tv = w * 64 + ln;
-        store_chunk(tv, freed, (c + TOP2_RING_AHEAD) * CR, pw);
-        load_chunk(tv, (c + TOP2_RING_AHEAD + 1) * CR, pw);
-        return ln;
+        if constexpr (decltype(expand)::value) {
+            store_chunk(freed, pw);
+            load_chunk(src8, (c + TOP2_RING_AHEAD + 1) * CR, pw);
+        }
     };
     int slot = top2_ring_slot(0), freed = top2_ring_slot(TOP2_RING_SLOTS - 1);
     if (act1) {
@@ -1093,11 +1112,11 @@ __global__ __launch_bounds__(NW * 64) void k_top2_fp4q2(const uint32_t *__restri
             i32x8 a[4];
             f32x16 acc0, acc1;
 #pragma unroll
-            for (int s = 0; s < 4; s++) a[s] = frag(s_buf + slot * SLOTB, s);
+            for (int s = 0; s < 4; s++) a[s] = frag(slot * SLOTB, s);
 #pragma unroll
             for (int i = 0; i < 16; i++) acc1[i] = MX_PAD;
             k1[1] += TOP2_TILE_ROWS;
-            for (int c = 0; c < nfc; c++) {
+            auto block = [&](int c, auto expand) {
                 // query tile 0 on the first row tile of chunk c (its fragments came with the last row tile of
                 // chunk c - 1, or above) beside the updates of query tile 1 on the last row tile of chunk c - 1
 #pragma unroll
@@ -1107,17 +1126,17 @@ __global__ __launch_bounds__(NW * 64) void k_top2_fp4q2(const uint32_t *__restri
                     pushk(1, acc1, s);
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                const int ln = seam(c, freed);
+                seam(c, freed, expand);
                 const int next = top2_ring_next(slot);
-                // this chunk's fragment offset from the lane id of the seam; the next slot's is a scalar step away
-                lbase = (ln & 31) * MX_RS + (ln >> 5) * 16;
-                const unsigned char *sb = s_buf + slot * SLOTB, *sn = sb + (next - slot) * SLOTB;
 #pragma unroll
                 for (int tt = 0; tt < NTILE; tt++) {
                     // query tile 1 of row tile tt beside the updates of query tile 0; the last row tile takes the
                     // next row tile's fragments from the next slot (chunk c + 1, written one barrier ago; when
                     // there is no such chunk, or it is not full, the fragments are not used)
-                    const unsigned char *nb = tt + 1 < NTILE ? sb + (tt + 1) * 32 * MX_RS : sn;
+                    // The pipeline's fragment offset includes the slot's base and steps to the next slot here, in
+                    // place, by a wave-uniform amount: one register, one add per block.
+                    if (tt + 1 == NTILE) lbase += (next - slot) * SLOTB;
+                    const int nb = tt + 1 < NTILE ? (tt + 1) * 32 * MX_RS : 0;
 #pragma unroll
                     for (int s = 0; s < 4; s++) {
                         acc1 = mfma(a[s], bq[1][s], s ? acc1 : crow);
@@ -1138,30 +1157,38 @@ __global__ __launch_bounds__(NW * 64) void k_top2_fp4q2(const uint32_t *__restri
                 }
                 freed = slot;
                 slot = next;
-            }
+            };
+            // the blocks that expand, then the (at most two) that have nothing left to expand
+            int c = 0;
+            for (; c < nex; c++) block(c, std::true_type{});
+            if (c < nfc) block(c++, std::false_type{});
+            if (c < nfc) block(c++, std::false_type{});
 #pragma unroll
             for (int s = 0; s < 4; s++) push(1, acc1, s);
         }
     } else {
         for (int c = 0; c < nfc; c++) {
-            seam(c, freed);
+            if (c < nex) seam(c, freed, std::true_type{});
+            else seam(c, freed, std::false_type{});
             if (act0) {
                 const int nfull = min(NTILE, (nt - c * CR) / 32);   // NTILE; a run-time bound keeps the loop rolled
 #pragma unroll 1
-                for (int tt = 0; tt < nfull; tt++) tile(s_buf + slot * SLOTB + tt * 32 * MX_RS, crow);
+                for (int tt = 0; tt < nfull; tt++) tile(slot * SLOTB + tt * 32 * MX_RS, crow);
             }
             freed = slot;
             slot = top2_ring_next(slot);
         }
     }
     if (nfc < nch) {
-        // the partial last chunk, unpipelined: its full row tiles, then the row tile that nt cuts
-        seam(nfc, freed);
+        // the partial last chunk, unpipelined: its full row tiles, then the row tile that nt cuts.  Chunk nfc + 2
+        // never exists, so this block's seam is the barrier alone
+        seam(nfc, freed, std::false_type{});
         if (act0) {
-            // the lane's half and fragment offset formed again from the lane id, not kept through the pipeline
+            // the lane's half, and from it and the row the fragment offset, formed again from the lane id: the
+            // pipeline holds the offset alone, not its parts
             const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)), h = ln >> 5;
             lbase = (ln & 31) * MX_RS + h * 16;
-            const unsigned char *sb = s_buf + slot * SLOTB;
+            const int sb = slot * SLOTB;
             const int c0 = nfc * CR, nfull = (nt - c0) / 32;
 #pragma unroll 1
             for (int tt = 0; tt < nfull; tt++) tile(sb + tt * 32 * MX_RS, crow);

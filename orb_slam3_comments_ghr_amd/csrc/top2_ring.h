@@ -5,7 +5,8 @@
 // A workgroup walks nch = ceil(nt / CR) chunks of CR train rows.  Chunk c is expanded into slot c % 3.  The
 // prologue stores chunks 0 and 1 behind the table's barrier and closes with a second barrier.  Block c (the
 // compute of chunk c) opens with one barrier; behind it every thread expands its part of chunk c + 2, which goes
-// into the slot that held chunk c - 1.  An epoch is the number of barriers a wave has passed, so block c runs in
+// into the slot that held chunk c - 1 (the last two blocks, whose chunk c + 2 does not exist, write nothing: their
+// write epochs stay free).  An epoch is the number of barriers a wave has passed, so block c runs in
 // epoch 3 + c.  All waves, whether they own two query tiles, one or none, pass the same 2 + nch barriers.
 //
 // Reads: a wave with two query tiles runs the row tiles of full chunks as one pipeline that does not stop at a
