@@ -22,6 +22,8 @@ ifdef MLPNP_PROF
 HIPFLAGS += -DOSG_MLPNP_PROF
 endif
 HDRS = include/osg.h include/osg_ba.h $(CSRC)/osg_internal.h
+# the RANSAC solvers' shared device helpers and host batch scaffolding
+RANSAC_HDRS = $(CSRC)/ransac_common.h $(CSRC)/batch_io.h $(CSRC)/glibc_math.h
 
 OBJS = $(OBJDIR)/runtime.o $(OBJDIR)/hamming.o $(OBJDIR)/hamming_mfma.o $(OBJDIR)/match.o $(OBJDIR)/pose.o $(OBJDIR)/sim3opt.o $(OBJDIR)/sim3ransac.o $(OBJDIR)/mlpnp.o $(OBJDIR)/twoview.o $(OBJDIR)/essgraph.o $(OBJDIR)/ba.o $(OBJDIR)/dbow.o $(OBJDIR)/kfdb.o $(OBJDIR)/fuse.o $(OBJDIR)/triang.o $(OBJDIR)/desc.o $(OBJDIR)/sim3.o $(OBJDIR)/init.o $(OBJDIR)/stereo.o $(OBJDIR)/orb.o $(OBJDIR)/fast.o $(OBJDIR)/pyramid.o
 
@@ -42,13 +44,13 @@ $(OBJDIR)/match.o: $(CSRC)/match.hip $(HDRS) $(CSRC)/match_common.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
 $(OBJDIR)/pose.o: $(CSRC)/pose.hip $(HDRS) $(CSRC)/ba_common.h $(CSRC)/exact_math.h $(CSRC)/glibc_math.h $(CSRC)/match_common.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
-$(OBJDIR)/sim3opt.o: $(CSRC)/sim3opt.hip $(HDRS) $(CSRC)/ba_common.h $(CSRC)/sim3_common.h $(CSRC)/exact_math.h $(CSRC)/glibc_math.h | $(OBJDIR)
+$(OBJDIR)/sim3opt.o: $(CSRC)/sim3opt.hip $(HDRS) $(CSRC)/ba_common.h $(CSRC)/sim3_common.h $(CSRC)/exact_math.h $(CSRC)/glibc_math.h $(CSRC)/batch_io.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
-$(OBJDIR)/sim3ransac.o: $(CSRC)/sim3ransac.hip $(HDRS) $(CSRC)/sim3ransac_select.h $(CSRC)/glibc_math.h | $(OBJDIR)
+$(OBJDIR)/sim3ransac.o: $(CSRC)/sim3ransac.hip $(HDRS) $(CSRC)/sim3ransac_select.h $(RANSAC_HDRS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
-$(OBJDIR)/mlpnp.o: $(CSRC)/mlpnp.hip $(HDRS) $(CSRC)/mlpnp_select.h $(CSRC)/glibc_math.h | $(OBJDIR)
+$(OBJDIR)/mlpnp.o: $(CSRC)/mlpnp.hip $(HDRS) $(CSRC)/mlpnp_select.h $(RANSAC_HDRS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
-$(OBJDIR)/twoview.o: $(CSRC)/twoview.hip $(HDRS) $(CSRC)/twoview_select.h | $(OBJDIR)
+$(OBJDIR)/twoview.o: $(CSRC)/twoview.hip $(HDRS) $(CSRC)/twoview_select.h $(RANSAC_HDRS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
 $(OBJDIR)/essgraph.o: $(CSRC)/essgraph.hip $(HDRS) $(CSRC)/sim3_common.h $(CSRC)/exact_math.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@

@@ -2482,6 +2482,27 @@ struct Sim3SolverGather {
     }
 };
 
+// `iterations` sets of K distinct indices into [0, N), drawn as the reference's RANSAC loops draw them
+// (ref:src/Sim3Solver.cc:169-183, ref:src/MLPnPsolver.cpp:177-202, TwoViewReconstruction::Reconstruct): every set
+// starts from all N indices and makes K calls of H::random_int(0, available - 1), the drawn slot taking the last
+// available index.  out[K it + j] is draw j of set it.
+template <class H, int K>
+inline void draw_sets(int N, int iterations, std::vector<int32_t> &out)
+{
+    out.resize((size_t)K * iterations);
+    std::vector<size_t> vAllIndices(N), vAvailableIndices;
+    for (int i = 0; i < N; i++) vAllIndices[i] = (size_t)i;
+    for (int it = 0; it < iterations; it++) {
+        vAvailableIndices = vAllIndices;
+        for (int j = 0; j < K; j++) {
+            const int randi = H::random_int(0, (int)vAvailableIndices.size() - 1);
+            out[(size_t)K * it + j] = (int32_t)vAvailableIndices[randi];
+            vAvailableIndices[randi] = vAvailableIndices.back();
+            vAvailableIndices.pop_back();
+        }
+    }
+}
+
 // The first iterate() / find() draws all mRansacMaxIts sample triples through H::random_int in the
 // reference's order (the reference stops drawing when it converges: the one observable difference) and
 // evaluates them in one osg_sim3_ransac call; that call and every later one replay their window with
@@ -2587,18 +2608,7 @@ private:
         if (evaluated) return ok;
         evaluated = true;
         ok = false;
-        samples.resize(3 * (size_t)mRansacMaxIts);
-        std::vector<size_t> vAllIndices(N), vAvailableIndices;
-        for (int i = 0; i < N; i++) vAllIndices[i] = (size_t)i;
-        for (int it = 0; it < mRansacMaxIts; it++) {  // :169-183
-            vAvailableIndices = vAllIndices;
-            for (short i = 0; i < 3; ++i) {
-                const int randi = H::random_int(0, (int)vAvailableIndices.size() - 1);
-                samples[3 * (size_t)it + i] = (int32_t)vAvailableIndices[randi];
-                vAvailableIndices[randi] = vAvailableIndices.back();
-                vAvailableIndices.pop_back();
-            }
-        }
+        draw_sets<H, 3>(N, mRansacMaxIts, samples);  // :169-183
         counts.assign(mRansacMaxIts, 0);
         sim3.assign(13 * (size_t)mRansacMaxIts, 0.f);
         inlier.assign(N, 0);
@@ -2760,18 +2770,7 @@ public:
 private:
     bool evaluate(int len)
     {
-        samples.resize(6 * (size_t)len);
-        std::vector<size_t> vAllIndices(N), vAvailableIndices;
-        for (int i = 0; i < N; i++) vAllIndices[i] = (size_t)i;
-        for (int it = 0; it < len; it++) {  // :177-202
-            vAvailableIndices = vAllIndices;
-            for (short i = 0; i < 6; ++i) {
-                const int randi = H::random_int(0, (int)vAvailableIndices.size() - 1);
-                samples[6 * (size_t)it + i] = (int32_t)vAvailableIndices[randi];
-                vAvailableIndices[randi] = vAvailableIndices.back();
-                vAvailableIndices.pop_back();
-            }
-        }
+        draw_sets<H, 6>(N, len, samples);  // :177-202
         counts.assign(len, 0);
         inlier.assign(N, 0);
         osg_mlpnp_problem p{};
@@ -2837,19 +2836,8 @@ public:
         }
         const int N = (int)mvMatches12.size();
         if (N < 8 || mMaxIterations < 1) return false;
-        mvSets.assign(8 * (size_t)mMaxIterations, 0);
-        std::vector<size_t> vAllIndices(N), vAvailableIndices;
-        for (int i = 0; i < N; i++) vAllIndices[i] = (size_t)i;
         H::seed_rand_once(0);
-        for (int it = 0; it < mMaxIterations; it++) {
-            vAvailableIndices = vAllIndices;
-            for (size_t j = 0; j < 8; j++) {
-                const int randi = H::random_int(0, (int)vAvailableIndices.size() - 1);
-                mvSets[8 * (size_t)it + j] = (int32_t)vAvailableIndices[randi];
-                vAvailableIndices[randi] = vAvailableIndices.back();
-                vAvailableIndices.pop_back();
-            }
-        }
+        draw_sets<H, 8>(N, mMaxIterations, mvSets);
         std::vector<float> keys1(2 * vKeys1.size()), keys2(2 * vKeys2.size()), kp1(2 * (size_t)N), kp2(2 * (size_t)N);
         for (size_t i = 0; i < vKeys1.size(); i++) keys1[2 * i] = vKeys1[i].pt.x, keys1[2 * i + 1] = vKeys1[i].pt.y;
         for (size_t i = 0; i < vKeys2.size(); i++) keys2[2 * i] = vKeys2[i].pt.x, keys2[2 * i + 1] = vKeys2[i].pt.y;

@@ -20,9 +20,9 @@
 #include <cstring>
 #include <vector>
 
-#include "glibc_math.h"
+#include "batch_io.h"
 #include "mlpnp_select.h"
-#include "osg_internal.h"
+#include "ransac_common.h"
 
 namespace {
 
@@ -58,28 +58,6 @@ __device__ __forceinline__ void wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// GeometricCamera::project(cv::Point3f): ref:src/CameraModels/Pinhole.cpp:39-43,
-// ref:src/CameraModels/KannalaBrandt8.cpp:40-55 (the arithmetic of sim3ransac.hip's project_f)
-__device__ __forceinline__ void project_f(const osg_camera &c, float x, float y, float z, float &u, float &v)
-{
-    if (c.type == OSG_CAM_KB8) {
-        const float x2_plus_y2 = x * x + y * y;
-        const float theta = osgm::atan2f_fd(sqrtf(x2_plus_y2), z);
-        const float psi = osgm::atan2f_fd(y, x);
-        const float theta2 = theta * theta;
-        const float theta3 = theta * theta2;
-        const float theta5 = theta3 * theta2;
-        const float theta7 = theta5 * theta2;
-        const float theta9 = theta7 * theta2;
-        const float r = theta + c.p[4] * theta3 + c.p[5] * theta5 + c.p[6] * theta7 + c.p[7] * theta9;
-        u = c.p[0] * r * cosf(psi) + c.p[2];
-        v = c.p[1] * r * sinf(psi) + c.p[3];
-    } else {
-        u = c.p[0] * x / z + c.p[2];
-        v = c.p[1] * y / z + c.p[3];
-    }
 }
 
 __device__ __forceinline__ double det3(const double *m)
@@ -167,53 +145,12 @@ __device__ inline int rank3(const double *M)
     return rank;
 }
 
-// one Jacobi rotation angle for the pair (app, aqq, apq): t = tan, c, s
-__device__ __forceinline__ void jacobi_angle(double app, double aqq, double apq, double &t, double &c, double &s)
-{
-    const double th = (aqq - app) / (2.0 * apq);
-    t = (th >= 0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));
-    c = 1.0 / sqrt(t * t + 1.0);
-    s = t * c;
-}
-
 // eigen-decomposition of the symmetric 3 x 3 S (row-major), ascending: cyclic Jacobi in double
 __device__ inline void eig3_ascending(const double *S, double *G /* columns = eigenvectors, row-major */)
 {
     double A[3][3] = {{S[0], S[1], S[2]}, {S[3], S[4], S[5]}, {S[6], S[7], S[8]}};
-    double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-#pragma unroll 1
-    for (int sweep = 0; sweep < 16; sweep++) {
-        const double off = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[1][2] * A[1][2];
-        const double diag = A[0][0] * A[0][0] + A[1][1] * A[1][1] + A[2][2] * A[2][2];
-        if (!(off > 1e-40 * diag)) break;
-#pragma unroll
-        for (int p = 0; p < 2; p++)
-#pragma unroll
-            for (int q = p + 1; q < 3; q++) {
-                const double apq = A[p][q];
-                if (apq == 0.0) continue;
-                double t, c, s;
-                jacobi_angle(A[p][p], A[q][q], apq, t, c, s);
-#pragma unroll
-                for (int k = 0; k < 3; k++) {
-                    const double akp = A[k][p], akq = A[k][q];
-                    A[k][p] = c * akp - s * akq;
-                    A[k][q] = s * akp + c * akq;
-                }
-#pragma unroll
-                for (int k = 0; k < 3; k++) {
-                    const double apk = A[p][k], aqk = A[q][k];
-                    A[p][k] = c * apk - s * aqk;
-                    A[q][k] = s * apk + c * aqk;
-                }
-#pragma unroll
-                for (int k = 0; k < 3; k++) {
-                    const double vkp = V[k][p], vkq = V[k][q];
-                    V[k][p] = c * vkp - s * vkq;
-                    V[k][q] = s * vkp + c * vkq;
-                }
-            }
-    }
+    double V[3][3];
+    jacobi_sym<3>(A, V, 16, 1e-40);
     // ascending order of the three diagonal entries
     int o0 = 0, o1 = 1, o2 = 2;
     double d0 = A[0][0], d1 = A[1][1], d2 = A[2][2];
@@ -248,8 +185,8 @@ __device__ inline void polar_uvt(const double *M, double *R)
                 const double be = m[q][0] * m[q][0] + m[q][1] * m[q][1] + m[q][2] * m[q][2];
                 const double ga = m[p][0] * m[q][0] + m[p][1] * m[q][1] + m[p][2] * m[q][2];
                 if (!(ga * ga > 1e-32 * al * be)) continue;
-                double t, c, s;
-                jacobi_angle(al, be, ga, t, c, s);
+                double c, s;
+                jacobi_rotation(al, be, ga, c, s);
 #pragma unroll
                 for (int k = 0; k < 3; k++) {
                     const double a = m[p][k], b = m[q][k];
@@ -419,10 +356,7 @@ __device__ inline void compute_pose(const double (*f)[3], const double (*p)[3], 
                     }
                     double c = 1.0, sn = 0.0;
                     const double apq = q < N ? A[12 * p + q] : 0.0;
-                    if (apq != 0.0) {
-                        double t;
-                        jacobi_angle(A[13 * p], A[13 * q], apq, t, c, sn);
-                    }
+                    if (apq != 0.0) jacobi_rotation(A[13 * p], A[13 * q], apq, c, sn);
                     const bool rot = apq != 0.0;
                     cc[p] = c, ss[p] = -sn, pa[p] = rot ? (double)q : (double)p;
                     cc[q] = c, ss[q] = sn, pa[q] = rot ? (double)p : (double)q;
@@ -806,27 +740,7 @@ __global__ __launch_bounds__(64) void k_mlpnp_select(const MProbDev *__restrict_
         o.Tcw[15] = 1.f;
     }
     hyp = __shfl(hyp, 0);
-    uint8_t *dst = inlier + P.pt_off;
-    if (hyp < 0) {
-        for (int i = lane; i < P.n; i += 64) dst[i] = 0;
-        return;
-    }
-    const unsigned long long *mask = masks + P.mask_off + (size_t)hyp * P.words;
-    for (int i = lane; i < P.n; i += 64) dst[i] = (uint8_t)((mask[i >> 6] >> (i & 63)) & 1ull);
-}
-
-// 0: every sample set holds six distinct indices into [0, n); 1: an index outside; 2: a repeated index
-int check_samples(const osg_mlpnp_problem &q, int *h_bad)
-{
-    for (int h = 0; h < q.n_hyp; h++) {
-        const int32_t *s = q.samples + 6 * (size_t)h;
-        for (int i = 0; i < 6; i++) {
-            if (s[i] < 0 || s[i] >= q.n) return *h_bad = h, 1;
-            for (int j = 0; j < i; j++)
-                if (s[i] == s[j]) return *h_bad = h, 2;
-        }
-    }
-    return 0;
+    expand_mask(hyp < 0 ? nullptr : masks + P.mask_off + (size_t)hyp * P.words, P.n, inlier + P.pt_off, lane);
 }
 
 }  // namespace
@@ -837,7 +751,7 @@ int osg_mlpnp_check_samples(const osg_mlpnp_problem *p)
 {
     int h_bad = -1;
     if (!p || p->n < 0 || p->n_hyp < 1 || !p->samples) return OSG_E_INVALID;
-    return check_samples(*p, &h_bad) ? OSG_E_INVALID : 0;
+    return check_sets(p->samples, 6, p->n_hyp, p->n, &h_bad) ? OSG_E_INVALID : 0;
 }
 
 void osg_mlpnp_ransac_parameters(double prob, int32_t min_inliers, int32_t max_its, int32_t min_set, float epsilon,
@@ -868,7 +782,7 @@ int osg_mlpnp_ransac_batch(osg_ctx *ctx, const osg_mlpnp_problem *p, int32_t nb,
         OSG_REQUIRE(ctx, q.n >= 6, "fewer than 6 matches");
         OSG_REQUIRE(ctx, q.bearing && q.p3dw && q.p2d && q.max_err && q.samples, "match arrays");
         int h_bad = -1;
-        const int why = check_samples(q, &h_bad);
+        const int why = check_sets(q.samples, 6, q.n_hyp, q.n, &h_bad);
         OSG_REQUIRE(ctx, why != 1, "sample index outside [0, n) in hypothesis %d of problem %d", h_bad, b);
         OSG_REQUIRE(ctx, why != 2, "repeated sample index in hypothesis %d of problem %d", h_bad, b);
         MProbDev d;
@@ -912,58 +826,42 @@ int osg_mlpnp_ransac_batch(osg_ctx *ctx, const osg_mlpnp_problem *p, int32_t nb,
     if (na == 0) return 0;
     bool want_hyp = false;
     for (int k = 0; k < na; k++) want_hyp = want_hyp || r[src[k]].hyp_inliers || r[src[k]].hyp_pose || r[src[k]].hyp_info;
-    auto al = [](size_t v) { return (v + 255) & ~size_t(255); };
-    // in: probs | bearing | p3dw | p2d | max_err | samples
-    const size_t i_br = al(sizeof(MProbDev) * na), i_p3 = i_br + al(12 * n_pts), i_p2 = i_p3 + al(12 * n_pts);
-    const size_t i_mx = i_p2 + al(8 * n_pts), i_sm = i_mx + al(4 * n_pts);
-    const size_t in_bytes = i_sm + al(24 * n_hyp);
-    // out: MSelOut | inlier bytes | counts | info | poses  (the last three are downloaded on request)
-    const size_t o_in = al(sizeof(MSelOut) * na), o_cnt = o_in + al(n_pts), o_inf = o_cnt + al(4 * n_hyp);
-    const size_t o_ps = o_inf + al(12 * n_hyp);
-    const size_t out_bytes = o_ps + al(96 * n_hyp);
-    const size_t dl_bytes = want_hyp ? out_bytes : o_cnt;
-    char *pin = (char *)osg_pinned(ctx, in_bytes + out_bytes);
-    if (!pin) return osg_set_error(ctx, OSG_E_NOMEM, "pinned alloc failed");
-    OSG_RC(osg_idle(ctx));  // the pinned block may still be in use
-    std::memcpy(pin, hp.data(), sizeof(MProbDev) * na);
+    osg_batch_io io(ctx);
+    const osg_seg i_pr = io.in(sizeof(MProbDev), na), i_br = io.in(3 * sizeof(float), n_pts), i_p3 = io.in(3 * sizeof(float), n_pts);
+    const osg_seg i_p2 = io.in(2 * sizeof(float), n_pts), i_mx = io.in(sizeof(float), n_pts), i_sm = io.in(6 * sizeof(int32_t), n_hyp);
+    // the counts, the info and the poses are downloaded on request
+    const osg_seg o_res = io.out(sizeof(MSelOut), na), o_in = io.out(1, n_pts), o_cnt = io.out(sizeof(int32_t), n_hyp);
+    const osg_seg o_inf = io.out(3 * sizeof(int32_t), n_hyp), o_ps = io.out(12 * sizeof(double), n_hyp);
+    const size_t dl_bytes = want_hyp ? io.out_bytes : o_cnt.off;
+    OSG_RC(io.stage());
+    io.put(i_pr, 0, hp.data(), na);
     for (int k = 0; k < na; k++) {
         const osg_mlpnp_problem &q = p[src[k]];
-        const size_t off = hp[k].pt_off, m = q.n;
-        std::memcpy(pin + i_br + 12 * off, q.bearing, 12 * m);
-        std::memcpy(pin + i_p3 + 12 * off, q.p3dw, 12 * m);
-        std::memcpy(pin + i_p2 + 8 * off, q.p2d, 8 * m);
-        std::memcpy(pin + i_mx + 4 * off, q.max_err, 4 * m);
-        std::memcpy(pin + i_sm + 24 * (size_t)hp[k].hyp_off, q.samples, 24 * (size_t)q.n_hyp);
+        io.put(i_br, hp[k].pt_off, q.bearing, q.n);
+        io.put(i_p3, hp[k].pt_off, q.p3dw, q.n);
+        io.put(i_p2, hp[k].pt_off, q.p2d, q.n);
+        io.put(i_mx, hp[k].pt_off, q.max_err, q.n);
+        io.put(i_sm, hp[k].hyp_off, q.samples, q.n_hyp);
     }
-    char *din = nullptr, *dout = nullptr;
+    OSG_RC(io.upload());
     unsigned long long *dmask = nullptr;
-    OSG_ALLOC(ctx, din, SLOT_BA0, in_bytes);
-    OSG_ALLOC(ctx, dout, SLOT_BA1, out_bytes);
     OSG_ALLOC(ctx, dmask, SLOT_BA2, 8 * n_words);
-    OSG_RC(osg_upload(ctx, din, pin, in_bytes));
     const size_t lds_bytes = TILE_BYTES + lds;
     if (lds_bytes > 48 * 1024)
         OSG_HIP_CHECK(ctx, hipFuncSetAttribute((const void *)k_mlpnp_eval, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    hipEvent_t *ev = osg_ctx_events(ctx);
-    if (!ev) return osg_set_error(ctx, OSG_E_HIP, "event create failed");
-    OSG_HIP_CHECK(ctx, hipEventRecord(ev[0], ctx->stream));
-    hipLaunchKernelGGL(k_mlpnp_eval, dim3((max_hyp + HPB - 1) / HPB, na), dim3(NT), lds_bytes, ctx->stream,
-                       (const MProbDev *)din, (const float *)(din + i_br), (const float *)(din + i_p3),
-                       (const float *)(din + i_p2), (const float *)(din + i_mx), (const int *)(din + i_sm),
-                       (int *)(dout + o_cnt), (double *)(dout + o_ps), (int *)(dout + o_inf), dmask);
+    OSG_RC(io.start());
+    const MProbDev *dp = io.dev_in<const MProbDev>(i_pr);
+    hipLaunchKernelGGL(k_mlpnp_eval, dim3((max_hyp + HPB - 1) / HPB, na), dim3(NT), lds_bytes, ctx->stream, dp,
+                       io.dev_in<const float>(i_br), io.dev_in<const float>(i_p3), io.dev_in<const float>(i_p2),
+                       io.dev_in<const float>(i_mx), io.dev_in<const int>(i_sm), io.dev_out<int>(o_cnt),
+                       io.dev_out<double>(o_ps), io.dev_out<int>(o_inf), dmask);
     OSG_HIP_CHECK(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_mlpnp_select, dim3(na), dim3(64), 0, ctx->stream, (const MProbDev *)din,
-                       (const int *)(dout + o_cnt), (const double *)(dout + o_ps), (const unsigned long long *)dmask,
-                       (MSelOut *)dout, (uint8_t *)(dout + o_in));
+    hipLaunchKernelGGL(k_mlpnp_select, dim3(na), dim3(64), 0, ctx->stream, dp, io.dev_out<const int>(o_cnt),
+                       io.dev_out<const double>(o_ps), (const unsigned long long *)dmask, io.dev_out<MSelOut>(o_res),
+                       io.dev_out<uint8_t>(o_in));
     OSG_HIP_CHECK(ctx, hipGetLastError());
-    OSG_HIP_CHECK(ctx, hipEventRecord(ev[1], ctx->stream));
-    char *pout = pin + in_bytes;
-    OSG_RC(osg_download(ctx, pout, dout, dl_bytes));
-    OSG_RC(osg_wait(ctx));
-    float kms = 0.f;
-    OSG_HIP_CHECK(ctx, hipEventElapsedTime(&kms, ev[0], ev[1]));
-    ctx->last_kernel_ms = kms;
-    const MSelOut *res = (const MSelOut *)pout;
+    OSG_RC(io.finish(dl_bytes));
+    const MSelOut *res = io.result<MSelOut>(o_res);
     int found = 0;
     for (int k = 0; k < na; k++) {
         const MSelOut &s = res[k];
@@ -976,10 +874,10 @@ int osg_mlpnp_ransac_batch(osg_ctx *ctx, const osg_mlpnp_problem *p, int32_t nb,
         std::memcpy(o.R, s.R, sizeof o.R);
         std::memcpy(o.t, s.t, sizeof o.t);
         std::memcpy(o.Tcw, s.Tcw, sizeof o.Tcw);
-        std::memcpy(o.inlier, pout + o_in + hp[k].pt_off, (size_t)hp[k].n);
-        if (o.hyp_inliers) std::memcpy(o.hyp_inliers, pout + o_cnt + 4 * (size_t)hp[k].hyp_off, 4 * (size_t)hp[k].n_hyp);
-        if (o.hyp_info) std::memcpy(o.hyp_info, pout + o_inf + 12 * (size_t)hp[k].hyp_off, 12 * (size_t)hp[k].n_hyp);
-        if (o.hyp_pose) std::memcpy(o.hyp_pose, pout + o_ps + 96 * (size_t)hp[k].hyp_off, 96 * (size_t)hp[k].n_hyp);
+        io.get(o.inlier, o_in, hp[k].pt_off, hp[k].n);
+        if (o.hyp_inliers) io.get(o.hyp_inliers, o_cnt, hp[k].hyp_off, hp[k].n_hyp);
+        if (o.hyp_info) io.get(o.hyp_info, o_inf, hp[k].hyp_off, hp[k].n_hyp);
+        if (o.hyp_pose) io.get(o.hyp_pose, o_ps, hp[k].hyp_off, hp[k].n_hyp);
         found += s.hyp >= 0 ? 1 : 0;
     }
     return found;

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "ba_common.h"
+#include "batch_io.h"
 #include "sim3_common.h"
 
 using namespace osgba;
@@ -530,47 +531,32 @@ int osg_optimize_sim3_batch(osg_ctx *ctx, const osg_sim3_problem *p, int32_t nb,
         total += (size_t)q.n_pairs;
     }
     OSG_REQUIRE(ctx, total < (size_t(1) << 28), "too many pairs in one batch");
-    auto al = [](size_t v) { return (v + 255) & ~size_t(255); };
-    // in: probs | p1c | p2c | obs1 | obs2 | w1 | w2;  out: state | chi2 | S3Out
-    const size_t o_p1 = al(sizeof(S3ProbDev) * nb), o_p2 = o_p1 + al(24 * total), o_o1 = o_p2 + al(24 * total);
-    const size_t o_o2 = o_o1 + al(16 * total), o_w1 = o_o2 + al(16 * total), o_w2 = o_w1 + al(4 * total);
-    const size_t in_bytes = o_w2 + al(4 * total) + 256;
-    const size_t o_chi = al(total), o_res = o_chi + al(16 * total);
-    const size_t io_bytes = o_res + al(sizeof(S3Out) * nb) + 256;
-    char *pin = (char *)osg_pinned(ctx, in_bytes + io_bytes);
-    if (!pin) return osg_set_error(ctx, OSG_E_NOMEM, "pinned alloc failed");
-    OSG_RC(osg_idle(ctx));  // the pinned block may still be in use
-    std::memcpy(pin, hp.data(), sizeof(S3ProbDev) * nb);
+    osg_batch_io io(ctx);
+    const osg_seg i_pr = io.in(sizeof(S3ProbDev), nb), i_p1 = io.in(3 * sizeof(double), total), i_p2 = io.in(3 * sizeof(double), total);
+    const osg_seg i_o1 = io.in(2 * sizeof(double), total), i_o2 = io.in(2 * sizeof(double), total);
+    const osg_seg i_w1 = io.in(sizeof(float), total), i_w2 = io.in(sizeof(float), total);
+    const osg_seg o_st = io.out(1, total), o_chi = io.out(2 * sizeof(double), total), o_res = io.out(sizeof(S3Out), nb);
+    io.in(1, 256), io.out(1, 256);  // slack behind both blocks
+    OSG_RC(io.stage());
+    io.put(i_pr, 0, hp.data(), nb);
     for (int b = 0; b < nb; b++) {
         const size_t off = hp[b].pair_off, m = p[b].n_pairs;
-        if (!m) continue;
-        std::memcpy(pin + o_p1 + 24 * off, p[b].p1c, 24 * m);
-        std::memcpy(pin + o_p2 + 24 * off, p[b].p2c, 24 * m);
-        std::memcpy(pin + o_o1 + 16 * off, p[b].obs1, 16 * m);
-        std::memcpy(pin + o_o2 + 16 * off, p[b].obs2, 16 * m);
-        std::memcpy(pin + o_w1 + 4 * off, p[b].inv_sigma2_1, 4 * m);
-        std::memcpy(pin + o_w2 + 4 * off, p[b].inv_sigma2_2, 4 * m);
+        io.put(i_p1, off, p[b].p1c, m);
+        io.put(i_p2, off, p[b].p2c, m);
+        io.put(i_o1, off, p[b].obs1, m);
+        io.put(i_o2, off, p[b].obs2, m);
+        io.put(i_w1, off, p[b].inv_sigma2_1, m);
+        io.put(i_w2, off, p[b].inv_sigma2_2, m);
     }
-    char *din = nullptr, *dio = nullptr;
-    OSG_ALLOC(ctx, din, SLOT_BA0, in_bytes);
-    OSG_ALLOC(ctx, dio, SLOT_BA1, io_bytes);
-    OSG_RC(osg_upload(ctx, din, pin, in_bytes));
-    hipEvent_t *ev = osg_ctx_events(ctx);
-    if (!ev) return osg_set_error(ctx, OSG_E_HIP, "event create failed");
-    OSG_HIP_CHECK(ctx, hipEventRecord(ev[0], ctx->stream));
-    hipLaunchKernelGGL(k_sim3_opt, dim3(nb), dim3(NT), 0, ctx->stream, (const S3ProbDev *)din,
-                       (const double *)(din + o_p1), (const double *)(din + o_p2), (const double *)(din + o_o1),
-                       (const double *)(din + o_o2), (const float *)(din + o_w1), (const float *)(din + o_w2),
-                       (uint8_t *)dio, (double *)(dio + o_chi), (S3Out *)(dio + o_res));
+    OSG_RC(io.upload());
+    OSG_RC(io.start());
+    hipLaunchKernelGGL(k_sim3_opt, dim3(nb), dim3(NT), 0, ctx->stream, io.dev_in<const S3ProbDev>(i_pr),
+                       io.dev_in<const double>(i_p1), io.dev_in<const double>(i_p2), io.dev_in<const double>(i_o1),
+                       io.dev_in<const double>(i_o2), io.dev_in<const float>(i_w1), io.dev_in<const float>(i_w2),
+                       io.dev_out<uint8_t>(o_st), io.dev_out<double>(o_chi), io.dev_out<S3Out>(o_res));
     OSG_HIP_CHECK(ctx, hipGetLastError());
-    OSG_HIP_CHECK(ctx, hipEventRecord(ev[1], ctx->stream));
-    char *pout = pin + in_bytes;
-    OSG_RC(osg_download(ctx, pout, dio, io_bytes));
-    OSG_RC(osg_wait(ctx));
-    float kms = 0.f;
-    OSG_HIP_CHECK(ctx, hipEventElapsedTime(&kms, ev[0], ev[1]));
-    ctx->last_kernel_ms = kms;
-    const S3Out *res = (const S3Out *)(pout + o_res);
+    OSG_RC(io.finish(io.out_bytes));
+    const S3Out *res = io.result<S3Out>(o_res);
     int sum = 0;
     for (int b = 0; b < nb; b++) {
         const S3Out &o = res[b];
@@ -585,11 +571,8 @@ int osg_optimize_sim3_batch(osg_ctx *ctx, const osg_sim3_problem *p, int32_t nb,
             r[b].lm_iterations[k] = o.lm_iterations[k];
             r[b].lm_trials[k] = o.lm_trials[k];
         }
-        const size_t off = hp[b].pair_off, m = p[b].n_pairs;
-        if (m) {
-            std::memcpy(r[b].pair_state, pout + off, m);
-            if (r[b].pair_chi2) std::memcpy(r[b].pair_chi2, pout + o_chi + 16 * off, 16 * m);
-        }
+        io.get(r[b].pair_state, o_st, hp[b].pair_off, p[b].n_pairs);
+        if (r[b].pair_chi2) io.get(r[b].pair_chi2, o_chi, hp[b].pair_off, p[b].n_pairs);
         sum += o.n_inliers;
     }
     return sum;

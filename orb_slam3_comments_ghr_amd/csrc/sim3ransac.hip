@@ -20,8 +20,8 @@
 #include <cstring>
 #include <vector>
 
-#include "glibc_math.h"
-#include "osg_internal.h"
+#include "batch_io.h"
+#include "ransac_common.h"
 #include "sim3ransac_select.h"
 
 namespace {
@@ -61,28 +61,6 @@ __device__ __forceinline__ float dot3(float a0, float a1, float a2, float b0, fl
     return sum3(a0 * b0, a1 * b1, a2 * b2);
 }
 
-// GeometricCamera::project(Eigen::Vector3f): ref:src/CameraModels/Pinhole.cpp:64-71,
-// ref:src/CameraModels/KannalaBrandt8.cpp:87-104
-__device__ __forceinline__ void project_f(const osg_camera &c, float x, float y, float z, float &u, float &v)
-{
-    if (c.type == OSG_CAM_KB8) {
-        const float x2_plus_y2 = x * x + y * y;
-        const float theta = osgm::atan2f_fd(sqrtf(x2_plus_y2), z);
-        const float psi = osgm::atan2f_fd(y, x);
-        const float theta2 = theta * theta;
-        const float theta3 = theta * theta2;
-        const float theta5 = theta3 * theta2;
-        const float theta7 = theta5 * theta2;
-        const float theta9 = theta7 * theta2;
-        const float r = theta + c.p[4] * theta3 + c.p[5] * theta5 + c.p[6] * theta7 + c.p[7] * theta9;
-        u = c.p[0] * r * cosf(psi) + c.p[2];
-        v = c.p[1] * r * sinf(psi) + c.p[3];
-    } else {
-        u = c.p[0] * x / z + c.p[2];
-        v = c.p[1] * y / z + c.p[3];
-    }
-}
-
 struct Hyp {
     float R[9], t[3], s;  // T12 = [sR | t]
     float A[9], a[3];     // s R, t
@@ -94,46 +72,8 @@ struct Hyp {
 __device__ inline void top_eigenvector(const double n[10], double q[4])
 {
     double A[4][4] = {{n[0], n[1], n[2], n[3]}, {n[1], n[4], n[5], n[6]}, {n[2], n[5], n[7], n[8]}, {n[3], n[6], n[8], n[9]}};
-    double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
-#pragma unroll 1
-    for (int sweep = 0; sweep < 16; sweep++) {
-        double off = 0, diag = 0;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            diag += A[i][i] * A[i][i];
-#pragma unroll
-            for (int j = i + 1; j < 4; j++) off += A[i][j] * A[i][j];
-        }
-        if (!(off > 1e-40 * diag)) break;  // converged, zero, or NaN
-#pragma unroll
-        for (int p = 0; p < 3; p++)
-#pragma unroll
-            for (int r = p + 1; r < 4; r++) {
-                const double apq = A[p][r];
-                if (apq == 0.0) continue;
-                const double th = (A[r][r] - A[p][p]) / (2.0 * apq);
-                const double tt = (th >= 0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));
-                const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const double akp = A[k][p], akq = A[k][r];
-                    A[k][p] = c * akp - s * akq;
-                    A[k][r] = s * akp + c * akq;
-                }
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const double apk = A[p][k], aqk = A[r][k];
-                    A[p][k] = c * apk - s * aqk;
-                    A[r][k] = s * apk + c * aqk;
-                }
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const double vkp = V[k][p], vkq = V[k][r];
-                    V[k][p] = c * vkp - s * vkq;
-                    V[k][r] = s * vkp + c * vkq;
-                }
-            }
-    }
+    double V[4][4];
+    jacobi_sym<4>(A, V, 16, 1e-40);  // stops when converged, zero, or NaN
     int top = 0;
     double best = A[0][0];
 #pragma unroll
@@ -374,9 +314,7 @@ __global__ __launch_bounds__(64) void k_s3r_select(const RProbDev *__restrict__ 
         o.T12[15] = 1.f;
     }
     hyp = __shfl(hyp, 0);
-    const unsigned long long *mask = masks + P.mask_off + (size_t)hyp * P.words;
-    uint8_t *dst = inlier + P.pt_off;
-    for (int i = lane; i < P.n; i += 64) dst[i] = (uint8_t)((mask[i >> 6] >> (i & 63)) & 1ull);
+    expand_mask(masks + P.mask_off + (size_t)hyp * P.words, P.n, inlier + P.pt_off, lane);
 }
 
 }  // namespace
@@ -405,13 +343,12 @@ int osg_sim3_ransac_batch(osg_ctx *ctx, const osg_sim3_ransac_problem *p, int32_
         OSG_REQUIRE(ctx, q.n == 0 || r[b].inlier, "inlier array");
         if (q.n == 0 || q.n < q.min_inliers) continue;
         OSG_REQUIRE(ctx, q.p1c && q.p2c && q.max_err1 && q.max_err2 && q.samples, "match arrays");
-        for (int h = 0; h < q.n_hyp; h++) {
-            const int32_t *s = q.samples + 3 * (size_t)h;
-            OSG_REQUIRE(ctx, s[0] >= 0 && s[0] < q.n && s[1] >= 0 && s[1] < q.n && s[2] >= 0 && s[2] < q.n,
-                        "sample index outside [0, n) in hypothesis %d of problem %d", h, b);
-            OSG_REQUIRE(ctx, s[0] != s[1] && s[0] != s[2] && s[1] != s[2],
-                        "repeated sample index in hypothesis %d of problem %d", h, b);
-        }
+        int h_bad = -1;
+        int why = check_sets(q.samples, 3, q.n_hyp, q.n, &h_bad);
+        for (int j = 0; why == 2 && j < 3; j++)  // a set with both faults reports the index outside
+            if (q.samples[3 * (size_t)h_bad + j] < 0 || q.samples[3 * (size_t)h_bad + j] >= q.n) why = 1;
+        OSG_REQUIRE(ctx, why != 1, "sample index outside [0, n) in hypothesis %d of problem %d", h_bad, b);
+        OSG_REQUIRE(ctx, why != 2, "repeated sample index in hypothesis %d of problem %d", h_bad, b);
         RProbDev d;
         std::memset(&d, 0, sizeof d);
         d.n = q.n;
@@ -455,56 +392,41 @@ int osg_sim3_ransac_batch(osg_ctx *ctx, const osg_sim3_ransac_problem *p, int32_
     if (na == 0) return 0;
     bool want_hyp = false;
     for (int k = 0; k < na; k++) want_hyp = want_hyp || r[src[k]].hyp_inliers || r[src[k]].hyp_sim3;
-    auto al = [](size_t v) { return (v + 255) & ~size_t(255); };
-    // in: probs | p1c | p2c | max1 | max2 | samples
-    const size_t i_p1 = al(sizeof(RProbDev) * na), i_p2 = i_p1 + al(12 * n_pts), i_m1 = i_p2 + al(12 * n_pts);
-    const size_t i_m2 = i_m1 + al(4 * n_pts), i_sm = i_m2 + al(4 * n_pts);
-    const size_t in_bytes = i_sm + al(12 * n_hyp);
-    // out: RSelOut | inlier bytes | counts | sim3  (the last two are downloaded on request)
-    const size_t o_in = al(sizeof(RSelOut) * na), o_cnt = o_in + al(n_pts), o_s3 = o_cnt + al(4 * n_hyp);
-    const size_t out_bytes = o_s3 + al(52 * n_hyp);
-    const size_t dl_bytes = want_hyp ? out_bytes : o_cnt;
-    char *pin = (char *)osg_pinned(ctx, in_bytes + out_bytes);
-    if (!pin) return osg_set_error(ctx, OSG_E_NOMEM, "pinned alloc failed");
-    OSG_RC(osg_idle(ctx));  // the pinned block may still be in use
-    std::memcpy(pin, hp.data(), sizeof(RProbDev) * na);
+    osg_batch_io io(ctx);
+    const osg_seg i_pr = io.in(sizeof(RProbDev), na), i_p1 = io.in(3 * sizeof(float), n_pts), i_p2 = io.in(3 * sizeof(float), n_pts);
+    const osg_seg i_m1 = io.in(sizeof(float), n_pts), i_m2 = io.in(sizeof(float), n_pts), i_sm = io.in(3 * sizeof(int32_t), n_hyp);
+    // the counts and the Sim3s are downloaded on request
+    const osg_seg o_res = io.out(sizeof(RSelOut), na), o_in = io.out(1, n_pts), o_cnt = io.out(sizeof(int32_t), n_hyp);
+    const osg_seg o_s3 = io.out(13 * sizeof(float), n_hyp);
+    const size_t dl_bytes = want_hyp ? io.out_bytes : o_cnt.off;
+    OSG_RC(io.stage());
+    io.put(i_pr, 0, hp.data(), na);
     for (int k = 0; k < na; k++) {
         const osg_sim3_ransac_problem &q = p[src[k]];
-        const size_t off = hp[k].pt_off, m = q.n;
-        std::memcpy(pin + i_p1 + 12 * off, q.p1c, 12 * m);
-        std::memcpy(pin + i_p2 + 12 * off, q.p2c, 12 * m);
-        std::memcpy(pin + i_m1 + 4 * off, q.max_err1, 4 * m);
-        std::memcpy(pin + i_m2 + 4 * off, q.max_err2, 4 * m);
-        std::memcpy(pin + i_sm + 12 * (size_t)hp[k].hyp_off, q.samples, 12 * (size_t)q.n_hyp);
+        io.put(i_p1, hp[k].pt_off, q.p1c, q.n);
+        io.put(i_p2, hp[k].pt_off, q.p2c, q.n);
+        io.put(i_m1, hp[k].pt_off, q.max_err1, q.n);
+        io.put(i_m2, hp[k].pt_off, q.max_err2, q.n);
+        io.put(i_sm, hp[k].hyp_off, q.samples, q.n_hyp);
     }
-    char *din = nullptr, *dout = nullptr;
+    OSG_RC(io.upload());
     unsigned long long *dmask = nullptr;
-    OSG_ALLOC(ctx, din, SLOT_BA0, in_bytes);
-    OSG_ALLOC(ctx, dout, SLOT_BA1, out_bytes);
     OSG_ALLOC(ctx, dmask, SLOT_BA2, 8 * n_words);
-    OSG_RC(osg_upload(ctx, din, pin, in_bytes));
     if (lds > 48 * 1024)
         OSG_HIP_CHECK(ctx, hipFuncSetAttribute((const void *)k_s3r_eval, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipEvent_t *ev = osg_ctx_events(ctx);
-    if (!ev) return osg_set_error(ctx, OSG_E_HIP, "event create failed");
-    OSG_HIP_CHECK(ctx, hipEventRecord(ev[0], ctx->stream));
-    hipLaunchKernelGGL(k_s3r_eval, dim3((max_hyp + HPB - 1) / HPB, na), dim3(NT), lds, ctx->stream,
-                       (const RProbDev *)din, (const float *)(din + i_p1), (const float *)(din + i_p2),
-                       (const float *)(din + i_m1), (const float *)(din + i_m2), (const int *)(din + i_sm),
-                       (int *)(dout + o_cnt), (float *)(dout + o_s3), dmask);
+    OSG_RC(io.start());
+    const RProbDev *dp = io.dev_in<const RProbDev>(i_pr);
+    hipLaunchKernelGGL(k_s3r_eval, dim3((max_hyp + HPB - 1) / HPB, na), dim3(NT), lds, ctx->stream, dp,
+                       io.dev_in<const float>(i_p1), io.dev_in<const float>(i_p2), io.dev_in<const float>(i_m1),
+                       io.dev_in<const float>(i_m2), io.dev_in<const int>(i_sm), io.dev_out<int>(o_cnt),
+                       io.dev_out<float>(o_s3), dmask);
     OSG_HIP_CHECK(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_s3r_select, dim3(na), dim3(64), 0, ctx->stream, (const RProbDev *)din,
-                       (const int *)(dout + o_cnt), (const float *)(dout + o_s3), (const unsigned long long *)dmask,
-                       (RSelOut *)dout, (uint8_t *)(dout + o_in));
+    hipLaunchKernelGGL(k_s3r_select, dim3(na), dim3(64), 0, ctx->stream, dp, io.dev_out<const int>(o_cnt),
+                       io.dev_out<const float>(o_s3), (const unsigned long long *)dmask, io.dev_out<RSelOut>(o_res),
+                       io.dev_out<uint8_t>(o_in));
     OSG_HIP_CHECK(ctx, hipGetLastError());
-    OSG_HIP_CHECK(ctx, hipEventRecord(ev[1], ctx->stream));
-    char *pout = pin + in_bytes;
-    OSG_RC(osg_download(ctx, pout, dout, dl_bytes));
-    OSG_RC(osg_wait(ctx));
-    float kms = 0.f;
-    OSG_HIP_CHECK(ctx, hipEventElapsedTime(&kms, ev[0], ev[1]));
-    ctx->last_kernel_ms = kms;
-    const RSelOut *res = (const RSelOut *)pout;
+    OSG_RC(io.finish(dl_bytes));
+    const RSelOut *res = io.result<RSelOut>(o_res);
     int conv = 0;
     for (int k = 0; k < na; k++) {
         const RSelOut &s = res[k];
@@ -518,9 +440,9 @@ int osg_sim3_ransac_batch(osg_ctx *ctx, const osg_sim3_ransac_problem *p, int32_
         std::memcpy(o.t, s.t, sizeof o.t);
         o.s = s.s;
         std::memcpy(o.T12, s.T12, sizeof o.T12);
-        std::memcpy(o.inlier, pout + o_in + hp[k].pt_off, (size_t)hp[k].n);
-        if (o.hyp_inliers) std::memcpy(o.hyp_inliers, pout + o_cnt + 4 * (size_t)hp[k].hyp_off, 4 * (size_t)hp[k].n_hyp);
-        if (o.hyp_sim3) std::memcpy(o.hyp_sim3, pout + o_s3 + 52 * (size_t)hp[k].hyp_off, 52 * (size_t)hp[k].n_hyp);
+        io.get(o.inlier, o_in, hp[k].pt_off, hp[k].n);
+        if (o.hyp_inliers) io.get(o.hyp_inliers, o_cnt, hp[k].hyp_off, hp[k].n_hyp);
+        if (o.hyp_sim3) io.get(o.hyp_sim3, o_s3, hp[k].hyp_off, hp[k].n_hyp);
         conv += s.converged ? 1 : 0;
     }
     return conv;

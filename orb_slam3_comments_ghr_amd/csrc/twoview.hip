@@ -31,7 +31,8 @@
 #include <cstring>
 #include <vector>
 
-#include "osg_internal.h"
+#include "batch_io.h"
+#include "ransac_common.h"
 #include "twoview_select.h"
 
 namespace {
@@ -57,55 +58,9 @@ struct TOut {
 };
 
 // ---- small dense algebra -------------------------------------------------------------------------
-// cyclic Jacobi on the symmetric N x N matrix A (registers, fully unrolled): A -> diagonal, V -> eigenvectors
-// in columns.  A matrix with a NaN stops at once.
-template <int N>
-__device__ inline void jacobi_sym(double (&A)[N][N], double (&V)[N][N])
-{
-#pragma unroll
-    for (int i = 0; i < N; i++)
-#pragma unroll
-        for (int j = 0; j < N; j++) V[i][j] = i == j ? 1.0 : 0.0;
-#pragma unroll 1
-    for (int sweep = 0; sweep < 24; sweep++) {
-        double off = 0, diag = 0;
-#pragma unroll
-        for (int i = 0; i < N; i++) {
-            diag += A[i][i] * A[i][i];
-#pragma unroll
-            for (int j = i + 1; j < N; j++) off += A[i][j] * A[i][j];
-        }
-        if (!(off > 1e-34 * diag)) break;
-#pragma unroll
-        for (int p = 0; p < N - 1; p++)
-#pragma unroll
-            for (int r = p + 1; r < N; r++) {
-                const double apq = A[p][r];
-                if (apq == 0.0) continue;
-                const double th = (A[r][r] - A[p][p]) / (2.0 * apq);
-                const double tt = (th >= 0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));
-                const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
-#pragma unroll
-                for (int k = 0; k < N; k++) {
-                    const double akp = A[k][p], akq = A[k][r];
-                    A[k][p] = c * akp - s * akq;
-                    A[k][r] = s * akp + c * akq;
-                }
-#pragma unroll
-                for (int k = 0; k < N; k++) {
-                    const double apk = A[p][k], aqk = A[r][k];
-                    A[p][k] = c * apk - s * aqk;
-                    A[r][k] = s * apk + c * aqk;
-                }
-#pragma unroll
-                for (int k = 0; k < N; k++) {
-                    const double vkp = V[k][p], vkq = V[k][r];
-                    V[k][p] = c * vkp - s * vkq;
-                    V[k][r] = s * vkp + c * vkq;
-                }
-            }
-    }
-}
+// the register Jacobi (ransac_common.h) with this module's sweep limit and convergence constant
+constexpr int JS_SWEEPS = 24;
+constexpr double JS_TOL = 1e-34;
 
 __device__ __forceinline__ void mul3(const float *a, const float *b, float *c)
 {
@@ -147,7 +102,7 @@ __device__ inline void svd3(const float *M, float *U, float *w, float *V)
 #pragma unroll
         for (int j = 0; j < 3; j++)
             G[i][j] = (double)M[i] * M[j] + (double)M[3 + i] * M[3 + j] + (double)M[6 + i] * M[6 + j];
-    jacobi_sym<3>(G, E);
+    jacobi_sym<3>(G, E, JS_SWEEPS, JS_TOL);
     int o0 = 0, o1 = 1, o2 = 2;
     double l0 = G[0][0], l1 = G[1][1], l2 = G[2][2];
     if (l1 > l0) { double x = l0; l0 = l1; l1 = x; int y = o0; o0 = o1; o1 = y; }
@@ -283,12 +238,7 @@ __global__ __launch_bounds__(NT) void k_tvr_eval(const TProbDev *__restrict__ pr
             if (tid < 4) {
                 const double spq = S[p][q];
                 double c = 1.0, s = 0.0;
-                if (spq != 0.0) {
-                    const double th = (S[q][q] - S[p][p]) / (2.0 * spq);
-                    const double tt = (th >= 0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));
-                    c = 1.0 / sqrt(tt * tt + 1.0);
-                    s = tt * c;
-                }
+                if (spq != 0.0) jacobi_rotation(S[p][p], S[q][q], spq, c, s);
                 cs[tid][0] = c, cs[tid][1] = s;
             }
             __syncthreads();
@@ -334,7 +284,7 @@ __global__ __launch_bounds__(NT) void k_tvr_eval(const TProbDev *__restrict__ pr
 #pragma unroll
             for (int j = 0; j < 3; j++)
                 G[i][j] = (double)Mn[i] * Mn[j] + (double)Mn[3 + i] * Mn[3 + j] + (double)Mn[6 + i] * Mn[6 + j];
-        jacobi_sym<3>(G, E);
+        jacobi_sym<3>(G, E, JS_SWEEPS, JS_TOL);
         int e = 0;
         double lm = G[0][0];
         if (G[1][1] < lm) lm = G[1][1], e = 1;
@@ -551,14 +501,9 @@ __global__ __launch_bounds__(64) void k_tvr_select(const TProbDev *__restrict__ 
     const int hh = sh[0], hf = sh[1], model = sh[2];
     const unsigned long long *mh = masks + P.mask_off + (size_t)(hh < 0 ? 0 : hh) * P.words;
     const unsigned long long *mf = masks + P.mask_off + ((size_t)P.n_hyp + (hf < 0 ? 0 : hf)) * P.words;
-    int cnt = 0;
-    for (int i = lane; i < P.n; i += 64) {
-        const uint8_t bh = hh < 0 ? 0 : (uint8_t)((mh[i >> 6] >> (i & 63)) & 1ull);
-        const uint8_t bf = hf < 0 ? 0 : (uint8_t)((mf[i >> 6] >> (i & 63)) & 1ull);
-        inl_h[P.pt_off + i] = bh;
-        inl_f[P.pt_off + i] = bf;
-        cnt += model == 0 ? bh : model == 1 ? bf : 0;
-    }
+    const int ch = expand_mask(hh < 0 ? nullptr : mh, P.n, inl_h + P.pt_off, lane);
+    const int cf = expand_mask(hf < 0 ? nullptr : mf, P.n, inl_f + P.pt_off, lane);
+    int cnt = model == 0 ? ch : model == 1 ? cf : 0;
     for (int d = 32; d > 0; d >>= 1) cnt += __shfl_xor(cnt, d);
     if (lane == 0) o.n_inliers = cnt;
 }
@@ -634,7 +579,7 @@ __global__ __launch_bounds__(NT) void k_tvr_checkrt(const TProbDev *__restrict__
 #pragma unroll
                 for (int b = 0; b < 4; b++)
                     G[a][b] = (double)A[0][a] * A[0][b] + (double)A[1][a] * A[1][b] + (double)A[2][a] * A[2][b] + (double)A[3][a] * A[3][b];
-            jacobi_sym<4>(G, E);
+            jacobi_sym<4>(G, E, JS_SWEEPS, JS_TOL);
             int e = 0;
             double lm = G[0][0];
 #pragma unroll
@@ -788,14 +733,10 @@ int osg_two_view_reconstruct_batch(osg_ctx *ctx, const osg_two_view_problem *p, 
                         "idx1 not strictly increasing in [0, n_keys1) at match %d of problem %d", i, b);
             OSG_REQUIRE(ctx, q.idx2[i] >= 0 && q.idx2[i] < q.n_keys2, "idx2 outside [0, n_keys2) at match %d of problem %d", i, b);
         }
-        for (int h = 0; h < q.n_hyp; h++) {
-            const int32_t *s = q.sets + 8 * (size_t)h;
-            for (int j = 0; j < 8; j++) {
-                OSG_REQUIRE(ctx, s[j] >= 0 && s[j] < q.n, "set index outside [0, n) in hypothesis %d of problem %d", h, b);
-                for (int k = 0; k < j; k++)
-                    OSG_REQUIRE(ctx, s[j] != s[k], "repeated set index in hypothesis %d of problem %d", h, b);
-            }
-        }
+        int h_bad = -1;
+        const int why = check_sets(q.sets, 8, q.n_hyp, q.n, &h_bad);
+        OSG_REQUIRE(ctx, why != 1, "set index outside [0, n) in hypothesis %d of problem %d", h_bad, b);
+        OSG_REQUIRE(ctx, why != 2, "repeated set index in hypothesis %d of problem %d", h_bad, b);
         TProbDev d;
         std::memset(&d, 0, sizeof d);
         d.n = q.n, d.n_hyp = q.n_hyp, d.n_keys1 = q.n_keys1, d.n_keys2 = q.n_keys2;
@@ -815,6 +756,13 @@ int osg_two_view_reconstruct_batch(osg_ctx *ctx, const osg_two_view_problem *p, 
     }
     const int na = (int)hp.size();
     OSG_REQUIRE(ctx, na <= 65535, "too many problems in one batch");
+    osg_batch_io io(ctx);
+    // kp: a float4 (kp1, kp2) per match
+    const osg_seg i_pr = io.in(sizeof(TProbDev), na), i_kp = io.in(sizeof(float4), n_pts), i_k1 = io.in(2 * sizeof(float), n_k1);
+    const osg_seg i_k2 = io.in(2 * sizeof(float), n_k2), i_ix = io.in(sizeof(int32_t), n_pts), i_st = io.in(8 * sizeof(int32_t), n_hyp);
+    // the scores (an H, F pair per hypothesis) and the models are downloaded on request
+    const osg_seg o_res = io.out(sizeof(TOut), na), o_ih = io.out(1, n_pts), o_if = io.out(1, n_pts), o_tr = io.out(1, n_k1);
+    const osg_seg o_p3 = io.out(3 * sizeof(float), n_k1), o_sc = io.out(2 * sizeof(float), n_hyp), o_md = io.out(18 * sizeof(float), n_hyp);
     // every problem starts as one that evaluates nothing
     for (int b = 0; b < nb; b++) {
         osg_two_view_result &o = r[b];
@@ -824,96 +772,79 @@ int osg_two_view_reconstruct_batch(osg_ctx *ctx, const osg_two_view_problem *p, 
         o.t[0] = o.t[1] = o.t[2] = 0.f;
         for (int j = 0; j < 8; j++) o.n_good[j] = 0, o.parallax[j] = 0.f;
         std::memset(o.cand_Rt, 0, sizeof o.cand_Rt);
-        if (q.n_keys1 > 0) std::memset(o.p3d, 0, 12 * (size_t)q.n_keys1), std::memset(o.triangulated, 0, (size_t)q.n_keys1);
+        if (q.n_keys1 > 0) std::memset(o.p3d, 0, o_p3.elem * q.n_keys1), std::memset(o.triangulated, 0, (size_t)q.n_keys1);
         if (q.n > 0) std::memset(o.inlier_h, 0, (size_t)q.n), std::memset(o.inlier_f, 0, (size_t)q.n);
-        if (o.hyp_score_h) std::memset(o.hyp_score_h, 0, 4 * (size_t)q.n_hyp);
-        if (o.hyp_score_f) std::memset(o.hyp_score_f, 0, 4 * (size_t)q.n_hyp);
-        if (o.hyp_models) std::memset(o.hyp_models, 0, 72 * (size_t)q.n_hyp);
+        if (o.hyp_score_h) std::memset(o.hyp_score_h, 0, o_sc.elem / 2 * q.n_hyp);
+        if (o.hyp_score_f) std::memset(o.hyp_score_f, 0, o_sc.elem / 2 * q.n_hyp);
+        if (o.hyp_models) std::memset(o.hyp_models, 0, o_md.elem * q.n_hyp);
     }
     if (na == 0) return 0;
     bool want_hyp = false;
     for (int k = 0; k < na; k++) want_hyp = want_hyp || r[src[k]].hyp_score_h || r[src[k]].hyp_score_f || r[src[k]].hyp_models;
-    auto al = [](size_t v) { return (v + 255) & ~size_t(255); };
-    // in: probs | kp (float4 per match) | keys1 | keys2 | idx1 | sets
-    const size_t i_kp = al(sizeof(TProbDev) * na), i_k1 = i_kp + al(16 * n_pts), i_k2 = i_k1 + al(8 * n_k1);
-    const size_t i_ix = i_k2 + al(8 * n_k2), i_st = i_ix + al(4 * n_pts);
-    const size_t in_bytes = i_st + al(32 * n_hyp);
-    // out: TOut | inlier_h | inlier_f | triangulated | p3d | scores | models  (the last two on request)
-    const size_t o_ih = al(sizeof(TOut) * na), o_if = o_ih + al(n_pts), o_tr = o_if + al(n_pts), o_p3 = o_tr + al(n_k1);
-    const size_t o_sc = o_p3 + al(12 * n_k1), o_md = o_sc + al(8 * n_hyp);
-    const size_t out_bytes = o_md + al(72 * n_hyp);
-    const size_t dl_bytes = want_hyp ? out_bytes : o_sc;
+    const size_t dl_bytes = want_hyp ? io.out_bytes : o_sc.off;
     // work: norm | p3d of 8 candidates | cos keys | flags
-    const size_t w_p3 = al(32 * (size_t)na), w_cs = w_p3 + al(96 * n_pts), w_fl = w_cs + al(32 * n_pts);
-    const size_t work_bytes = w_fl + al(8 * n_pts);
-    char *pin = (char *)osg_pinned(ctx, in_bytes + out_bytes);
-    if (!pin) return osg_set_error(ctx, OSG_E_NOMEM, "pinned alloc failed");
-    OSG_RC(osg_idle(ctx));  // the pinned block may still be in use
-    std::memcpy(pin, hp.data(), sizeof(TProbDev) * na);
+    size_t work_bytes = 0;
+    osg_seg_add(work_bytes, 8 * sizeof(float), na);
+    const size_t w_p3 = osg_seg_add(work_bytes, 8 * 3 * sizeof(float), n_pts).off;
+    const size_t w_cs = osg_seg_add(work_bytes, 8 * sizeof(unsigned), n_pts).off;
+    const size_t w_fl = osg_seg_add(work_bytes, 8, n_pts).off;
+    OSG_RC(io.stage());
+    io.put(i_pr, 0, hp.data(), na);
     for (int k = 0; k < na; k++) {
         const osg_two_view_problem &q = p[src[k]];
-        float *kp = (float *)(pin + i_kp) + 4 * (size_t)hp[k].pt_off;
+        float *kp = io.host_in<float>(i_kp, hp[k].pt_off);
         for (int i = 0; i < q.n; i++) {
             kp[4 * i] = q.kp1[2 * i], kp[4 * i + 1] = q.kp1[2 * i + 1];
             kp[4 * i + 2] = q.kp2[2 * i], kp[4 * i + 3] = q.kp2[2 * i + 1];
         }
-        std::memcpy(pin + i_k1 + 8 * (size_t)hp[k].key1_off, q.keys1, 8 * (size_t)q.n_keys1);
-        std::memcpy(pin + i_k2 + 8 * (size_t)hp[k].key2_off, q.keys2, 8 * (size_t)q.n_keys2);
-        std::memcpy(pin + i_ix + 4 * (size_t)hp[k].pt_off, q.idx1, 4 * (size_t)q.n);
-        std::memcpy(pin + i_st + 32 * (size_t)hp[k].hyp_off, q.sets, 32 * (size_t)q.n_hyp);
+        io.put(i_k1, hp[k].key1_off, q.keys1, q.n_keys1);
+        io.put(i_k2, hp[k].key2_off, q.keys2, q.n_keys2);
+        io.put(i_ix, hp[k].pt_off, q.idx1, q.n);
+        io.put(i_st, hp[k].hyp_off, q.sets, q.n_hyp);
     }
-    char *din = nullptr, *dout = nullptr, *dwork = nullptr;
+    OSG_RC(io.upload());
+    char *dwork = nullptr;
     unsigned long long *dmask = nullptr;
-    OSG_ALLOC(ctx, din, SLOT_BA0, in_bytes);
-    OSG_ALLOC(ctx, dout, SLOT_BA1, out_bytes);
     OSG_ALLOC(ctx, dmask, SLOT_BA2, 8 * n_words);
     OSG_ALLOC(ctx, dwork, SLOT_BA3, work_bytes);
-    OSG_RC(osg_upload(ctx, din, pin, in_bytes));
-    hipEvent_t *ev = osg_ctx_events(ctx);
-    if (!ev) return osg_set_error(ctx, OSG_E_HIP, "event create failed");
-    OSG_HIP_CHECK(ctx, hipEventRecord(ev[0], ctx->stream));
+    OSG_RC(io.start());
+    hipEvent_t *ev = io.ev;
     KernelEvents kevs;  // between the five launches, on request; destroyed on every way out
     hipEvent_t(&kev)[4] = kevs.e;
     const bool ktime = tv_ktime;
     if (ktime)
         for (auto &e : kev) OSG_HIP_CHECK(ctx, hipEventCreate(&e));
-    const TProbDev *dp = (const TProbDev *)din;
-    const float4 *dkp = (const float4 *)(din + i_kp);
-    TOut *dres = (TOut *)dout;
-    hipLaunchKernelGGL(k_tvr_norm, dim3(2, na), dim3(NT), 0, ctx->stream, dp, (const float *)(din + i_k1),
-                       (const float *)(din + i_k2), (float *)dwork);
+    const TProbDev *dp = io.dev_in<const TProbDev>(i_pr);
+    const float4 *dkp = io.dev_in<const float4>(i_kp);
+    TOut *dres = io.dev_out<TOut>(o_res);
+    hipLaunchKernelGGL(k_tvr_norm, dim3(2, na), dim3(NT), 0, ctx->stream, dp, io.dev_in<const float>(i_k1),
+                       io.dev_in<const float>(i_k2), (float *)dwork);
     OSG_HIP_CHECK(ctx, hipGetLastError());
     if (ktime) OSG_HIP_CHECK(ctx, hipEventRecord(kev[0], ctx->stream));
-    hipLaunchKernelGGL(k_tvr_eval, dim3(max_hyp, 2, na), dim3(NT), 0, ctx->stream, dp, dkp, (const int *)(din + i_st),
-                       (const float *)dwork, (float *)(dout + o_sc), (float *)(dout + o_md), dmask);
+    hipLaunchKernelGGL(k_tvr_eval, dim3(max_hyp, 2, na), dim3(NT), 0, ctx->stream, dp, dkp, io.dev_in<const int>(i_st),
+                       (const float *)dwork, io.dev_out<float>(o_sc), io.dev_out<float>(o_md), dmask);
     OSG_HIP_CHECK(ctx, hipGetLastError());
     if (ktime) OSG_HIP_CHECK(ctx, hipEventRecord(kev[1], ctx->stream));
-    hipLaunchKernelGGL(k_tvr_select, dim3(na), dim3(64), 0, ctx->stream, dp, (const float *)(dout + o_sc),
-                       (const float *)(dout + o_md), (const unsigned long long *)dmask, dres, (uint8_t *)(dout + o_ih),
-                       (uint8_t *)(dout + o_if));
+    hipLaunchKernelGGL(k_tvr_select, dim3(na), dim3(64), 0, ctx->stream, dp, io.dev_out<const float>(o_sc),
+                       io.dev_out<const float>(o_md), (const unsigned long long *)dmask, dres, io.dev_out<uint8_t>(o_ih),
+                       io.dev_out<uint8_t>(o_if));
     OSG_HIP_CHECK(ctx, hipGetLastError());
     if (ktime) OSG_HIP_CHECK(ctx, hipEventRecord(kev[2], ctx->stream));
-    hipLaunchKernelGGL(k_tvr_checkrt, dim3(8, na), dim3(NT), 0, ctx->stream, dp, dkp, (const uint8_t *)(dout + o_ih),
-                       (const uint8_t *)(dout + o_if), dres, (float *)(dwork + w_p3), (unsigned *)(dwork + w_cs),
+    hipLaunchKernelGGL(k_tvr_checkrt, dim3(8, na), dim3(NT), 0, ctx->stream, dp, dkp, io.dev_out<const uint8_t>(o_ih),
+                       io.dev_out<const uint8_t>(o_if), dres, (float *)(dwork + w_p3), (unsigned *)(dwork + w_cs),
                        (uint8_t *)(dwork + w_fl));
     OSG_HIP_CHECK(ctx, hipGetLastError());
     if (ktime) OSG_HIP_CHECK(ctx, hipEventRecord(kev[3], ctx->stream));
-    hipLaunchKernelGGL(k_tvr_final, dim3(na), dim3(NT), 0, ctx->stream, dp, dres, (const int *)(din + i_ix),
-                       (const float *)(dwork + w_p3), (const uint8_t *)(dwork + w_fl), (float *)(dout + o_p3),
-                       (uint8_t *)(dout + o_tr));
+    hipLaunchKernelGGL(k_tvr_final, dim3(na), dim3(NT), 0, ctx->stream, dp, dres, io.dev_in<const int>(i_ix),
+                       (const float *)(dwork + w_p3), (const uint8_t *)(dwork + w_fl), io.dev_out<float>(o_p3),
+                       io.dev_out<uint8_t>(o_tr));
     OSG_HIP_CHECK(ctx, hipGetLastError());
-    OSG_HIP_CHECK(ctx, hipEventRecord(ev[1], ctx->stream));
-    char *pout = pin + in_bytes;
-    OSG_RC(osg_download(ctx, pout, dout, dl_bytes));
-    OSG_RC(osg_wait(ctx));
-    float kms = 0.f;
-    OSG_HIP_CHECK(ctx, hipEventElapsedTime(&kms, ev[0], ev[1]));
-    ctx->last_kernel_ms = kms;
+    OSG_RC(io.finish(dl_bytes));
     if (ktime) {
         const hipEvent_t seq[6] = {ev[0], kev[0], kev[1], kev[2], kev[3], ev[1]};
         for (int k = 0; k < 5; k++) OSG_HIP_CHECK(ctx, hipEventElapsedTime(&tv_kms[k], seq[k], seq[k + 1]));
     }
-    const TOut *res = (const TOut *)pout;
+    const TOut *res = io.result<TOut>(o_res);
     int n_ok = 0;
     for (int k = 0; k < na; k++) {
         const TOut &s = res[k];
@@ -928,12 +859,12 @@ int osg_two_view_reconstruct_batch(osg_ctx *ctx, const osg_two_view_problem *p, 
         std::memcpy(o.n_good, s.n_good, sizeof o.n_good);
         std::memcpy(o.parallax, s.parallax, sizeof o.parallax);
         std::memcpy(o.cand_Rt, s.cand_Rt, sizeof o.cand_Rt);
-        std::memcpy(o.inlier_h, pout + o_ih + d.pt_off, (size_t)d.n);
-        std::memcpy(o.inlier_f, pout + o_if + d.pt_off, (size_t)d.n);
-        std::memcpy(o.triangulated, pout + o_tr + d.key1_off, (size_t)d.n_keys1);
-        std::memcpy(o.p3d, pout + o_p3 + 12 * (size_t)d.key1_off, 12 * (size_t)d.n_keys1);
-        if (o.hyp_models) std::memcpy(o.hyp_models, pout + o_md + 72 * (size_t)d.hyp_off, 72 * (size_t)d.n_hyp);
-        const float *sc = (const float *)(pout + o_sc) + 2 * (size_t)d.hyp_off;
+        io.get(o.inlier_h, o_ih, d.pt_off, d.n);
+        io.get(o.inlier_f, o_if, d.pt_off, d.n);
+        io.get(o.triangulated, o_tr, d.key1_off, d.n_keys1);
+        io.get(o.p3d, o_p3, d.key1_off, d.n_keys1);
+        if (o.hyp_models) io.get(o.hyp_models, o_md, d.hyp_off, d.n_hyp);
+        const float *sc = io.result<float>(o_sc, d.hyp_off);
         for (int h = 0; h < d.n_hyp && (o.hyp_score_h || o.hyp_score_f); h++) {
             if (o.hyp_score_h) o.hyp_score_h[h] = sc[2 * h];
             if (o.hyp_score_f) o.hyp_score_f[h] = sc[2 * h + 1];
