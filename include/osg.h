@@ -634,6 +634,33 @@ void osg_debug_gaussian_kernel7(int32_t *k7);
  * stereo-partner write by a MapPoint without observations unblocked a slot), out[3] nmatches.
  * No reference counterpart. */
 int osg_match_last_stats(osg_ctx *ctx, int32_t *out4);
+/* Diagnostics: which code path the last search call on this context took (the five search
+ * operators above and their batched forms launch k_match; one launch per call).
+ *   out[0] grid-staging level of the launch: 2 the grids, the per-entry keypoint records and the
+ *          descriptors in LDS, 1 the grids and records, 0 the grids read from global memory
+ *          (SearchByBoW always); -1 when the last call that wrote osg_match_last_stats was not a
+ *          k_match call (SearchForInitialization, SearchByProjection with a Sim3) or failed
+ *   out[1] dynamic LDS bytes of the launch
+ *   out[2] problems whose serial redo (osg_match_last_stats out[2]) ran the 64-lane speculative
+ *          walk on LDS copies of its inputs
+ *   out[3] problems whose serial redo ran the one-thread walk (the launch was not staged, or the
+ *          walk's inputs exceed the LDS the launch left past the problem's resolve arrays)
+ *   out[4] 1 when the k_grid_* prepass formed the candidate lists (OSG_MATCH_PREPASS = 0 / 1 pins it;
+ *          by default launches of up to 64 problems take it)
+ *   out[5] the LDS per workgroup the device reports (hipDeviceProp_t::sharedMemPerBlock)
+ *   out[6] problems in the launch, out[7] 0.
+ * No reference counterpart. */
+int osg_match_last_path(osg_ctx *ctx, int32_t *out8);
+/* Diagnostics (host only: no context, no GPU): the staging level (as out[0] above) and the dynamic
+ * LDS bytes k_match takes for one grid-mode problem of n_slots keypoints (two_cam: Frame::Nleft !=
+ * -1) on a device of lds_per_block bytes of LDS per workgroup: the highest level <= stage_cap (the
+ * OSG_MATCH_STAGE environment variable, read per call; default 2) whose layout fits lds_per_block
+ * less 8 KiB.  A batched launch takes the lowest level over its problems and the largest LDS size at
+ * that level.  Returns OSG_E_INVALID for n_slots outside [0, 8192] and OSG_E_UNSUPPORTED when even
+ * level 0 does not fit: the search calls reject such a frame the same way (a device reporting 64 KiB
+ * holds 4096 keypoints at most; one reporting 160 KiB holds all 8192). */
+int osg_debug_match_plan(int32_t lds_per_block, int32_t stage_cap, int32_t n_slots, int32_t two_cam, int32_t *stage,
+                         int64_t *lds_bytes);
 /* Device time (HIP events around the launch, ms) of the last matching or pose-optimization kernel
  * this context ran: the search calls and osg_pose_optimization[_batch]. */
 int osg_ctx_last_kernel_ms(osg_ctx *ctx, double *ms);

@@ -150,6 +150,17 @@ class Context:
         return dict(candidates=int(out[0]), rounds=int(out[1]), serial=bool(out[2]), nmatches=int(out[3]),
                     kernel_ms=self.last_kernel_ms())
 
+    def match_last_path(self) -> dict:
+        """The code path of the last search call: ``stage`` (grid-staging level of the k_match launch,
+        -1 when the last call was not one), ``lds_bytes`` (its dynamic LDS), ``walk_lds`` /
+        ``walk_thread`` (problems whose serial redo ran the speculative LDS walk / the one-thread
+        walk), ``prepass`` (the k_grid_* prepass ran), ``lds_per_block`` (as the device reports it)
+        and ``problems`` (in the launch)."""
+        out = np.zeros(8, np.int32)
+        self.check(self.lib.osg_match_last_path(self.handle, _ptr(out)), "osg_match_last_path")
+        return dict(stage=int(out[0]), lds_bytes=int(out[1]), walk_lds=int(out[2]), walk_thread=int(out[3]),
+                    prepass=bool(out[4]), lds_per_block=int(out[5]), problems=int(out[6]))
+
     def last_kernel_ms(self) -> float:
         """Device time of the last matching / pose-optimization kernel (HIP events), ms."""
         ms = np.zeros(1, np.float64)
@@ -179,6 +190,19 @@ def descriptor_distance(a: np.ndarray, b: np.ndarray) -> int:
     a = np.ascontiguousarray(a, dtype=np.uint8).reshape(32)
     b = np.ascontiguousarray(b, dtype=np.uint8).reshape(32)
     return int(lib.osg_descriptor_distance(_ptr(a), _ptr(b)))
+
+
+def match_plan(lds_per_block: int, stage_cap: int, n_slots: int, two_cam: bool) -> tuple[int, int]:
+    """(staging level, dynamic LDS bytes) of a grid-mode k_match problem (osg_debug_match_plan; host
+    only).  Raises OsgError when the frame is out of range or does not fit the device's LDS."""
+    lib = load_library()
+    stage, lds = C.c_int32(-1), C.c_int64(-1)
+    rc = lib.osg_debug_match_plan(int(lds_per_block), int(stage_cap), int(n_slots), int(bool(two_cam)),
+                                  C.byref(stage), C.byref(lds))
+    if rc < 0:
+        raise OsgError(f"osg_debug_match_plan({lds_per_block}, {stage_cap}, {n_slots}, {two_cam}): "
+                       f"{lib.osg_strerror(rc).decode()}")
+    return int(stage.value), int(lds.value)
 
 
 def __getattr__(name):

@@ -291,7 +291,7 @@ EXPORTS = [
     "osg_search_by_projection_kf", "osg_search_by_bow_kf_f", "osg_search_by_bow_kf_kf",
     "osg_search_by_projection_mps_batch", "osg_search_by_projection_last_batch",
     "osg_search_by_projection_kf_batch", "osg_search_by_bow_kf_f_batch", "osg_search_by_bow_kf_kf_batch",
-    "osg_match_last_stats", "osg_ctx_last_kernel_ms", "osg_ctx_device_bytes", "osg_pose_optimization", "osg_pose_optimization_batch",
+    "osg_match_last_stats", "osg_match_last_path", "osg_debug_match_plan", "osg_ctx_last_kernel_ms", "osg_ctx_device_bytes", "osg_pose_optimization", "osg_pose_optimization_batch",
     "osg_local_bundle_adjustment", "osg_local_bundle_adjustment_batch", "osg_bundle_adjustment",
     "osg_lba_kernel_times", "osg_optimize_sim3", "osg_optimize_sim3_batch",
     "osg_sim3_ransac", "osg_sim3_ransac_batch", "osg_sim3_ransac_iterations",
@@ -352,6 +352,8 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.osg_search_by_bow_kf_f_batch.argtypes = [vp, vp, vp, i32, f32, C.c_int, vp, vp]
     lib.osg_search_by_bow_kf_kf_batch.argtypes = [vp, vp, vp, i32, f32, C.c_int, vp, vp]
     lib.osg_match_last_stats.argtypes = [vp, vp]
+    lib.osg_match_last_path.argtypes = [vp, vp]
+    lib.osg_debug_match_plan.argtypes = [i32, i32, i32, i32, C.POINTER(i32), C.POINTER(C.c_int64)]
     lib.osg_ctx_last_kernel_ms.argtypes = [vp, vp]
     lib.osg_ctx_device_bytes.argtypes = [vp, vp]
     lib.osg_pose_optimization.argtypes = [vp, C.POINTER(OsgPoseProblem), C.POINTER(OsgPoseResult)]

@@ -514,6 +514,7 @@ int init_run(osg_ctx *ctx, const osg_frame *F1, const osg_frame *F2, float *prev
     }
     ctx->match_stats[1] = rounds_max;
     ctx->match_stats[2] = serial;
+    osg_match_path_clear(ctx);  // not a k_match call
     return OSG_OK;
 }
 

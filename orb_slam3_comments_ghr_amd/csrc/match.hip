@@ -94,7 +94,9 @@ struct MatchArgs {
     GLOBAL uint32_t *cands;
     GLOBAL int32_t *q_res;           // 2 nq: {left slot, right slot}, -1 = no match
     GLOBAL uint8_t *q_bin;           // 2 nq
-    GLOBAL int32_t *status;          // [0] candidates, [1] nmatches, [2] rounds, [3] overflow, [4] serial
+    GLOBAL int32_t *status;          // [0] candidates, [1] nmatches, [2] rounds, [3] overflow, [4] serial,
+                                     // [5..12] phase clocks, [13] BoW first round changed, [14] prepass ticket,
+                                     // [15] serial walk taken (0 none, 1 speculative in LDS, 2 one thread)
     int cap;
     int lds_free;                    // dynamic LDS bytes past the resolve arrays (the staged grid region)
     int prefilled;                   // SearchByBoW: k_bow_fill wrote q_off (host CSR), cands and the first q_res;
@@ -931,15 +933,40 @@ __device__ __forceinline__ int rot_bin(float a, float b)
     return bin;
 }
 
-// Extra LDS of a staged grid-mode launch: cell offsets (one or two grids) + 4 words per keypoint.
+// Dynamic LDS of k_match, in the order the kernel carves it up (ns = n_slots):
+//   resolve arrays   3 ns ints (claimA, claimB, lastS) + 2 x ceil16(ns) bytes (taken0, removedS)
+//   STAGE >= 1       GS_PAD cell offsets per grid (one grid, or two on a two-camera rig) and 4 words
+//                    per keypoint (x, y, u_R, index << 8 | octave), straight behind the resolve arrays
+//   STAGE 2          the descriptors, 32 B per slot, from the next 16-byte boundary of the block (the
+//                    resolve arrays end on a multiple of 4 only, so up to 12 bytes of padding)
 constexpr int GS_PAD = (OSG_GRID_CELLS + 1 + 3) & ~3;
-// STAGE 1: cell offsets + per-entry records; STAGE 2: also the descriptors (32 B per slot).
-__host__ __device__ inline size_t staged_lds_bytes(int ns, bool two_cam, int stage)
+inline size_t match_lds_bytes(int ns)
 {
-    if (stage <= 0) return 0;
-    size_t b = sizeof(int) * ((size_t)GS_PAD * (two_cam ? 2 : 1) + 4 * (size_t)ns);
+    return (size_t)ns * 3 * sizeof(int) + 2 * (((size_t)ns + 15) & ~size_t(15));
+}
+inline size_t launch_lds_bytes(int ns, bool two_cam, int stage)
+{
+    size_t b = match_lds_bytes(ns);
+    if (stage >= 1) b += sizeof(int) * ((size_t)GS_PAD * (two_cam ? 2 : 1) + 4 * (size_t)ns);
     if (stage >= 2) b = ((b + 15) & ~size_t(15)) + 32 * (size_t)ns;
     return b;
+}
+// The staging level of one problem and the dynamic LDS its launch needs: the highest level <= cap
+// whose layout fits lds_per_block less 8 KiB (k_match's static LDS is ~4.3 KB).  Level 0 holds the
+// resolve arrays alone; false when even those do not fit.
+constexpr int MATCH_LDS_RESERVE = 8 * 1024;
+inline bool match_plan(int lds_per_block, int stage_cap, int ns, bool two_cam, int *stage, size_t *lds)
+{
+    const size_t budget = (size_t)std::max(0, lds_per_block - MATCH_LDS_RESERVE);
+    for (int st = std::min(std::max(stage_cap, 0), 2); st >= 0; st--) {
+        const size_t need = launch_lds_bytes(ns, two_cam, st);
+        if (need <= budget) {
+            *stage = st;
+            *lds = need;
+            return true;
+        }
+    }
+    return false;
 }
 
 template <int MODE, int STAGE>
@@ -1183,6 +1210,7 @@ __global__ __launch_bounds__(MT) void k_match(const MatchArgs *__restrict__ args
     // redone serially in query order on the live slot state.
     tclk[7] = __builtin_amdgcn_s_memtime();
     int serial = 0;
+    int walk = 0;  // which serial walk ran (status[15]): 1 the speculative one in LDS, 2 the one-thread one
     if (MODE == MODE_MPS && A.nleft >= 0) {
         int need = 0;
         for (int q = q0; q < q1; q++) {
@@ -1206,7 +1234,8 @@ __global__ __launch_bounds__(MT) void k_match(const MatchArgs *__restrict__ args
             const size_t o_mid = 4 * ((size_t)nq + 1), o_l2r = o_mid + 4 * (size_t)nq;
             const size_t o_r2l = o_l2r + 4 * (size_t)A.nleft, o_c = o_r2l + 4 * (size_t)nright;
             const size_t o_obs = o_c + 4 * (size_t)total, lds_need = o_obs + (size_t)nq;
-            if (STAGED && A.l2r && A.r2l && lds_need <= (size_t)A.lds_free) {
+            walk = (STAGED && A.l2r && A.r2l && lds_need <= (size_t)A.lds_free) ? 1 : 2;
+            if (walk == 1) {
                 char *fr = (char *)(removedS + ((NS + 15) & ~15));
                 SerialLds V{(const int *)fr, (const int *)(fr + o_mid), (const int *)(fr + o_l2r),
                             (const int *)(fr + o_r2l), (const uint32_t *)(fr + o_c), (const uint8_t *)(fr + o_obs)};
@@ -1367,15 +1396,11 @@ __global__ __launch_bounds__(MT) void k_match(const MatchArgs *__restrict__ args
         A.status[0] = total;
         A.status[3] &= 2;  // keep k_grid_prepass's wait-bound flag
         A.status[4] = serial;
+        A.status[15] = walk;
         tclk[8] = __builtin_amdgcn_s_memtime();
         if (BOW) tclk[1] = tclk[2] = tclk[0];
         for (int i = 0; i < 8; i++) A.status[5 + i] = (int32_t)(tclk[i + 1] - tclk[i]);
     }
-}
-
-size_t match_lds_bytes(int ns)
-{
-    return (size_t)ns * 3 * sizeof(int) + 2 * (((size_t)ns + 15) & ~size_t(15));
 }
 
 // Pointer fields of MatchArgs are first filled with packer offsets (+1 so that offset 0 is not
@@ -1449,29 +1474,30 @@ int run_batch(osg_ctx *ctx, std::deque<Problem> &P, int B, const osg_packer &pk,
     hclock::time_point hs[6], hx[4];
     hs[0] = hclock::now();
     std::vector<size_t> slot_off(B + 1, 0), q_base(B + 1, 0);
-    size_t lds = 0;
     for (int b = 0; b < B; b++) {
         OSG_REQUIRE(ctx, P[b].A.n_slots <= MAX_SLOTS, "problem %d: %d slots exceed the %d supported", b,
                     P[b].A.n_slots, MAX_SLOTS);
         slot_off[b + 1] = slot_off[b] + (size_t)P[b].n_slot;
         q_base[b + 1] = q_base[b] + (size_t)P[b].A.nq + 1;
-        lds = std::max(lds, match_lds_bytes(P[b].A.n_slots));
     }
-    // grid modes stage the frames' grids (and descriptors) in LDS when every problem's fits
+    // grid modes stage the frames' grids (and descriptors) in LDS: the launch takes the highest level
+    // that every problem fits (match_plan; OSG_MATCH_STAGE = 0 / 1 caps it) and the dynamic LDS of its
+    // largest problem at that level
     constexpr bool BOW = MODE == MODE_BOW_KF_F || MODE == MODE_BOW_KF_KF;
-    static const int stage_env = getenv("OSG_MATCH_STAGE") ? atoi(getenv("OSG_MATCH_STAGE")) : 2;
-    const size_t lds_budget = (size_t)std::max(0, ctx->lds_per_block - 8 * 1024);  // static LDS ~4.3 KB
-    int stage = 0;
-    if (!BOW)
-        for (int st = std::min(stage_env, 2); st >= 1 && stage == 0; st--) {
-            size_t need = lds;
-            for (int b = 0; b < B; b++)
-                need = std::max(need, match_lds_bytes(P[b].A.n_slots) +
-                                          staged_lds_bytes(P[b].A.n_slots, P[b].A.nleft >= 0, st));
-            if (need <= lds_budget) {
-                stage = st;
-                lds = need;
-            }
+    const char *se = getenv("OSG_MATCH_STAGE");  // read per call: tests switch it
+    int stage = BOW ? 0 : (se ? atoi(se) : 2);
+    size_t lds = 0;
+    for (int pass = 0; pass < 2; pass++)
+        for (int b = 0; b < B; b++) {
+            int st = 0;
+            size_t need = 0;
+            if (!match_plan(ctx->lds_per_block, stage, P[b].A.n_slots, P[b].A.nleft >= 0, &st, &need))
+                return osg_set_error(ctx, OSG_E_UNSUPPORTED,
+                                     "problem %d: %d slots need %zu bytes of LDS, the device offers %d less %d per workgroup",
+                                     b, P[b].A.n_slots, match_lds_bytes(P[b].A.n_slots), ctx->lds_per_block,
+                                     MATCH_LDS_RESERVE);
+            if (pass == 0) stage = std::min(stage, st);  // the level every problem fits
+            else lds = std::max(lds, need);              // at that level (st == stage for every problem)
         }
     // (dynamic LDS up to the 160 KiB of a CU launches without a function attribute on gfx950:
     // tools/micro/lds_limit.hip)
@@ -1625,9 +1651,10 @@ int run_batch(osg_ctx *ctx, std::deque<Problem> &P, int B, const osg_packer &pk,
                             sizeof(int32_t) * P[b].n_slot);
     }
     int64_t cand_sum = 0, nm_sum = 0;
-    int rounds_max = 0, serial_n = 0;
+    int rounds_max = 0, serial_n = 0, walk_n[3] = {};
     for (int b = 0; b < B; b++) {
         const int32_t *sb = &st[(size_t)STATUS_INTS * b];
+        walk_n[std::min(std::max((int)sb[15], 0), 2)]++;
         nmatches[b] = sb[1];
         cand_sum += sb[0];
         nm_sum += sb[1];
@@ -1663,6 +1690,12 @@ int run_batch(osg_ctx *ctx, std::deque<Problem> &P, int B, const osg_packer &pk,
     ctx->match_stats[1] = rounds_max;
     ctx->match_stats[2] = serial_n;
     ctx->match_stats[3] = (int32_t)std::min<int64_t>(nm_sum, INT_BIG);
+    ctx->match_path[0] = stage;
+    ctx->match_path[1] = (int32_t)lds;
+    ctx->match_path[2] = walk_n[1];
+    ctx->match_path[3] = walk_n[2];
+    ctx->match_path[4] = grid_pre ? 1 : 0;
+    ctx->match_path[6] = B;
     return OSG_OK;
 }
 
@@ -1705,6 +1738,8 @@ int check_grid(osg_ctx *ctx, const int32_t *gs, const int32_t *gi, int n_cam, co
     for (int c = 0; c < OSG_GRID_CELLS; c++)
         OSG_REQUIRE(ctx, gs[c + 1] >= gs[c], "%s grid_start not monotone at cell %d", which, c);
     const int m = gs[OSG_GRID_CELLS];
+    // a keypoint lies in one cell at most: a staged launch keeps one LDS record per grid entry
+    OSG_REQUIRE(ctx, m <= n_cam, "%s grid holds %d entries for %d keypoints", which, m, n_cam);
     for (int j = 0; j < m; j++)
         OSG_REQUIRE(ctx, gi[j] >= 0 && gi[j] < n_cam, "%s grid_idx[%d] = %d out of range", which, j, gi[j]);
     return OSG_OK;
@@ -1998,6 +2033,7 @@ template <int MODE, typename Prep>
 int run_problems(osg_ctx *ctx, int B, int32_t *nmatches, Prep prep)
 {
     if (!ctx) return OSG_E_INVALID;
+    osg_match_path_clear(ctx);  // a call that is rejected, or launches nothing, reports no launch
     OSG_REQUIRE(ctx, B >= 0 && (B == 0 || nmatches), "batch size / nmatches");
     if (!ctx->match_cache) ctx->match_cache = std::make_shared<MatchCache>();
     MatchCache &mc = *static_cast<MatchCache *>(ctx->match_cache.get());
@@ -2038,6 +2074,18 @@ int run_single(osg_ctx *ctx, Prep prep)
 int osg_check_frame(osg_ctx *ctx, const osg_frame *F) { return check_frame(ctx, F); }
 
 extern "C" {
+
+int osg_debug_match_plan(int32_t lds_per_block, int32_t stage_cap, int32_t n_slots, int32_t two_cam, int32_t *stage,
+                         int64_t *lds_bytes)
+{
+    if (!stage || !lds_bytes || n_slots < 0 || n_slots > MAX_SLOTS) return OSG_E_INVALID;
+    int st = 0;
+    size_t lds = 0;
+    if (!match_plan(lds_per_block, stage_cap, n_slots, two_cam != 0, &st, &lds)) return OSG_E_UNSUPPORTED;
+    *stage = st;
+    *lds_bytes = (int64_t)lds;
+    return OSG_OK;
+}
 
 int osg_search_by_projection_mps(osg_ctx *ctx, const osg_frame *F, const osg_mp_queries *Q, float nnratio,
                                  float th, int far_points, float th_far_points, int32_t *slot_mp,

@@ -40,6 +40,10 @@ struct osg_ctx {
     int num_cus = 256;
     int lds_per_block = 65536;
     int32_t match_stats[4] = {};  // last matcher call: candidates, Jacobi rounds, serial redo, nmatches
+    // the code path of the last matcher call (osg_match_last_path): staging level (-1: not a k_match
+    // call), dynamic LDS bytes, problems on the speculative / the one-thread serial walk, k_grid_*
+    // prepass ran, lds_per_block, problems in the launch, 0
+    int32_t match_path[8] = {-1, 0, 0, 0, 0, 0, 0, 0};
     double last_kernel_ms = 0;    // last k_match / k_pose_opt launch time (HIP events)
     hipEvent_t ev[2] = {};        // timing events (osg_ctx_events)
     hipEvent_t ev_done = nullptr; // completion marker of osg_wait (no timing)
@@ -56,6 +60,14 @@ struct osg_ctx {
 };
 
 int osg_set_error(osg_ctx *ctx, int code, const char *fmt, ...);
+// Every caller that writes match_stats starts here: "not a k_match call" until run_batch (match.hip)
+// fills in what it launched, so a stale report cannot be read as this call's.
+inline void osg_match_path_clear(osg_ctx *ctx)
+{
+    for (int32_t &v : ctx->match_path) v = 0;
+    ctx->match_path[0] = -1;
+    ctx->match_path[5] = ctx->lds_per_block;
+}
 // the context's two timing events, created on first use (nullptr on failure)
 hipEvent_t *osg_ctx_events(osg_ctx *ctx);
 // device buffer of at least `bytes` for `slot` (grows, never shrinks)

@@ -504,6 +504,14 @@ int osg_match_last_stats(osg_ctx *ctx, int32_t *out4)
     return OSG_OK;
 }
 
+int osg_match_last_path(osg_ctx *ctx, int32_t *out8)
+{
+    if (!ctx || !out8) return OSG_E_INVALID;
+    for (int i = 0; i < 8; i++) out8[i] = ctx->match_path[i];
+    out8[5] = ctx->lds_per_block;
+    return OSG_OK;
+}
+
 int osg_ctx_last_kernel_ms(osg_ctx *ctx, double *ms)
 {
     if (!ctx || !ms) return OSG_E_INVALID;

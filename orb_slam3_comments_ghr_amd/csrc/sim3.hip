@@ -267,6 +267,7 @@ int sim3_run(osg_ctx *ctx, const osg_frame *KF, const osg_fuse_queries *Q, int B
         for (size_t i = 0; i < nq_total; i++) query_best[i] = pin_out[i];
         for (int b = 0; b < B; b++) rounds_max = std::max(rounds_max, pin_out[nq_total + b]);
         ctx->match_stats[1] = rounds_max;
+        osg_match_path_clear(ctx);  // not a k_match call
         return OSG_OK;
     }
     for (int b = 0; b < B; b++) {
@@ -283,6 +284,7 @@ int sim3_run(osg_ctx *ctx, const osg_frame *KF, const osg_fuse_queries *Q, int B
         rounds_max = std::max(rounds_max, pin_out[nq_total + b]);
     }
     ctx->match_stats[1] = rounds_max;
+    osg_match_path_clear(ctx);  // not a k_match call
     return OSG_OK;
 }
 

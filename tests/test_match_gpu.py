@@ -176,7 +176,11 @@ def test_search_by_projection_mps_two_cam_paths(ctx, oracle, monkeypatch, prepas
 @pytest.mark.parametrize("seed", range(4))
 def test_search_by_projection_mps_two_cam_dense_conflicts(ctx, oracle, seed):
     """The serial redo's 64-query speculative batches under heavy conflicts: few keypoints, many
-    queries on the same slots, so most batches stop early and commit a prefix."""
+    queries on the same slots, so most batches stop early and commit a prefix.  The walk's inputs
+    (9 bytes per query, 4 per keypoint and per candidate: about 12 KB for the 700-850 candidates
+    here) fit the ~30 KB a staged 130-keypoint launch holds past its resolve arrays, so every seed
+    runs the speculative walk, as the path report confirms; tests/test_match_paths_gpu.py has the
+    many-query case that falls to the one-thread walk."""
     rng = np.random.default_rng(6200 + seed)
     F = two_cam(rng, 70, 60)
     Q = fr.synth_mp_queries_two_cam(rng, F, m=900, noise_px=1.0, match_frac=0.95)
@@ -186,6 +190,8 @@ def test_search_by_projection_mps_two_cam_dense_conflicts(ctx, oracle, seed):
     s = slot_mp.copy()
     n = ORBmatcher(ctx, 0.95).SearchByProjection(F, Q, 5.0, False, 20.0, slot_mp=s, slot_taken=taken)
     assert_same(f"mps two-cam dense seed {seed}", n, s, *ref)
+    path = ctx.match_last_path()
+    assert ctx.match_last_stats()["serial"] and (path["stage"], path["walk_lds"], path["walk_thread"]) == (2, 1, 0), path
 
 
 @pytest.mark.parametrize("seed", range(6))

@@ -192,6 +192,67 @@ def test_oracle_bow_two_cam_vs_python(oracle, seed):
         assert (got[1][K1.nleft:] == -1).all()
 
 
+# ---- the frame sizes of tests/test_match_paths_gpu.py (up to the 8192 slots a launch supports):
+# the oracle that checks the kernels there is itself pinned here at those sizes
+
+def big_frame(rng, two):
+    if two:
+        return fr.synth_frame_two_cam(rng, n_left=4096, n_right=4096, stereo_frac=0.6)
+    return fr.synth_frame(rng, n=8192, stereo=True)
+
+
+@pytest.mark.parametrize("two", [False, True])
+def test_oracle_mps_vs_python_8192(oracle, two):
+    rng = np.random.default_rng(800 + two)
+    F = big_frame(rng, two)
+    Q = (fr.synth_mp_queries_two_cam if two else fr.synth_mp_queries)(rng, F, m=1500)
+    slot_mp, taken = fr.synth_slots(rng, F.n, frac_assigned=0.15)
+    got = oc.mps(oracle, F, Q, 0.8, 3.0, False, 20.0, slot_mp, taken)
+    ref = pr.search_mps(F, Q, 0.8, 3.0, False, 20.0, slot_mp, taken)
+    assert got[0] == ref[0] and got[0] > 100
+    np.testing.assert_array_equal(got[1], ref[1])
+    if two:
+        assert (got[1][F.nleft:] != slot_mp[F.nleft:]).any(), "right-camera slots must be exercised"
+
+
+@pytest.mark.parametrize("two", [False, True])
+def test_oracle_last_vs_python_8192(oracle, two):
+    rng = np.random.default_rng(810 + two)
+    F = big_frame(rng, two)
+    L = (fr.synth_last_queries_two_cam if two else fr.synth_last_queries)(rng, F, n_last=1200)
+    slot_mp, taken = fr.synth_slots(rng, F.n)
+    got = oc.last(oracle, F, L, 7.0, False, True, slot_mp, taken)
+    ref = pr.search_last(F, L, 7.0, False, True, slot_mp, taken)
+    assert got[0] == ref[0] and got[0] > 100
+    np.testing.assert_array_equal(got[1], ref[1])
+
+
+@pytest.mark.parametrize("two", [False, True])
+def test_oracle_kf_vs_python_8192(oracle, two):
+    rng = np.random.default_rng(820 + two)
+    F = big_frame(rng, two)
+    K = fr.synth_kf_queries(rng, F, n_kf=1200)
+    slot_mp, _ = fr.synth_slots(rng, F.n, frac_assigned=0.2)
+    got = oc.kf(oracle, F, K, 10.0, 100, True, slot_mp)
+    ref = pr.search_kf(F, K, 10.0, 100, True, slot_mp)
+    assert got[0] == ref[0] and got[0] > 100
+    np.testing.assert_array_equal(got[1], ref[1])
+
+
+def test_oracle_bow_vs_python_5000(oracle):
+    rng = np.random.default_rng(830)
+    KF, F = fr.synth_bow_pair(rng, n_kf=600, n_f=5000, n_nodes=100)
+    K1, K2 = fr.synth_bow_pair(rng, n_kf=600, n_f=5000, n_nodes=100, f_is_kf=True)
+    got = oc.bow_kf_f(oracle, KF, F, 0.75, True)
+    ref = pr.search_bow_kf_f(KF, F, 0.75, True)
+    assert got[0] == ref[0] and got[0] > 100
+    np.testing.assert_array_equal(got[1], ref[1])
+    got = oc.bow_kf_kf(oracle, K1, K2, 0.75, True)
+    ref = pr.search_bow_kf_kf(K1, K2, 0.75, True)
+    assert got[0] == ref[0] and got[0] > 100
+    np.testing.assert_array_equal(got[1], ref[1])
+
+
 @pytest.mark.parametrize("seed", range(3))
 def test_oracle_fuse_vs_python(oracle, seed):
     """Fuse search half, both overloads (gated: Fuse(KF, vpMapPoints); ungated: the Sim3 Fuse)."""
