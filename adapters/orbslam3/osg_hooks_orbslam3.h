@@ -327,6 +327,30 @@ struct OsgHooks {
     }
     // TwoViewReconstruction (ref:src/TwoViewReconstruction.cc:96)
     static void seed_rand_once(int seed) { DUtils::Random::SeedRandOnce(seed); }
+    // CreateNewMapPoints (ref:src/LocalMapping.cc:559-565, 633-637, 683-728; ref:src/KeyFrame.cc:935): the poses and
+    // camera centres of both cameras, mRwc / mTwc.translation() and the cameras' parameters, as the reference's own
+    // Sophus / Eigen values (OsgHooks is a friend of KeyFrame under ORB_SLAM3_OSG for mRwc / mTwc)
+    static void np_kf(KeyFrame *pKF, osg_np_kf &k)
+    {
+        const bool rig = pKF->mpCamera2 != nullptr;
+        for (int c = 0; c < (rig ? 2 : 1); c++) {
+            const Eigen::Matrix<float, 3, 4> T = (c ? pKF->GetRightPose() : pKF->GetPose()).matrix3x4();
+            const Eigen::Vector3f O = c ? pKF->GetRightCameraCenter() : pKF->GetCameraCenter();
+            for (int r = 0; r < 3; r++) {
+                for (int j = 0; j < 4; j++) k.Tcw[c][4 * r + j] = T(r, j);
+                k.Ow[c][r] = O(r);
+            }
+            GeometricCamera *cam = c ? pKF->mpCamera2 : pKF->mpCamera;
+            for (int j = 0; j < 8 && j < (int)cam->size(); j++) k.cam[c][j] = cam->getParameter(j);
+        }
+        k.cam_type = pKF->mpCamera->GetType() == GeometricCamera::CAM_PINHOLE ? 0 : 1;
+        std::unique_lock<std::mutex> lock(pKF->mMutexPose);
+        const Eigen::Vector3f twc = pKF->mTwc.translation();
+        for (int r = 0; r < 3; r++) {
+            for (int j = 0; j < 3; j++) k.Rwc[3 * r + j] = pKF->mRwc(r, j);
+            k.twc[r] = twc(r);
+        }
+    }
     // KeyFrameDatabase: the vocabulary on the device, set by System right after it loads ORBvoc
     // (osg_vocabulary_load_text) and before it constructs the database
     static const osg_vocabulary *&device_vocabulary()

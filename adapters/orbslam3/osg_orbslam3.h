@@ -3447,5 +3447,136 @@ private:
     osg_kfdb_query_out mLast{};
 };
 
+// --------------------------------------------------------------- LocalMapping::CreateNewMapPoints
+// ref:src/LocalMapping.cc:526-934 in one osg_create_new_map_points call.  NewPointsGather builds the neighbour
+// list of :531-552 and the problem: one osg_kf_side per KeyFrame as search_for_triangulation gathers it, the
+// KeyFrame geometry through H::np_kf (poses, camera centres, mRwc / mTwc and the cameras, the reference's own
+// Sophus / Eigen values), mvDepth / mvKeys, the neighbours' ComputeSceneMedianDepth(2) (monocular) and the
+// pair geometry through H::triang_geom.
+template <class H, class KeyFrameT>
+struct NewPointsGather {
+    struct Side {
+        std::vector<uint8_t> desc, has_mp;
+        std::vector<float> x, y, a, kx, ky;
+        std::vector<int32_t> oct;
+        std::unique_ptr<FeatVecCSR<decltype(KeyFrameT::mFeatVec)>> fv;
+    };
+    std::vector<KeyFrameT *> neigh;
+    std::vector<Side> sides;  // [0] the current KeyFrame, [1 + b] neighbour b
+    std::vector<osg_kf_side> kf;
+    std::vector<osg_np_kf> g;
+    std::vector<osg_triang_geom> geom;
+    osg_newpoints_problem problem{};
+
+    // vpNeighKFs, ref:src/LocalMapping.cc:531-552
+    static std::vector<KeyFrameT *> neighbours(KeyFrameT *cur, bool monocular, bool inertial)
+    {
+        int nn = 10;
+        if (monocular) nn = 30;
+        std::vector<KeyFrameT *> v = cur->GetBestCovisibilityKeyFrames(nn);
+        if (inertial) {
+            KeyFrameT *pKF = cur;
+            int count = 0;
+            while (((int)v.size() <= nn) && (pKF->mPrevKF) && (count++ < nn)) {
+                if (std::find(v.begin(), v.end(), pKF->mPrevKF) == v.end()) v.push_back(pKF->mPrevKF);
+                pKF = pKF->mPrevKF;
+            }
+        }
+        return v;
+    }
+
+    void side(KeyFrameT *p, bool neighbour, bool monocular)
+    {
+        sides.emplace_back();
+        Side &s = sides.back();
+        const int n = p->N;
+        copy_desc_rows(p->mDescriptors, n, s.desc);
+        s.has_mp.resize(n);
+        for (int i = 0; i < n; i++) {
+            // :659-661 / :671-673: mvKeysUn, or mvKeys / mvKeysRight on a rig
+            const auto &kp = (p->NLeft == -1) ? p->mvKeysUn[i] : (i < p->NLeft ? p->mvKeys[i] : p->mvKeysRight[i - p->NLeft]);
+            s.x.push_back(kp.pt.x);
+            s.y.push_back(kp.pt.y);
+            s.a.push_back(kp.angle);
+            s.oct.push_back(kp.octave);
+            s.has_mp[i] = p->GetMapPoint(i) != nullptr;
+        }
+        const bool stereo = !p->mpCamera2 && !p->mvuRight.empty();
+        if (stereo)  // KeyFrame::UnprojectStereo reads mvKeys, not mvKeysUn (ref:src/KeyFrame.cc:928-929)
+            for (int i = 0; i < n; i++) {
+                s.kx.push_back(p->mvKeys[i].pt.x);
+                s.ky.push_back(p->mvKeys[i].pt.y);
+            }
+        s.fv.reset(new FeatVecCSR<decltype(KeyFrameT::mFeatVec)>(p->mFeatVec));
+        kf.push_back(osg_kf_side{n, p->NLeft, p->mpCamera2 != nullptr, s.desc.data(), s.x.data(), s.y.data(), s.a.data(),
+                                 s.oct.data(), p->mvuRight.empty() ? nullptr : p->mvuRight.data(), s.has_mp.data(),
+                                 p->mvLevelSigma2.data(), p->mvScaleFactors.data(), (int32_t)p->mvScaleFactors.size(),
+                                 s.fv->view()});
+        osg_np_kf k{};
+        H::np_kf(p, k);
+        k.fx = p->fx, k.fy = p->fy, k.cx = p->cx, k.cy = p->cy, k.invfx = p->invfx, k.invfy = p->invfy;
+        k.mb = p->mb, k.mbf = p->mbf;
+        k.depth = stereo ? p->mvDepth.data() : nullptr;
+        k.keys_x = stereo ? s.kx.data() : nullptr;
+        k.keys_y = stereo ? s.ky.data() : nullptr;
+        k.median_depth = (neighbour && monocular) ? p->ComputeSceneMedianDepth(2) : 0.f;
+        g.push_back(k);
+    }
+
+    NewPointsGather(KeyFrameT *cur, const std::vector<KeyFrameT *> &vpNeighKFs, bool monocular, bool inertial,
+                    bool coarse, bool far_points, float th_far_points)
+        : neigh(vpNeighKFs)
+    {
+        const size_t B = neigh.size();
+        sides.reserve(B + 1);  // the views point into the sides
+        kf.reserve(B + 1);
+        g.reserve(B + 1);
+        side(cur, false, monocular);
+        geom.resize(B);
+        for (size_t b = 0; b < B; b++) {
+            side(neigh[b], true, monocular);
+            H::triang_geom(cur, neigh[b], geom[b]);
+        }
+        problem.kf1 = kf[0];
+        problem.g1 = g[0];
+        problem.n_neigh = (int32_t)B;
+        problem.kf2 = B ? kf.data() + 1 : nullptr;
+        problem.g2 = B ? g.data() + 1 : nullptr;
+        problem.geom = B ? geom.data() : nullptr;
+        problem.monocular = monocular, problem.inertial = inertial, problem.coarse = coarse;
+        problem.far_points = far_points;
+        problem.th_far_points = th_far_points;
+        problem.ratio_factor = 1.5f * cur->mfScaleFactor;  // :575
+    }
+};
+
+// The call and the creation order.  check_new_keyframes is LocalMapping::CheckNewKeyFrames() read once before the
+// call: true -> only neighbour 0 is processed (the reference's behaviour when the flag is up at its i = 1 check),
+// false -> all of them (its behaviour when the flag stays down); what the reference does in between depends on
+// thread timing.  on_point(pKF2, idx1, idx2, x3D) is called for every MapPoint to create in the reference's order
+// (ascending neighbour, then ascending KF1 index): the caller constructs the MapPoint and does :916-931 there.
+// Returns the number of points, or a negative OSG_E_* code (nothing created).
+template <class H, class KeyFrameT, class OnPoint>
+int create_new_map_points(KeyFrameT *cur, bool monocular, bool inertial, bool coarse, bool far_points,
+                          float th_far_points, bool check_new_keyframes, OnPoint on_point)
+{
+    osg_ctx *ctx = thread_ctx();
+    std::vector<KeyFrameT *> neigh = NewPointsGather<H, KeyFrameT>::neighbours(cur, monocular, inertial);
+    if (check_new_keyframes && neigh.size() > 1) neigh.resize(1);
+    NewPointsGather<H, KeyFrameT> G(cur, neigh, monocular, inertial, coarse, far_points, th_far_points);
+    const size_t n1 = (size_t)cur->N, B = neigh.size();
+    std::vector<int32_t> match(B * n1, -1);
+    std::vector<uint8_t> status(B * n1, 0);
+    std::vector<float> x3d(3 * B * n1, 0.f);
+    osg_newpoints_result r{match.data(), status.data(), x3d.data(), nullptr, nullptr};
+    const int rc = call(ctx, "osg_create_new_map_points", [&] { return osg_create_new_map_points(ctx, &G.problem, &r); });
+    if (rc < 0) return rc;
+    for (size_t b = 0; b < B; b++)
+        for (size_t i = 0; i < n1; i++)
+            if ((status[b * n1 + i] & 0x7f) == OSG_NP_CREATED)
+                on_point(neigh[b], (int)i, (int)match[b * n1 + i], &x3d[3 * (b * n1 + i)]);
+    return rc;
+}
+
 }  // namespace osg_orbslam3
 #endif

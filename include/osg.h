@@ -520,6 +520,89 @@ int osg_search_for_triangulation_batch(osg_ctx *ctx, const osg_kf_side *kf1, con
                                        const osg_triang_geom *geom, int32_t B, int only_stereo, int coarse,
                                        int check_orientation, int32_t *match12, int32_t *nmatches);
 
+/* ---- b3n: LocalMapping::CreateNewMapPoints ------------------------------------------------------
+ * ref:src/LocalMapping.cc:584-933 for one current KeyFrame (KF1) and its neighbours in the order of
+ * vpNeighKFs: per neighbour the baseline skip (:595-621), SearchForTriangulation(cur, pKF2, ., false,
+ * bCoarse) without the orientation check (ORBmatcher(0.6f, false), :556), and per match the
+ * triangulation / UnprojectStereo and every acceptance test of :649-906, in the reference's float
+ * arithmetic and order.  Every (keypoint, neighbour) is evaluated in parallel for the KF1 MapPoint
+ * state at call time (kf1.has_mp); the reference's sequential rule is then replayed on the device: a KF1
+ * keypoint gets its MapPoint at the first neighbour, in order, that is not skipped and whose match is
+ * accepted, and no later neighbour sees it.  This is exact because in this fork no KF2 keypoint is
+ * claimed (ref:src/ORBmatcher.cc:1262) and there is no rotation histogram, so a match and its tests
+ * depend on (keypoint, neighbour) alone.  Kept upstream quirks: the second KeyFrame's stereo
+ * reprojection uses the current KeyFrame's mbf (:875); in a two-camera rig Ow1 stays that of the last
+ * match of the previous processed neighbour for the next baseline test (:683-728, :599).
+ * cos / atan2 of :762-765 are the float overloads (std:: via "using namespace std" of the DBoW2
+ * header), evaluated by fixed kernels; the 4x4 JacobiSVD null vector is the smallest-eigenvalue
+ * eigenvector of A^T A (cyclic Jacobi, double): parity with libm / Eigen is unpinned at the last ulp.
+ *
+ * The neighbours of one call must be distinct KeyFrames (the ABI cannot check it): the claim rule
+ * carries KF1's MapPoint slots from neighbour to neighbour, not a neighbour's own. */
+#define OSG_NEWPOINTS_MAX_NEIGHBOURS 64 /* the reference uses at most 31 (nn = 30 + mPrevKF walk) */
+
+/* status byte: low 7 bits one of the codes, bit 7 = bPointStereo */
+#define OSG_NP_NONE 0          /* no match (or not seen: claimed earlier, neighbour skipped) */
+#define OSG_NP_CREATED 1
+#define OSG_NP_LOW_PARALLAX 2  /* the 'continue' of :803-806 */
+#define OSG_NP_NO_POINT 3      /* Triangulate (w == 0) / UnprojectStereo (depth <= 0) false */
+#define OSG_NP_Z1 4
+#define OSG_NP_Z2 5
+#define OSG_NP_REPROJ1 6
+#define OSG_NP_REPROJ2 7
+#define OSG_NP_ZERO_DIST 8
+#define OSG_NP_FAR 9
+#define OSG_NP_SCALE 10
+#define OSG_NP_STEREO_BIT 0x80
+
+/* A KeyFrame's geometry as the reference holds it (float values are its own). */
+typedef struct osg_np_kf {
+    float Tcw[2][12];   /* GetPose() / GetRightPose() as matrix3x4, row-major; [1] read only in a rig */
+    float Ow[2][3];     /* GetCameraCenter() / GetRightCameraCenter() */
+    float Rwc[9];       /* mRwc, row-major (UnprojectStereo) */
+    float twc[3];       /* mTwc.translation() */
+    int32_t cam_type;   /* 0 Pinhole, 1 KannalaBrandt8 (both cameras) */
+    float cam[2][8];    /* mpCamera / mpCamera2 mvParameters: fx fy cx cy [k0 k1 k2 k3] */
+    float fx, fy, cx, cy, invfx, invfy, mb, mbf;
+    const float *depth;             /* mvDepth[n]; NULL allowed when u_right is NULL or in a rig */
+    const float *keys_x, *keys_y;   /* mvKeys[n].pt (not mvKeysUn); as depth */
+    float median_depth;             /* neighbours: ComputeSceneMedianDepth(2); read when monocular */
+} osg_np_kf;
+
+typedef struct osg_newpoints_problem {
+    osg_kf_side kf1;                /* mpCurrentKeyFrame */
+    osg_np_kf g1;
+    int32_t n_neigh;                /* <= OSG_NEWPOINTS_MAX_NEIGHBOURS */
+    const osg_kf_side *kf2;         /* [n_neigh] */
+    const osg_np_kf *g2;            /* [n_neigh] */
+    const osg_triang_geom *geom;    /* [n_neigh], of (KF1, neighbour) */
+    int32_t monocular, inertial, coarse, far_points; /* mbMonocular, mbInertial, bCoarse, mbFarPoints */
+    float th_far_points;            /* mThFarPoints */
+    float ratio_factor;             /* 1.5f * mpCurrentKeyFrame->mfScaleFactor */
+} osg_newpoints_problem;
+
+/* Outputs in the sequential state, concatenated by neighbour (index b * kf1.n + i).  Every array may be
+ * NULL.  x3d is valid where the status is CREATED or a rejection after the point exists (Z1 .. SCALE),
+ * zero elsewhere.  The MapPoints to create are the (b, i) with status CREATED in ascending b, then
+ * ascending i: the reference's creation order. */
+typedef struct osg_newpoints_result {
+    int32_t *match;     /* [n_neigh * n]: KF2 index, -1 */
+    uint8_t *status;    /* [n_neigh * n] */
+    float *x3d;         /* [n_neigh * n][3] */
+    uint8_t *skipped;   /* [n_neigh]: the baseline test skipped the neighbour */
+    int32_t *n_created; /* [n_neigh] */
+} osg_newpoints_result;
+
+/* Returns the number of MapPoints to create (>= 0) or an OSG_E_* code.  Before any launch:
+ * OSG_E_INVALID for negative counts, null arrays with positive counts, n_neigh above the limit;
+ * OSG_E_UNSUPPORTED for a rig KeyFrame paired with a non-rig one. */
+int osg_create_new_map_points(osg_ctx *ctx, const osg_newpoints_problem *problem, osg_newpoints_result *result);
+/* n_problems independent current KeyFrames in the same launches; returns the total created. */
+int osg_create_new_map_points_batch(osg_ctx *ctx, const osg_newpoints_problem *problems,
+                                    osg_newpoints_result *results, int32_t n_problems);
+/* The argument checks of the two calls above alone (host only: no context, no GPU): 0 or the code. */
+int osg_create_new_map_points_check(const osg_newpoints_problem *problem);
+
 /* ---- b4: MapPoint::ComputeDistinctiveDescriptors ------------------------------------------------
  * ref:src/MapPoint.cc:444-535, for a list of MapPoints at once (LocalMapping runs it for every MapPoint
  * of a keyframe, ref:src/LocalMapping.cc:421-436, 1066-1082).  MapPoint p's observation descriptors

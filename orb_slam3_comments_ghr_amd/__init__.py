@@ -15,7 +15,8 @@ import numpy as np
 from . import _abi
 from ._abi import LIB_PATH
 
-__all__ = ["load_library", "Context", "OsgError", "LIB_PATH", "TwoViewReconstruction", "draw_sets"]
+__all__ = ["load_library", "Context", "OsgError", "LIB_PATH", "TwoViewReconstruction", "draw_sets",
+           "CreateNewMapPoints"]
 
 _lib = None
 
@@ -214,4 +215,8 @@ def __getattr__(name):
     if name in ("MLPnPsolver", "MlpnpProblem"):
         from . import mlpnpsolver
         return getattr(mlpnpsolver, name)
+    # LocalMapping's new-point triangulation, likewise
+    if name in ("CreateNewMapPoints", "NewPointsProblem", "NpKeyFrame"):
+        from . import localmapping
+        return getattr(localmapping, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

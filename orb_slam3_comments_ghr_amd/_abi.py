@@ -105,6 +105,28 @@ class OsgTriangGeom(C.Structure):
                 ("t12", f32 * 12), ("kb", f32 * 32)]
 
 
+class OsgNpKf(C.Structure):
+    _fields_ = [("Tcw", f32 * 24), ("Ow", f32 * 6), ("Rwc", f32 * 9), ("twc", f32 * 3), ("cam_type", i32),
+                ("cam", f32 * 16), ("fx", f32), ("fy", f32), ("cx", f32), ("cy", f32), ("invfx", f32), ("invfy", f32),
+                ("mb", f32), ("mbf", f32), ("depth", P), ("keys_x", P), ("keys_y", P), ("median_depth", f32)]
+
+
+class OsgNewPointsProblem(C.Structure):
+    _fields_ = [("kf1", OsgKfSide), ("g1", OsgNpKf), ("n_neigh", i32), ("kf2", P), ("g2", P), ("geom", P),
+                ("monocular", i32), ("inertial", i32), ("coarse", i32), ("far_points", i32),
+                ("th_far_points", f32), ("ratio_factor", f32)]
+
+
+class OsgNewPointsResult(C.Structure):
+    _fields_ = [("match", P), ("status", P), ("x3d", P), ("skipped", P), ("n_created", P)]
+
+
+NEWPOINTS_MAX_NEIGHBOURS = 64
+NP_NONE, NP_CREATED, NP_LOW_PARALLAX, NP_NO_POINT, NP_Z1, NP_Z2 = 0, 1, 2, 3, 4, 5
+NP_REPROJ1, NP_REPROJ2, NP_ZERO_DIST, NP_FAR, NP_SCALE = 6, 7, 8, 9, 10
+NP_STEREO_BIT = 0x80
+
+
 class OsgImagePyramid(C.Structure):
     _fields_ = [("n_levels", i32), ("on_device", i32), ("data", P), ("rows", P), ("cols", P), ("step", P)]
 
@@ -303,6 +325,7 @@ EXPORTS = [
     "osg_kfdb_clear", "osg_kfdb_clear_map", "osg_kfdb_state_get", "osg_kfdb_state_set", "osg_kfdb_query",
     "osg_kfdb_select_nbest", "osg_kfdb_select_reloc",
     "osg_fuse_search", "osg_fuse_search_batch", "osg_search_for_triangulation", "osg_search_for_triangulation_batch",
+    "osg_create_new_map_points", "osg_create_new_map_points_batch", "osg_create_new_map_points_check",
     "osg_compute_distinctive_descriptors", "osg_compute_distinctive_descriptors_dev",
     "osg_search_by_projection_sim3", "osg_search_by_projection_sim3_batch", "osg_search_by_sim3",
     "osg_search_for_initialization", "osg_search_for_initialization_batch",
@@ -430,4 +453,7 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.osg_compute_distinctive_descriptors.argtypes = [vp, vp, vp, i32, vp]
     lib.osg_compute_distinctive_descriptors_dev.argtypes = [vp, vp, vp, i32, vp]
     lib.osg_search_for_triangulation_batch.argtypes = [vp, vp, vp, vp, i32, C.c_int, C.c_int, C.c_int, vp, vp]
+    lib.osg_create_new_map_points.argtypes = [vp, C.POINTER(OsgNewPointsProblem), C.POINTER(OsgNewPointsResult)]
+    lib.osg_create_new_map_points_batch.argtypes = [vp, vp, vp, i32]
+    lib.osg_create_new_map_points_check.argtypes = [C.POINTER(OsgNewPointsProblem)]
     return lib

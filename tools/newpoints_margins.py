@@ -1,0 +1,51 @@
+#!/usr/bin/env python3
+"""Measure how far the tested quantities of CreateNewMapPoints move between equally valid evaluations, per fixture
+group, and write profiles/newpoints_margins.json (CPU only; read by tests/newpoints_fixtures.py).
+
+    python tools/newpoints_margins.py
+
+Replicas of every fixture of tests/newpoints_fixtures.py are run through tests/pyref_newpoints.py: the SVD and the
+norms in float64, the sums back to front, cos / atan2 of the stereo parallax in double, keypoints and poses nudged
+by one ulp (three times).  Per fixture the largest movement of each kind of quantity is recorded (cos, z, reproj,
+ratio, baseline, x3d: see tests/newpoints_fixtures.py); per group the largest over its fixtures, and the tolerance
+10 x that.  Then every fixture's guard is evaluated at its group's tolerances; the tool fails when one is invalid.
+"""
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from tests import newpoints_fixtures as FX  # noqa: E402
+
+
+def measure():
+    fixtures = {name: FX.spreads(name) for name in FX.FIXTURES}
+    groups = {}
+    for g in FX.GROUPS:
+        members = [k for k in FX.FIXTURES if FX.group(k) == g]
+        mx = {q: max(fixtures[k][q] for k in members) for q in FX.KINDS}
+        groups[g] = {"max": mx, "tol": {q: 10.0 * v for q, v in mx.items()}}
+    for name, f in fixtures.items():
+        tol = groups[FX.group(name)]["tol"]
+        f["borderline"] = len(FX.borderline(name, tol))
+        f["matches"] = int((FX.reference(name).match >= 0).sum())
+        f["valid"] = not FX.guard(name, tol)
+    return {"replicas": [[n, vars(v)] for n, v in FX.REPLICAS], "fixtures": fixtures, "groups": groups}
+
+
+def main():
+    m = measure()
+    bad = [k for k, f in m["fixtures"].items() if not f["valid"]]
+    for k in bad:
+        print("invalid fixture", k, FX.guard(k, m["groups"][FX.group(k)]["tol"]))
+    with open(FX.MARGINS, "w") as f:
+        json.dump(m, f, indent=1, sort_keys=True)
+        f.write("\n")
+    for g, v in m["groups"].items():
+        print(g, {q: "%.3g" % t for q, t in v["tol"].items()})
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
