@@ -25,7 +25,7 @@ HDRS = include/osg.h include/osg_ba.h $(CSRC)/osg_internal.h
 # the RANSAC solvers' shared device helpers and host batch scaffolding
 RANSAC_HDRS = $(CSRC)/ransac_common.h $(CSRC)/batch_io.h $(CSRC)/glibc_math.h
 
-OBJS = $(OBJDIR)/runtime.o $(OBJDIR)/hamming.o $(OBJDIR)/hamming_mfma.o $(OBJDIR)/match.o $(OBJDIR)/pose.o $(OBJDIR)/sim3opt.o $(OBJDIR)/sim3ransac.o $(OBJDIR)/mlpnp.o $(OBJDIR)/twoview.o $(OBJDIR)/essgraph.o $(OBJDIR)/ba.o $(OBJDIR)/dbow.o $(OBJDIR)/kfdb.o $(OBJDIR)/fuse.o $(OBJDIR)/triang.o $(OBJDIR)/newpoints.o $(OBJDIR)/desc.o $(OBJDIR)/sim3.o $(OBJDIR)/init.o $(OBJDIR)/stereo.o $(OBJDIR)/orb.o $(OBJDIR)/fast.o $(OBJDIR)/pyramid.o
+OBJS = $(OBJDIR)/runtime.o $(OBJDIR)/hamming.o $(OBJDIR)/hamming_mfma.o $(OBJDIR)/match.o $(OBJDIR)/pose.o $(OBJDIR)/sim3opt.o $(OBJDIR)/sim3ransac.o $(OBJDIR)/mlpnp.o $(OBJDIR)/twoview.o $(OBJDIR)/essgraph.o $(OBJDIR)/ba.o $(OBJDIR)/dbow.o $(OBJDIR)/kfdb.o $(OBJDIR)/fuse.o $(OBJDIR)/triang.o $(OBJDIR)/newpoints.o $(OBJDIR)/frustum.o $(OBJDIR)/desc.o $(OBJDIR)/sim3.o $(OBJDIR)/init.o $(OBJDIR)/stereo.o $(OBJDIR)/orb.o $(OBJDIR)/fast.o $(OBJDIR)/pyramid.o
 
 WALL_BENCH = tools/adapter_wall_bench
 
@@ -40,7 +40,7 @@ $(OBJDIR)/hamming.o: $(CSRC)/hamming.hip $(HDRS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
 $(OBJDIR)/hamming_mfma.o: $(CSRC)/hamming_mfma.hip $(HDRS) $(CSRC)/top2_key.h $(CSRC)/top2_ring.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(OBJDIR)/match.o: $(CSRC)/match.hip $(HDRS) $(CSRC)/match_common.h | $(OBJDIR)
+$(OBJDIR)/match.o: $(CSRC)/match.hip $(HDRS) $(CSRC)/match_common.h $(CSRC)/frustum_common.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
 $(OBJDIR)/pose.o: $(CSRC)/pose.hip $(HDRS) $(CSRC)/ba_common.h $(CSRC)/exact_math.h $(CSRC)/glibc_math.h $(CSRC)/match_common.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
@@ -68,6 +68,9 @@ $(OBJDIR)/triang.o: $(CSRC)/triang.hip $(HDRS) $(CSRC)/match_common.h $(CSRC)/kb
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
 
 $(OBJDIR)/newpoints.o: $(CSRC)/newpoints.hip $(HDRS) $(CSRC)/kb8_epipolar.h $(RANSAC_HDRS) | $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
+
+$(OBJDIR)/frustum.o: $(CSRC)/frustum.hip $(HDRS) $(CSRC)/frustum_common.h $(RANSAC_HDRS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
 
 $(OBJDIR)/desc.o: $(CSRC)/desc.hip $(HDRS) $(CSRC)/match_common.h | $(OBJDIR)

@@ -351,6 +351,50 @@ struct OsgHooks {
             k.twc[r] = twc(r);
         }
     }
+    // SearchLocalPoints: the constants Frame::isInFrustum[Checks] reads (ref:src/Frame.cc:694, 723, 1618-1628).  mRcw /
+    // mtcw are what UpdatePoseMatrices stored (:601-602: mTcw.rotationMatrix(), mTcw.translation()); the right
+    // camera's mR, mt and twc are formed by the reference's own Eigen expressions
+    static void frustum_frame(Frame &F, osg_frustum_frame &f)
+    {
+        std::memset(&f, 0, sizeof f);
+        const Sophus::SE3f Tcw = F.GetPose();
+        Eigen::Matrix3f mR[2];
+        Eigen::Vector3f mt[2], twc[2];
+        mR[0] = Tcw.rotationMatrix();
+        mt[0] = Tcw.translation();
+        twc[0] = F.GetOw();
+        f.two_cam = F.Nleft != -1;
+        if (f.two_cam) {
+            const Sophus::SE3f Trl = F.GetRelativePoseTrl();
+            const Eigen::Matrix3f Rrl = Trl.rotationMatrix();
+            const Eigen::Vector3f trl = Trl.translation();
+            mR[1] = Rrl * mR[0];
+            mt[1] = Rrl * mt[0] + trl;
+            twc[1] = F.GetRwc() * F.GetRelativePoseTlr().translation() + twc[0];
+        }
+        for (int c = 0; c < (f.two_cam ? 2 : 1); c++) {
+            for (int r = 0; r < 3; r++) {
+                for (int j = 0; j < 3; j++) f.cam[c].R[3 * r + j] = mR[c](r, j);
+                f.cam[c].t[r] = mt[c](r);
+                f.cam[c].c[r] = twc[c](r);
+            }
+            GeometricCamera *cam = c ? F.mpCamera2 : F.mpCamera;
+            f.cam[c].cam_type = cam->GetType() == GeometricCamera::CAM_PINHOLE ? 0 : 1;
+            for (int j = 0; j < 8 && j < (int)cam->size(); j++) f.cam[c].cam[j] = cam->getParameter(j);
+        }
+        f.min_x = Frame::mnMinX, f.max_x = Frame::mnMaxX, f.min_y = Frame::mnMinY, f.max_y = Frame::mnMaxY;
+        f.mbf = F.mbf;
+        f.log_scale_factor = F.mfLogScaleFactor;
+        f.n_levels = F.mnScaleLevels;
+    }
+    // GetDistanceRange: the integration's accessor of the raw mfMaxDistance / mfMinDistance under mMutexPos
+    // (GetMaxDistanceInvariance() / 1.2f is not the stored value)
+    static void mp_frustum(MapPoint *p, float pos[3], float normal[3], float &max_dist, float &min_dist)
+    {
+        const Eigen::Vector3f P = p->GetWorldPos(), Pn = p->GetNormal();
+        for (int k = 0; k < 3; k++) pos[k] = P(k), normal[k] = Pn(k);
+        p->GetDistanceRange(max_dist, min_dist);
+    }
     // KeyFrameDatabase: the vocabulary on the device, set by System right after it loads ORBvoc
     // (osg_vocabulary_load_text) and before it constructs the database
     static const osg_vocabulary *&device_vocabulary()

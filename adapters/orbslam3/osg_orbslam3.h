@@ -22,6 +22,9 @@
 //   static bool  H::fuse_query / H::fuse_sim3_query   see b1/b2 Fuse below
 //   static void  H::set_gba_pose(KeyFrame&, const double q[7], nLoopKF)   mTcwGBA, mnBAGlobalForKF
 //   static void  H::set_gba_pos(MapPoint*, const double x[3], nLoopKF)   mPosGBA, mnBAGlobalForKF
+//   static void  H::frustum_frame(Frame&, osg_frustum_frame&)            what Frame::isInFrustum[Checks] reads of the frame
+//   static void  H::mp_frustum(MapPoint*, float pos[3], float normal[3], float& max_dist, float& min_dist)
+//                GetWorldPos(), GetNormal(), the raw mfMaxDistance / mfMinDistance (SearchLocalPoints below)
 #ifndef OSG_ORBSLAM3_H
 #define OSG_ORBSLAM3_H
 
@@ -3576,6 +3579,152 @@ int create_new_map_points(KeyFrameT *cur, bool monocular, bool inertial, bool co
             if ((status[b * n1 + i] & 0x7f) == OSG_NP_CREATED)
                 on_point(neigh[b], (int)i, (int)match[b * n1 + i], &x3d[3 * (b * n1 + i)]);
     return rc;
+}
+
+// ------------------------------------------------------------------- a5f Tracking::SearchLocalPoints
+// ref:src/Tracking.cc:4097-4182 with Frame::isInFrustum (ref:src/Frame.cc:676-782, :1608-1705) in one
+// osg_search_local_points call.  Hooks:
+//   static void H::frustum_frame(Frame&, osg_frustum_frame&)   mRcw / mtcw / mOw, the right camera's mR / mt / twc by
+//                the expressions of ref:src/Frame.cc:1618-1622, the cameras, bounds, mbf, mfLogScaleFactor
+//   static void H::mp_frustum(MapPoint*, float pos[3], float normal[3], float &max_dist, float &min_dist)
+//                GetWorldPos(), GetNormal(), the raw mfMaxDistance / mfMinDistance
+// LocalPointsGather: the Frame, its slot state, the local MapPoints' inputs (read for candidates only: the
+// reference's two `continue` tests come before any other read) and room for the frustum's outputs.
+template <class H, class FrameT, class MapPointT>
+struct LocalPointsGather {
+    OSG_PINNED_STRUCT(LocalPointsGather);
+    FrameView<FrameT> fv;
+    Slots<MapPointT> slots;
+    osg_frustum_frame ff{};
+    osg_local_points lp{};
+    osg_frustum_result res{};
+    std::vector<float> pos, normal, maxd, mind, prev_depth;
+    std::vector<uint8_t> cand, desc, has_obs, status[2];
+    std::vector<int32_t> id, lvl[2];
+    std::vector<float> px[2], py[2], pxr, vc[2], depth[2];
+    LocalPointsGather() = default;
+    void assign(FrameT &F, const std::vector<MapPointT *> &pts)
+    {
+        fv.assign(F);
+        const int n = (int)pts.size();
+        slots.assign(F.mvpMapPoints, n, true);
+        H::frustum_frame(F, ff);
+        pos.assign(3 * (size_t)n, 0.f);
+        normal.assign(3 * (size_t)n, 0.f);
+        for (auto *v : {&maxd, &mind, &prev_depth, &pxr}) v->assign(n, 0.f);
+        cand.assign(n, 0);
+        has_obs.assign(n, 0);
+        desc.assign(32 * (size_t)n, 0);
+        id.assign(n, 0);
+        for (int c = 0; c < 2; c++) {
+            status[c].assign(n, 0);
+            lvl[c].assign(n, -1);
+            for (auto *v : {&px[c], &py[c], &vc[c], &depth[c]}) v->assign(n, 0.f);
+        }
+        constexpr int PF = 8;
+        for (int i = 0; i < std::min(PF, n); i++) __builtin_prefetch(pts[i]);
+        for (int i = 0; i < n; i++) {
+            if (i + PF < n) prefetch_obj(pts[i + PF]);
+            MapPointT *p = pts[i];
+            id[i] = i;
+            if (p->mnLastFrameSeen == F.mnId) continue;  // ref:src/Tracking.cc:4133
+            if (p->isBad()) continue;                    // :4136
+            cand[i] = 1;
+            H::mp_frustum(p, &pos[3 * (size_t)i], &normal[3 * (size_t)i], maxd[i], mind[i]);
+            prev_depth[i] = p->mTrackDepth;
+            has_obs[i] = p->Observations() > 0;
+            mp_descriptor(p, &desc[(size_t)32 * i]);
+        }
+        lp = osg_local_points{};
+        lp.pts.n = n;
+        lp.pts.pos = pos.data(), lp.pts.normal = normal.data(), lp.pts.max_dist = maxd.data();
+        lp.pts.min_dist = mind.data(), lp.pts.candidate = cand.data(), lp.pts.prev_depth = prev_depth.data();
+        lp.mp_id = id.data(), lp.desc = desc.data(), lp.has_obs = has_obs.data();
+        res = osg_frustum_result{};
+        for (int c = 0; c < 2; c++) {
+            res.status[c] = status[c].data(), res.proj_x[c] = px[c].data(), res.proj_y[c] = py[c].data();
+            res.view_cos[c] = vc[c].data(), res.depth[c] = depth[c].data(), res.level[c] = lvl[c].data();
+        }
+        res.proj_xr = pxr.data();
+    }
+    // the writes Frame::isInFrustum made, by status byte (include/osg.h), then ref:src/Tracking.cc:4140-4150
+    template <class ProjectPoints, class Point2fT>
+    void write_back(const std::vector<MapPointT *> &pts, ProjectPoints &mmProjectPoints, Point2fT) const
+    {
+        const bool rig = ff.two_cam != 0;
+        for (size_t i = 0; i < pts.size(); i++) {
+            const int s0 = status[0][i], s1 = rig ? status[1][i] : 0;
+            if (s0 == OSG_FRUSTUM_NOT_CANDIDATE) continue;
+            MapPointT *p = pts[i];
+            if (!rig) {
+                p->mbTrackInView = s0 == OSG_FRUSTUM_IN_VIEW;
+                p->mTrackProjX = px[0][i];  // -1 below OSG_FRUSTUM_DISTANCE
+                p->mTrackProjY = py[0][i];
+                if (s0 == OSG_FRUSTUM_IN_VIEW) {
+                    p->mTrackProjXR = pxr[i];
+                    p->mTrackDepth = depth[0][i];
+                    p->mnTrackScaleLevel = lvl[0][i];
+                    p->mTrackViewCos = vc[0][i];
+                }
+            } else {
+                p->mbTrackInView = s0 == OSG_FRUSTUM_IN_VIEW;
+                p->mbTrackInViewR = s1 == OSG_FRUSTUM_IN_VIEW;
+                p->mnTrackScaleLevel = lvl[0][i];  // -1 unless in view
+                p->mnTrackScaleLevelR = lvl[1][i];
+                if (s0 == OSG_FRUSTUM_IN_VIEW) {
+                    p->mTrackProjX = px[0][i];
+                    p->mTrackProjY = py[0][i];
+                    p->mTrackViewCos = vc[0][i];
+                    p->mTrackDepth = depth[0][i];
+                }
+                if (s1 == OSG_FRUSTUM_IN_VIEW) {
+                    p->mTrackProjXR = px[1][i];
+                    p->mTrackProjYR = py[1][i];
+                    p->mTrackViewCosR = vc[1][i];
+                    p->mTrackDepthR = depth[1][i];
+                }
+            }
+            if (s0 == OSG_FRUSTUM_IN_VIEW || s1 == OSG_FRUSTUM_IN_VIEW) p->IncreaseVisible();
+            if (p->mbTrackInView) {
+                Point2fT pt;
+                pt.x = p->mTrackProjX, pt.y = p->mTrackProjY;
+                mmProjectPoints[p->mnId] = pt;
+            }
+        }
+    }
+};
+
+// Step 1 (the marking loop) on the host, one osg_search_local_points call for steps 2 and 3, the write-back.
+// th: the caller's choice (ref:src/Tracking.cc:4157-4178).  Returns the matches SearchByProjection made (0 when
+// nothing was in view); on a failing call 0 with the frame's slots and the MapPoints' track fields untouched.
+template <class H, class FrameT, class MapPointT>
+int search_local_points(FrameT &F, const std::vector<MapPointT *> &vpLocalMapPoints, float th, bool bFarPoints,
+                        float thFarPoints, float nnratio = 0.8f)
+{
+    for (auto &pMP : F.mvpMapPoints) {  // ref:src/Tracking.cc:4101-4121
+        if (!pMP) continue;
+        if (pMP->isBad()) {
+            pMP = nullptr;
+        } else {
+            pMP->IncreaseVisible();
+            pMP->mnLastFrameSeen = F.mnId;
+            pMP->mbTrackInView = false;
+            pMP->mbTrackInViewR = false;
+        }
+    }
+    osg_ctx *ctx = thread_ctx();
+    using G = LocalPointsGather<H, FrameT, MapPointT>;
+    G &g = gather_pool<G>(1)[0];
+    g.assign(F, vpLocalMapPoints);
+    const int nm = call(ctx, "osg_search_local_points", [&] {
+        return osg_search_local_points(ctx, &g.fv.v, &g.ff, &g.lp, 0.5f, nnratio, th, bFarPoints, thFarPoints,
+                                       g.slots.mp.data(), g.slots.taken.data(), &g.res);
+    });
+    if (nm < 0) return 0;
+    using Point2fT = typename std::decay<decltype(F.mmProjectPoints.begin()->second)>::type;
+    g.write_back(vpLocalMapPoints, F.mmProjectPoints, Point2fT());
+    if (g.res.n_to_match > 0) g.slots.apply(F.mvpMapPoints, vpLocalMapPoints, (int)vpLocalMapPoints.size());
+    return nm;
 }
 
 }  // namespace osg_orbslam3

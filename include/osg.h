@@ -16,6 +16,10 @@
  *                                ref:src/ORBmatcher.cc:890-1043
  *   osg_search_by_projection_mps   ← ORBmatcher::SearchByProjection(Frame&, const vector<MapPoint*>&, th, bFarPoints, thFar)
  *                                ref:src/ORBmatcher.cc:44-242
+ *   osg_frustum*                   ← Frame::isInFrustum over a frame's local MapPoints
+ *                                ref:src/Frame.cc:676-782, 1608-1705
+ *   osg_search_local_points*       ← steps 2 and 3 of Tracking::SearchLocalPoints (isInFrustum, then the operator above)
+ *                                ref:src/Tracking.cc:4124-4181
  *   osg_search_by_projection_last  ← ORBmatcher::SearchByProjection(Frame&, const Frame&, th, bMono)
  *                                ref:src/ORBmatcher.cc:1957-2191
  *   osg_search_by_projection_kf    ← ORBmatcher::SearchByProjection(Frame&, KeyFrame*, const set<MapPoint*>&, th, ORBdist)
@@ -602,6 +606,107 @@ int osg_create_new_map_points_batch(osg_ctx *ctx, const osg_newpoints_problem *p
                                     osg_newpoints_result *results, int32_t n_problems);
 /* The argument checks of the two calls above alone (host only: no context, no GPU): 0 or the code. */
 int osg_create_new_map_points_check(const osg_newpoints_problem *problem);
+
+/* ---- a5f: Frame::isInFrustum over the local map, and Tracking::SearchLocalPoints -------------------
+ * ref:src/Frame.cc:676-782 (Nleft == -1), :1608-1705 (isInFrustumChecks, a two-camera rig) for every local
+ * MapPoint of a frame (ref:src/Tracking.cc:4128-4151), one lane per (MapPoint, camera), in float and in the
+ * reference's order of operations: Pc = R P + t, |Pc|, the depth test, project, the image test (strict
+ * '<' / '>'), PO = P - c, |PO| against [0.8f * min_dist, 1.2f * max_dist], PO . Pn / dist against
+ * view_cos_limit, PredictScale (ref:src/MapPoint.cc:722-738: ceil(logf(max_dist / dist) /
+ * log_scale_factor) clamped to [0, n_levels - 1]).  Comparisons are IEEE: a NaN compares false, as there.
+ * A sum of three terms runs left to right.  logf is the device's: the level is exact unless
+ * log(ratio) / log_scale_factor lies within a few float ulps of an integer.  A KannalaBrandt8 projection's
+ * cosf / sinf are the device's: parity with libm is unpinned at the last ulp.
+ *
+ * The status byte of each camera tells the caller which writes the reference made:
+ *   Nleft == -1 (camera 0 only): every candidate gets mbTrackInView = false, mTrackProjX = mTrackProjY = -1
+ *     first; from OSG_FRUSTUM_DISTANCE on mTrackProjX / Y = proj_x / proj_y (written at :713 before the tests
+ *     that may still reject the point); OSG_FRUSTUM_IN_VIEW also mbTrackInView = true, mTrackProjXR = proj_xr,
+ *     mTrackDepth, mnTrackScaleLevel, mTrackViewCos.
+ *   rig: every candidate gets both mbTrackInView[R] = false and both levels = -1 first; a camera writes its
+ *     other fields at OSG_FRUSTUM_IN_VIEW only (camera 1: mTrackProjXR / YR = proj_x[1] / proj_y[1],
+ *     mnTrackScaleLevelR, mTrackViewCosR, mTrackDepthR).
+ * Output elements the reference did not write for that status hold 0 (level -1; proj_x / proj_y -1 where
+ * the Nleft == -1 path left -1), except depth[0] in a rig, which then holds prev_depth. */
+#define OSG_FRUSTUM_NOT_CANDIDATE 0
+#define OSG_FRUSTUM_NEG_DEPTH 1
+#define OSG_FRUSTUM_OUTSIDE 2
+#define OSG_FRUSTUM_DISTANCE 3
+#define OSG_FRUSTUM_VIEW_COS 4
+#define OSG_FRUSTUM_IN_VIEW 5
+
+typedef struct osg_frustum_camera {
+    float R[9];        /* row-major.  Left: mRcw.  Right: Rrl * mRcw (ref:src/Frame.cc:1620) */
+    float t[3];        /* mtcw.  Right: Rrl * mtcw + trl (:1621) */
+    float c[3];        /* mOw.  Right: mRwc * mTlr.translation() + mOw (:1622) */
+    int32_t cam_type;  /* 0 Pinhole, 1 KannalaBrandt8 */
+    float cam[8];      /* mvParameters: fx fy cx cy [k0 k1 k2 k3] */
+} osg_frustum_camera;
+
+typedef struct osg_frustum_frame {
+    int32_t two_cam;            /* Nleft != -1: the rig path, cam[1] is read */
+    osg_frustum_camera cam[2];
+    float min_x, max_x, min_y, max_y; /* mnMinX, mnMaxX, mnMinY, mnMaxY */
+    float mbf;
+    float log_scale_factor;     /* mfLogScaleFactor */
+    int32_t n_levels;           /* mnScaleLevels */
+} osg_frustum_frame;
+
+typedef struct osg_frustum_points {
+    int32_t n;                  /* mvpLocalMapPoints.size(), <= 2^24 */
+    const float *pos;           /* n x 3: GetWorldPos() */
+    const float *normal;        /* n x 3: GetNormal() */
+    const float *max_dist;      /* mfMaxDistance (raw: the 1.2f is applied here) */
+    const float *min_dist;      /* mfMinDistance (raw: the 0.8f is applied here) */
+    const uint8_t *candidate;   /* mnLastFrameSeen != mCurrentFrame.mnId && !isBad() */
+    const float *prev_depth;    /* optional, rig only: mTrackDepth before the call, which SearchByProjection's
+                                   bFarPoints test reads even where only the right camera sees the point; NULL: 0 */
+} osg_frustum_points;
+
+/* Every array may be NULL; index [1] is the right camera of a rig (not written without one). */
+typedef struct osg_frustum_result {
+    uint8_t *status[2];         /* OSG_FRUSTUM_* */
+    float *proj_x[2], *proj_y[2]; /* mTrackProjX / Y; [1]: mTrackProjXR / YR of a rig */
+    float *proj_xr;             /* Nleft == -1: mTrackProjXR = u - mbf * (1 / Pc.z) */
+    float *view_cos[2];
+    float *depth[2];            /* mTrackDepth, mTrackDepthR */
+    int32_t *level[2];          /* mnTrackScaleLevel[R] */
+    int32_t n_to_match;         /* out: candidates in view in either camera (nToMatch) */
+} osg_frustum_result;
+
+/* Returns n_to_match (>= 0) or an OSG_E_* code. */
+int osg_frustum(osg_ctx *ctx, const osg_frustum_frame *frame, const osg_frustum_points *points,
+                float view_cos_limit, osg_frustum_result *result);
+/* B frames in one launch (B <= 65535), each with its own points; returns OSG_OK, results[b].n_to_match. */
+int osg_frustum_batch(osg_ctx *ctx, const osg_frustum_frame *frames, const osg_frustum_points *points, int32_t B,
+                      float view_cos_limit, osg_frustum_result *results);
+/* The argument checks of the calls above alone (host only: no context, no GPU): 0 or OSG_E_INVALID. */
+int osg_frustum_check(const osg_frustum_frame *frame, const osg_frustum_points *points);
+
+/* Tracking::SearchLocalPoints' steps 2 and 3 (ref:src/Tracking.cc:4124-4181) in one call: k_frustum fills the
+ * query fields of osg_mp_queries on the device and the unchanged SearchByProjection kernel of
+ * osg_search_by_projection_mps reads them there, on the same stream, with no host round trip in between.
+ * F->nleft != -1 must agree with frame->two_cam.  result (may be NULL) receives the frustum fields as
+ * osg_frustum returns them.  A frame with n_to_match == 0 returns 0 matches and its slot_mp is left as it
+ * was (ref:src/Tracking.cc:4154); its workgroup of the matcher launch finds no query in view (skipping the
+ * launch itself would take the host round trip this call exists to avoid). */
+typedef struct osg_local_points {
+    osg_frustum_points pts;
+    const int32_t *mp_id;       /* as osg_mp_queries */
+    const uint8_t *desc;        /* n x 32 */
+    const uint8_t *has_obs;
+} osg_local_points;
+
+/* Returns nmatches (>= 0) or an OSG_E_* code. */
+int osg_search_local_points(osg_ctx *ctx, const osg_frame *F, const osg_frustum_frame *frame,
+                            const osg_local_points *points, float view_cos_limit, float nnratio, float th,
+                            int far_points, float th_far_points, int32_t *slot_mp, const uint8_t *slot_taken,
+                            osg_frustum_result *result);
+/* B frames; slot arrays concatenated by F[b].n as in osg_search_by_projection_mps_batch; results may be NULL. */
+int osg_search_local_points_batch(osg_ctx *ctx, const osg_frame *F, const osg_frustum_frame *frames,
+                                  const osg_local_points *points, int32_t B, float view_cos_limit, float nnratio,
+                                  float th, int far_points, float th_far_points, int32_t *slot_mp,
+                                  const uint8_t *slot_taken, int32_t *nmatches, osg_frustum_result *results);
 
 /* ---- b4: MapPoint::ComputeDistinctiveDescriptors ------------------------------------------------
  * ref:src/MapPoint.cc:444-535, for a list of MapPoints at once (LocalMapping runs it for every MapPoint

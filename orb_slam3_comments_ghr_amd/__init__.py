@@ -16,7 +16,7 @@ from . import _abi
 from ._abi import LIB_PATH
 
 __all__ = ["load_library", "Context", "OsgError", "LIB_PATH", "TwoViewReconstruction", "draw_sets",
-           "CreateNewMapPoints"]
+           "CreateNewMapPoints", "frustum", "frustum_batch", "search_local_points", "search_local_points_batch"]
 
 _lib = None
 
@@ -219,4 +219,9 @@ def __getattr__(name):
     if name in ("CreateNewMapPoints", "NewPointsProblem", "NpKeyFrame"):
         from . import localmapping
         return getattr(localmapping, name)
+    # Tracking's per-frame projection of the local map, likewise
+    if name in ("frustum", "frustum_batch", "search_local_points", "search_local_points_batch", "FrustumFrame",
+                "FrustumCamera", "LocalPoints"):
+        from . import tracking
+        return getattr(tracking, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

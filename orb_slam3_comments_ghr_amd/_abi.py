@@ -127,6 +127,32 @@ NP_REPROJ1, NP_REPROJ2, NP_ZERO_DIST, NP_FAR, NP_SCALE = 6, 7, 8, 9, 10
 NP_STEREO_BIT = 0x80
 
 
+FRUSTUM_NOT_CANDIDATE, FRUSTUM_NEG_DEPTH, FRUSTUM_OUTSIDE, FRUSTUM_DISTANCE, FRUSTUM_VIEW_COS, FRUSTUM_IN_VIEW = range(6)
+
+
+class OsgFrustumCamera(C.Structure):
+    _fields_ = [("R", f32 * 9), ("t", f32 * 3), ("c", f32 * 3), ("cam_type", i32), ("cam", f32 * 8)]
+
+
+class OsgFrustumFrame(C.Structure):
+    _fields_ = [("two_cam", i32), ("cam", OsgFrustumCamera * 2), ("min_x", f32), ("max_x", f32), ("min_y", f32),
+                ("max_y", f32), ("mbf", f32), ("log_scale_factor", f32), ("n_levels", i32)]
+
+
+class OsgFrustumPoints(C.Structure):
+    _fields_ = [("n", i32), ("pos", P), ("normal", P), ("max_dist", P), ("min_dist", P), ("candidate", P),
+                ("prev_depth", P)]
+
+
+class OsgFrustumResult(C.Structure):
+    _fields_ = [("status", P * 2), ("proj_x", P * 2), ("proj_y", P * 2), ("proj_xr", P), ("view_cos", P * 2),
+                ("depth", P * 2), ("level", P * 2), ("n_to_match", i32)]
+
+
+class OsgLocalPoints(C.Structure):
+    _fields_ = [("pts", OsgFrustumPoints), ("mp_id", P), ("desc", P), ("has_obs", P)]
+
+
 class OsgImagePyramid(C.Structure):
     _fields_ = [("n_levels", i32), ("on_device", i32), ("data", P), ("rows", P), ("cols", P), ("step", P)]
 
@@ -326,6 +352,8 @@ EXPORTS = [
     "osg_kfdb_select_nbest", "osg_kfdb_select_reloc",
     "osg_fuse_search", "osg_fuse_search_batch", "osg_search_for_triangulation", "osg_search_for_triangulation_batch",
     "osg_create_new_map_points", "osg_create_new_map_points_batch", "osg_create_new_map_points_check",
+    "osg_frustum", "osg_frustum_batch", "osg_frustum_check", "osg_search_local_points",
+    "osg_search_local_points_batch",
     "osg_compute_distinctive_descriptors", "osg_compute_distinctive_descriptors_dev",
     "osg_search_by_projection_sim3", "osg_search_by_projection_sim3_batch", "osg_search_by_sim3",
     "osg_search_for_initialization", "osg_search_for_initialization_batch",
@@ -456,4 +484,12 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.osg_create_new_map_points.argtypes = [vp, C.POINTER(OsgNewPointsProblem), C.POINTER(OsgNewPointsResult)]
     lib.osg_create_new_map_points_batch.argtypes = [vp, vp, vp, i32]
     lib.osg_create_new_map_points_check.argtypes = [C.POINTER(OsgNewPointsProblem)]
+    lib.osg_frustum.argtypes = [vp, C.POINTER(OsgFrustumFrame), C.POINTER(OsgFrustumPoints), f32,
+                                C.POINTER(OsgFrustumResult)]
+    lib.osg_frustum_batch.argtypes = [vp, vp, vp, i32, f32, vp]
+    lib.osg_frustum_check.argtypes = [C.POINTER(OsgFrustumFrame), C.POINTER(OsgFrustumPoints)]
+    lib.osg_search_local_points.argtypes = [vp, C.POINTER(OsgFrame), C.POINTER(OsgFrustumFrame),
+                                            C.POINTER(OsgLocalPoints), f32, f32, f32, C.c_int, f32, vp, vp,
+                                            C.POINTER(OsgFrustumResult)]
+    lib.osg_search_local_points_batch.argtypes = [vp, vp, vp, vp, i32, f32, f32, f32, C.c_int, f32, vp, vp, vp, vp]
     return lib

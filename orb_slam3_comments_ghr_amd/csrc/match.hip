@@ -32,6 +32,7 @@
 #include <type_traits>
 #include <string>
 
+#include "frustum_common.h"
 #include "match_common.h"
 
 // Every MatchArgs array lives in global memory; typing the pointers so (address space 1) makes the
@@ -1462,11 +1463,26 @@ struct MatchCache {
 
 constexpr int STATUS_INTS = 16;
 
+// A step that runs on the device between the upload and the matcher's kernels and writes part of the packed
+// block there (osg_search_local_points: k_frustum fills the query arrays).  The packer bytes from skip_begin
+// on are written by the device only: a launch with more than SKIP_MIN of them uploads around them, a smaller
+// one keeps the single copy (a second copy costs more than a few KiB on the bus).
+struct BatchHook {
+    size_t skip_begin = 0;
+    virtual int finalize(std::deque<Problem> &P, int B, osg_packer &pk) = 0;  // after every problem's prep
+    virtual int before_upload(char *pin, char *dev_in) = 0;                   // the pinned block is filled
+    virtual int enqueue(char *dev_in) = 0;                                    // uploaded; the stream is ctx's
+    virtual int download(char *pin, char *dev_in) = 0;                        // after the matcher's kernels
+    virtual ~BatchHook() = default;
+};
+constexpr size_t SKIP_MIN = size_t(256) << 10;
+
 // Upload every problem's packed inputs and slot arrays, launch one workgroup per problem (growing
 // a problem's candidate buffer when its count pass reports more than the capacity), and download
 // the slot arrays / KF-KF results and the per-problem match counts.
 template <int MODE>
-int run_batch(osg_ctx *ctx, std::deque<Problem> &P, int B, const osg_packer &pk, int32_t *nmatches)
+int run_batch(osg_ctx *ctx, std::deque<Problem> &P, int B, const osg_packer &pk, int32_t *nmatches,
+              BatchHook *hook = nullptr)
 {
     if (B == 0) return OSG_OK;
     // host phase stamps for OSG_MATCH_PROFILE=2: setup, sync + pack, launches, wait, results
@@ -1529,6 +1545,7 @@ int run_batch(osg_ctx *ctx, std::deque<Problem> &P, int B, const osg_packer &pk,
     OSG_ALLOC(ctx, dev_in, SLOT_TMP0, in_bytes + io_pad + args_bytes + 256);
     char *dev_io = dev_in + in_bytes;
     MatchArgs *dev_args = (MatchArgs *)(dev_io + io_pad);
+    if (hook) OSG_RC(hook->before_upload(pin, dev_in));
     // grid modes: the k_grid_* prepass for launches of a few problems (OSG_MATCH_PREPASS=0 / 1 pins it)
     const char *pe = getenv("OSG_MATCH_PREPASS");  // read per call: tests switch it
     const int prepass_env = pe ? atoi(pe) : -1;
@@ -1579,13 +1596,17 @@ int run_batch(osg_ctx *ctx, std::deque<Problem> &P, int B, const osg_packer &pk,
         // re-uploads [io | args] (it must not see the slot arrays written by the problems that fitted
         // the first time)
         if (attempt == 0) hs[2] = hclock::now();
-        if (attempt == 0) OSG_RC(osg_upload(ctx, dev_in, pin, in_bytes + io_pad + args_bytes));
+        if (attempt == 0 && hook && in_bytes - hook->skip_begin > SKIP_MIN) {  // not the device-written tail
+            OSG_RC(osg_upload(ctx, dev_in, pin, hook->skip_begin));
+            OSG_RC(osg_upload(ctx, dev_io, pin_io, io_pad + args_bytes));
+        } else if (attempt == 0) OSG_RC(osg_upload(ctx, dev_in, pin, in_bytes + io_pad + args_bytes));
         if (attempt == 0) hx[1] = hclock::now();
         else OSG_RC(osg_upload(ctx, dev_io, pin_io, io_pad + args_bytes));
         hipEvent_t *ev = osg_ctx_events(ctx);
         if (!ev) return osg_set_error(ctx, OSG_E_HIP, "event create failed");
         OSG_HIP_CHECK(ctx, hipEventRecord(ev[0], ctx->stream));
         if (attempt == 0) hx[2] = hclock::now();
+        if (attempt == 0 && hook) OSG_RC(hook->enqueue(dev_in));
         if (BOW) {
             int max_nq = 0;
             for (int b = 0; b < B; b++) max_nq = std::max(max_nq, P[b].A.prefilled ? P[b].A.nq : 0);
@@ -1626,6 +1647,7 @@ int run_batch(osg_ctx *ctx, std::deque<Problem> &P, int B, const osg_packer &pk,
         OSG_HIP_CHECK(ctx, hipGetLastError());
         if (attempt == 0) hx[3] = hclock::now();
         OSG_HIP_CHECK(ctx, hipEventRecord(ev[1], ctx->stream));
+        if (attempt == 0 && hook) OSG_RC(hook->download(pin, dev_in));
         // status, slot arrays and KF-KF results in one copy (the pinned io block is re-filled from the
         // callers' slots before a retry)
         OSG_RC(osg_download(ctx, pin_io, dev_io, io_bytes));
@@ -2030,7 +2052,7 @@ int prep_bow_kf_kf(osg_ctx *ctx, Problem &P, osg_packer &pk, const osg_bow_side 
 
 // Single and batched entry points share one path: prepare B problems, one launch.
 template <int MODE, typename Prep>
-int run_problems(osg_ctx *ctx, int B, int32_t *nmatches, Prep prep)
+int run_problems(osg_ctx *ctx, int B, int32_t *nmatches, Prep prep, BatchHook *hook = nullptr)
 {
     if (!ctx) return OSG_E_INVALID;
     osg_match_path_clear(ctx);  // a call that is rejected, or launches nothing, reports no launch
@@ -2058,7 +2080,8 @@ int run_problems(osg_ctx *ctx, int B, int32_t *nmatches, Prep prep)
     if (prof_level >= 2)
         fprintf(stderr, "[osg match prep] mode %d B %d: %.1f us\n", MODE, B,
                 std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tp).count());
-    return run_batch<MODE>(ctx, P, B, pk, nmatches);
+    if (hook) OSG_RC(hook->finalize(P, B, pk));
+    return run_batch<MODE>(ctx, P, B, pk, nmatches, hook);
 }
 
 template <int MODE, typename Prep>
@@ -2067,6 +2090,152 @@ int run_single(osg_ctx *ctx, Prep prep)
     int32_t nm = 0;
     const int rc = run_problems<MODE>(ctx, 1, &nm, [&](Problem &P, osg_packer &pk, int) { return prep(P, pk); });
     return rc < 0 ? rc : nm;
+}
+
+// ---- Tracking::SearchLocalPoints: k_frustum (frustum.hip) writes SearchByProjection's query arrays ----------
+// A problem's frustum inputs are a reserved region its prep asks for (filled in the pinned block before the
+// upload: pos / normal are transposed to planes there); the kernel arguments and, after them, the counts and
+// every problem's outputs are reserved once all problems are prepared, so that the device-written part is the
+// tail of the packed block.
+struct LocalPointsHook : BatchHook {
+    osg_ctx *ctx;
+    const osg_frustum_frame *frames;
+    const osg_local_points *points;
+    float limit;
+    int B = 0, max_lanes = 0;
+    std::vector<FrBlock> L;
+    std::vector<size_t> in_off, out_off;
+    size_t prob_off = 0, cnt_off = 0, end_off = 0;
+    char *pin = nullptr;
+
+    LocalPointsHook(osg_ctx *c, const osg_frustum_frame *f, const osg_local_points *p, float lim, int nb)
+        : ctx(c), frames(f), points(p), limit(lim), B(nb), L(nb), in_off(nb, SIZE_MAX), out_off(nb, SIZE_MAX)
+    {
+    }
+    int finalize(std::deque<Problem> &P, int, osg_packer &pk) override
+    {
+        prob_off = pk.reserve(sizeof(FrProb) * (size_t)B);
+        cnt_off = pk.reserve(sizeof(int32_t) * (size_t)B);  // zeroed here, uploaded, then added to by k_frustum
+        skip_begin = pk.total;
+        for (int b = 0; b < B; b++) {
+            const int n = points[b].pts.n;
+            if (n == 0) continue;
+            const bool rig = frames[b].two_cam != 0;
+            const FrBlock &l = L[b];
+            out_off[b] = pk.reserve(l.total - l.in_end);
+            const size_t o = out_off[b] - l.in_end;  // o + l.x: output x in the packed block
+            MatchArgs &A = P[b].A;
+            set_off(A.q_m0, o + l.in_view[0]);
+            set_off(A.q_m1, in_off[b] + l.cand);  // usable: a candidate is not bad
+            set_off(A.q_x, o + l.proj_x[0]);
+            set_off(A.q_y, o + l.proj_y[0]);
+            set_off(A.q_f0, o + l.view_cos[0]);
+            set_off(A.q_f1, o + (rig ? l.proj_x[1] : l.proj_xr));  // mTrackProjXR
+            set_off(A.q_f2, o + l.depth[0]);
+            set_off(A.q_lvl, o + l.level[0]);
+            if (rig) {
+                A.q_xr = A.q_f1;
+                set_off(A.q_yr, o + l.proj_y[1]);
+                set_off(A.q_f0r, o + l.view_cos[1]);
+                set_off(A.q_lvl_r, o + l.level[1]);
+                set_off(A.q_m0r, o + l.in_view[1]);
+            }
+            max_lanes = std::max(max_lanes, n << (rig ? 1 : 0));
+        }
+        end_off = pk.total;
+        return OSG_OK;
+    }
+    int before_upload(char *pin_, char *dev_in) override
+    {
+        pin = pin_;
+        std::memset(pin + cnt_off, 0, sizeof(int32_t) * (size_t)B);
+        FrProb *hp = (FrProb *)(pin + prob_off);
+        for (int b = 0; b < B; b++) {
+            if (points[b].pts.n == 0) {
+                hp[b] = FrProb{};
+                continue;
+            }
+            osg_frustum_pack_inputs(pin + in_off[b], L[b], &points[b].pts);
+            hp[b] = osg_frustum_prob(&frames[b], points[b].pts.n, limit, L[b], dev_in + in_off[b], dev_in + out_off[b]);
+        }
+        return OSG_OK;
+    }
+    int enqueue(char *dev_in) override
+    {
+        if (max_lanes == 0) return OSG_OK;
+        return osg_frustum_enqueue(ctx, (const FrProb *)(dev_in + prob_off), (int32_t *)(dev_in + cnt_off), B, max_lanes,
+                                   false);
+    }
+    int download(char *pin_, char *dev_in) override
+    {
+        return osg_download(ctx, pin_ + cnt_off, dev_in + cnt_off, end_off - cnt_off);
+    }
+    int n_to_match(int b) const { return ((const int32_t *)(pin + cnt_off))[b]; }
+    void results(int b, osg_frustum_result *r) const
+    {
+        r->n_to_match = n_to_match(b);
+        if (points[b].pts.n > 0)
+            osg_frustum_unpack(pin + out_off[b], L[b], points[b].pts.n, frames[b].two_cam != 0, r);
+    }
+};
+
+int prep_local(osg_ctx *ctx, Problem &P, osg_packer &pk, LocalPointsHook &H, int b, const osg_frame *F, float nnratio,
+               float th, int far_points, float th_far_points, int32_t *slot_mp, const uint8_t *slot_taken)
+{
+    int rc = check_frame(ctx, F);
+    if (rc < 0) return rc;
+    const osg_frustum_frame *ff = &H.frames[b];
+    const osg_local_points *lp = &H.points[b];
+    rc = osg_frustum_check_args(ctx, ff, &lp->pts, b);
+    if (rc < 0) return rc;
+    OSG_REQUIRE(ctx, slot_mp && slot_taken, "null argument");
+    OSG_REQUIRE(ctx, (F->nleft != -1) == (ff->two_cam != 0), "frame nleft = %d but two_cam = %d", F->nleft, ff->two_cam);
+    OSG_REQUIRE(ctx, F->n_levels == ff->n_levels, "frame n_levels = %d but the frustum's is %d", F->n_levels, ff->n_levels);
+    MatchArgs &A = P.A;
+    frame_into_args(A, pk, F);
+    P.host_slot = slot_mp;
+    P.n_slot = F->n;
+    const int n = lp->pts.n;
+    A.nq = n;
+    A.nnratio = nnratio;
+    A.th = th;
+    A.far_points = far_points;
+    A.th_far = th_far_points;
+    if (n == 0) return OSG_OK;
+    OSG_REQUIRE(ctx, lp->desc && lp->mp_id && lp->has_obs, "MapPoint arrays");
+    set_off(A.qdesc, pk.add(lp->desc, (size_t)n * 32));
+    set_off(A.q_mp, pk.add(lp->mp_id, sizeof(int32_t) * n));
+    set_off(A.q_has_obs, pk.add(lp->has_obs, n));
+    set_off(A.slot_taken, pk.add(slot_taken, F->n));
+    H.L[b] = osg_frustum_block(n, ff->two_cam != 0);
+    H.in_off[b] = pk.reserve(H.L[b].in_end);
+    return OSG_OK;
+}
+
+int local_points_run(osg_ctx *ctx, const osg_frame *F, const osg_frustum_frame *frames, const osg_local_points *points,
+                     int B, float limit, float nnratio, float th, int far_points, float th_far_points, int32_t *slot_mp,
+                     const uint8_t *slot_taken, int32_t *nmatches, osg_frustum_result *results)
+{
+    if (!ctx) return OSG_E_INVALID;
+    OSG_REQUIRE(ctx, B >= 0 && B <= 65535 && (B == 0 || (F && frames && points)), "batch size / null argument");
+    LocalPointsHook H(ctx, frames, points, limit, B);
+    size_t off = 0;
+    const int rc = run_problems<MODE_MPS>(
+        ctx, B, nmatches,
+        [&](Problem &P, osg_packer &pk, int b) {
+            OSG_REQUIRE(ctx, slot_mp && slot_taken, "null argument");
+            const int r = prep_local(ctx, P, pk, H, b, &F[b], nnratio, th, far_points, th_far_points, slot_mp + off,
+                                     slot_taken + off);
+            off += F[b].n;
+            return r;
+        },
+        &H);
+    if (rc < 0 || B == 0) return rc;
+    for (int b = 0; b < B; b++) {
+        if (H.n_to_match(b) == 0) nmatches[b] = 0;  // no query was in view
+        if (results) H.results(b, &results[b]);
+    }
+    return OSG_OK;
 }
 
 }  // namespace
@@ -2193,6 +2362,26 @@ int osg_search_by_bow_kf_kf_batch(osg_ctx *ctx, const osg_bow_side *kf1, const o
         off += kf1[b].n;
         return rc;
     });
+}
+
+int osg_search_local_points(osg_ctx *ctx, const osg_frame *F, const osg_frustum_frame *frame,
+                            const osg_local_points *points, float view_cos_limit, float nnratio, float th,
+                            int far_points, float th_far_points, int32_t *slot_mp, const uint8_t *slot_taken,
+                            osg_frustum_result *result)
+{
+    int32_t nm = 0;
+    const int rc = local_points_run(ctx, F, frame, points, 1, view_cos_limit, nnratio, th, far_points, th_far_points,
+                                    slot_mp, slot_taken, &nm, result);
+    return rc < 0 ? rc : nm;
+}
+
+int osg_search_local_points_batch(osg_ctx *ctx, const osg_frame *F, const osg_frustum_frame *frames,
+                                  const osg_local_points *points, int32_t B, float view_cos_limit, float nnratio,
+                                  float th, int far_points, float th_far_points, int32_t *slot_mp,
+                                  const uint8_t *slot_taken, int32_t *nmatches, osg_frustum_result *results)
+{
+    return local_points_run(ctx, F, frames, points, B, view_cos_limit, nnratio, th, far_points, th_far_points, slot_mp,
+                            slot_taken, nmatches, results);
 }
 
 }  // extern "C"

@@ -31,6 +31,15 @@ struct osg_packer {
         total = (total + bytes + 255) & ~size_t(255);
         return off;
     }
+    // a region of `bytes` that no item fills: the caller writes it in the pinned block itself, or a kernel
+    // writes it on the device (k_frustum's outputs, which k_match then reads as its query arrays)
+    size_t reserve(size_t bytes)
+    {
+        if (bytes == 0) return SIZE_MAX;
+        const size_t off = total;
+        total = (total + bytes + 255) & ~size_t(255);
+        return off;
+    }
     // rows src[idx[0]], src[idx[1]], ... of `row` bytes each; idx must stay valid until the fill
     size_t add_rows(const void *src, const int32_t *idx, size_t rows, size_t row)
     {
