@@ -24,6 +24,8 @@ endif
 HDRS = include/osg.h include/osg_ba.h $(CSRC)/osg_internal.h
 # the RANSAC solvers' shared device helpers and host batch scaffolding
 RANSAC_HDRS = $(CSRC)/ransac_common.h $(CSRC)/batch_io.h $(CSRC)/glibc_math.h
+# the pointer-binding packer and the launch sequence of the entry points built on it
+PACKED_HDRS = $(CSRC)/match_common.h $(CSRC)/packed_launch.h
 
 OBJS = $(OBJDIR)/runtime.o $(OBJDIR)/hamming.o $(OBJDIR)/hamming_mfma.o $(OBJDIR)/match.o $(OBJDIR)/pose.o $(OBJDIR)/sim3opt.o $(OBJDIR)/sim3ransac.o $(OBJDIR)/mlpnp.o $(OBJDIR)/twoview.o $(OBJDIR)/essgraph.o $(OBJDIR)/ba.o $(OBJDIR)/dbow.o $(OBJDIR)/kfdb.o $(OBJDIR)/fuse.o $(OBJDIR)/triang.o $(OBJDIR)/newpoints.o $(OBJDIR)/frustum.o $(OBJDIR)/desc.o $(OBJDIR)/sim3.o $(OBJDIR)/init.o $(OBJDIR)/stereo.o $(OBJDIR)/orb.o $(OBJDIR)/fast.o $(OBJDIR)/pyramid.o
 
@@ -61,10 +63,10 @@ $(OBJDIR)/dbow.o: $(CSRC)/dbow.hip $(HDRS) include/osg_dbow.h $(CSRC)/match_comm
 $(OBJDIR)/kfdb.o: $(CSRC)/kfdb.hip $(HDRS) include/osg_dbow.h $(CSRC)/kfdb_select.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
 
-$(OBJDIR)/fuse.o: $(CSRC)/fuse.hip $(HDRS) $(CSRC)/match_common.h | $(OBJDIR)
+$(OBJDIR)/fuse.o: $(CSRC)/fuse.hip $(HDRS) $(PACKED_HDRS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
 
-$(OBJDIR)/triang.o: $(CSRC)/triang.hip $(HDRS) $(CSRC)/match_common.h $(CSRC)/kb8_epipolar.h | $(OBJDIR)
+$(OBJDIR)/triang.o: $(CSRC)/triang.hip $(HDRS) $(PACKED_HDRS) $(CSRC)/kb8_epipolar.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
 
 $(OBJDIR)/newpoints.o: $(CSRC)/newpoints.hip $(HDRS) $(CSRC)/kb8_epipolar.h $(RANSAC_HDRS) | $(OBJDIR)
@@ -76,13 +78,13 @@ $(OBJDIR)/frustum.o: $(CSRC)/frustum.hip $(HDRS) $(CSRC)/frustum_common.h $(RANS
 $(OBJDIR)/desc.o: $(CSRC)/desc.hip $(HDRS) $(CSRC)/match_common.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(OBJDIR)/sim3.o: $(CSRC)/sim3.hip $(HDRS) $(CSRC)/match_common.h | $(OBJDIR)
+$(OBJDIR)/sim3.o: $(CSRC)/sim3.hip $(HDRS) $(PACKED_HDRS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
 
-$(OBJDIR)/init.o: $(CSRC)/init.hip $(HDRS) $(CSRC)/match_common.h | $(OBJDIR)
+$(OBJDIR)/init.o: $(CSRC)/init.hip $(HDRS) $(PACKED_HDRS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
 
-$(OBJDIR)/stereo.o: $(CSRC)/stereo.hip $(HDRS) $(CSRC)/match_common.h | $(OBJDIR)
+$(OBJDIR)/stereo.o: $(CSRC)/stereo.hip $(HDRS) $(PACKED_HDRS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
 
 $(OBJDIR)/orb.o: $(CSRC)/orb.hip $(HDRS) $(CSRC)/match_common.h | $(OBJDIR)

@@ -14,7 +14,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "match_common.h"
+#include "packed_launch.h"
 
 #define GLOBAL __attribute__((address_space(1)))
 
@@ -114,17 +114,6 @@ __global__ __launch_bounds__(FT) void k_fuse(const FuseArgs *__restrict__ args)
     A.out[2 * q + 1] = best;
 }
 
-template <typename T>
-void set_off(T *&field, size_t off)
-{
-    field = (off == SIZE_MAX) ? nullptr : (T *)(uintptr_t)(off + 1);
-}
-template <typename T>
-void relocate(T *&field, char *base)
-{
-    if (field) field = (T *)(base + ((uintptr_t)field - 1));
-}
-
 int fuse_run(osg_ctx *ctx, const osg_frame *KF, const osg_fuse_queries *Q, int B, float th, int right, int gated,
              int32_t *best_idx, int32_t *best_dist, int32_t *nfused)
 {
@@ -165,76 +154,37 @@ int fuse_run(osg_ctx *ctx, const osg_frame *KF, const osg_fuse_queries *Q, int B
             for (int i = 0; F->u_right && i < F->n && !any_ur; i++) any_ur = F->u_right[i] >= 0;
             OSG_REQUIRE(ctx, S->ur || !any_ur, "problem %d: ur needed (keyframe has u_right >= 0)", b);
         }
-        set_off(A.kdesc, pk.add(F->desc, (size_t)F->n * 32));
-        set_off(A.kp_x, pk.add(F->kp_x, sizeof(float) * F->n));
-        set_off(A.kp_y, pk.add(F->kp_y, sizeof(float) * F->n));
-        set_off(A.kp_octave, pk.add(F->kp_octave, sizeof(int32_t) * F->n));
-        if (gated) set_off(A.u_right, pk.add(F->u_right, sizeof(float) * F->n));
+        pk.bind(A.kdesc, F->desc, (size_t)F->n * 32);
+        pk.bind(A.kp_x, F->kp_x, sizeof(float) * F->n);
+        pk.bind(A.kp_y, F->kp_y, sizeof(float) * F->n);
+        pk.bind(A.kp_octave, F->kp_octave, sizeof(int32_t) * F->n);
+        if (gated) pk.bind(A.u_right, F->u_right, sizeof(float) * F->n);
         const int32_t *gs = right ? F->grid_start_r : F->grid_start;
         const int32_t *gi = right ? F->grid_idx_r : F->grid_idx;
-        set_off(A.gs, pk.add(gs, sizeof(int32_t) * (OSG_GRID_CELLS + 1)));
-        set_off(A.gi, pk.add(gi, sizeof(int32_t) * gs[OSG_GRID_CELLS]));
-        set_off(A.scale, pk.add(F->scale_factors, sizeof(float) * F->n_levels));
-        if (gated) set_off(A.inv_s2, pk.add(S->inv_level_sigma2, sizeof(float) * F->n_levels));
-        set_off(A.qdesc, pk.add(S->desc, (size_t)S->n * 32));
-        set_off(A.valid, pk.add(S->valid, S->n));
-        set_off(A.u, pk.add(S->u, sizeof(float) * S->n));
-        set_off(A.v, pk.add(S->v, sizeof(float) * S->n));
-        if (gated) set_off(A.ur, pk.add(S->ur, sizeof(float) * S->n));
-        set_off(A.lvl, pk.add(S->pred_level, sizeof(int32_t) * S->n));
+        pk.bind(A.gs, gs, sizeof(int32_t) * (OSG_GRID_CELLS + 1));
+        pk.bind(A.gi, gi, sizeof(int32_t) * gs[OSG_GRID_CELLS]);
+        pk.bind(A.scale, F->scale_factors, sizeof(float) * F->n_levels);
+        if (gated) pk.bind(A.inv_s2, S->inv_level_sigma2, sizeof(float) * F->n_levels);
+        pk.bind(A.qdesc, S->desc, (size_t)S->n * 32);
+        pk.bind(A.valid, S->valid, S->n);
+        pk.bind(A.u, S->u, sizeof(float) * S->n);
+        pk.bind(A.v, S->v, sizeof(float) * S->n);
+        if (gated) pk.bind(A.ur, S->ur, sizeof(float) * S->n);
+        pk.bind(A.lvl, S->pred_level, sizeof(int32_t) * S->n);
     }
     const size_t nq_total = q_base[B];
     for (int b = 0; b < B; b++) nfused[b] = 0;
     if (nq_total == 0) return OSG_OK;
     OSG_REQUIRE(ctx, best_idx && best_dist, "null output");
-    const size_t in_bytes = (pk.total + 255) & ~size_t(255);
-    const size_t args_bytes = sizeof(FuseArgs) * (size_t)B;
-    const size_t out_bytes = sizeof(int32_t) * 2 * nq_total;
-    char *pin = (char *)osg_pinned(ctx, in_bytes + ((args_bytes + 255) & ~size_t(255)) + out_bytes + 256);
-    if (!pin) return osg_set_error(ctx, OSG_E_NOMEM, "pinned alloc failed");
-    OSG_RC(osg_idle(ctx));  // the pinned block may still be in use
-    pk.fill_parallel(pin, 8);
-    FuseArgs *pin_args = (FuseArgs *)(pin + in_bytes);
-    int32_t *pin_out = (int32_t *)((char *)pin_args + ((args_bytes + 255) & ~size_t(255)));
-    char *dev_in = nullptr;
-    FuseArgs *dev_args = nullptr;
-    int32_t *dev_out = nullptr;
-    OSG_ALLOC(ctx, dev_in, SLOT_TMP0, pk.total + 256);
-    OSG_ALLOC(ctx, dev_args, SLOT_TMP1, args_bytes);
-    OSG_ALLOC(ctx, dev_out, SLOT_TMP2, out_bytes);
-    for (int b = 0; b < B; b++) {
-        FuseArgs &A = args[b];
-        relocate(A.kdesc, dev_in);
-        relocate(A.kp_x, dev_in);
-        relocate(A.kp_y, dev_in);
-        relocate(A.kp_octave, dev_in);
-        relocate(A.u_right, dev_in);
-        relocate(A.gs, dev_in);
-        relocate(A.gi, dev_in);
-        relocate(A.scale, dev_in);
-        relocate(A.inv_s2, dev_in);
-        relocate(A.qdesc, dev_in);
-        relocate(A.valid, dev_in);
-        relocate(A.u, dev_in);
-        relocate(A.v, dev_in);
-        relocate(A.ur, dev_in);
-        relocate(A.lvl, dev_in);
-        A.out = (GLOBAL int32_t *)(dev_out + 2 * q_base[b]);
-        pin_args[b] = A;
-    }
-    OSG_HIP_CHECK(ctx, hipMemcpyAsync(dev_in, pin, pk.total, hipMemcpyHostToDevice, ctx->stream));
-    OSG_HIP_CHECK(ctx, hipMemcpyAsync(dev_args, pin_args, args_bytes, hipMemcpyHostToDevice, ctx->stream));
-    hipEvent_t *ev = osg_ctx_events(ctx);
-    if (!ev) return osg_set_error(ctx, OSG_E_HIP, "event create failed");
-    OSG_HIP_CHECK(ctx, hipEventRecord(ev[0], ctx->stream));
-    hipLaunchKernelGGL(k_fuse, dim3((maxq + FT - 1) / FT, B), dim3(FT), 0, ctx->stream, dev_args);
-    OSG_HIP_CHECK(ctx, hipGetLastError());
-    OSG_HIP_CHECK(ctx, hipEventRecord(ev[1], ctx->stream));
-    OSG_RC(osg_download(ctx, pin_out, dev_out, out_bytes));
-    OSG_RC(osg_wait(ctx));
-    float ms = 0.f;
-    OSG_HIP_CHECK(ctx, hipEventElapsedTime(&ms, ev[0], ev[1]));
-    ctx->last_kernel_ms = ms;
+    osg_packed_launch L(ctx, pk);
+    OSG_RC(L.stage(sizeof(FuseArgs) * (size_t)B, sizeof(int32_t) * 2 * nq_total));
+    OSG_RC(L.alloc());
+    for (int b = 0; b < B; b++) args[b].out = (GLOBAL int32_t *)(L.dev_out<int32_t>() + 2 * q_base[b]);
+    OSG_RC(L.upload(args.data()));
+    OSG_RC(L.start());
+    hipLaunchKernelGGL(k_fuse, dim3((maxq + FT - 1) / FT, B), dim3(FT), 0, ctx->stream, L.dev_args<FuseArgs>());
+    OSG_RC(L.finish());
+    const int32_t *pin_out = L.out<int32_t>();
     for (int b = 0; b < B; b++) {
         int nf = 0;
         for (size_t i = q_base[b]; i < q_base[b + 1]; i++) {

@@ -19,7 +19,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "match_common.h"
+#include "packed_launch.h"
 
 #define GLOBAL __attribute__((address_space(1)))
 
@@ -362,17 +362,6 @@ __global__ __launch_bounds__(IT) void k_init(const InitArgs *__restrict__ args)
     }
 }
 
-template <typename T>
-void set_off(T *&field, size_t off)
-{
-    field = (off == SIZE_MAX) ? nullptr : (T *)(uintptr_t)(off + 1);
-}
-template <typename T>
-void relocate(T *&field, char *base)
-{
-    if (field) field = (T *)(base + ((uintptr_t)field - 1));
-}
-
 struct Problem {
     std::vector<int32_t> q_i1, gs0, gi0, l0_i2;
 };
@@ -427,73 +416,41 @@ int init_run(osg_ctx *ctx, const osg_frame *F1, const osg_frame *F2, float *prev
         A.inv_w = c->grid_inv_w;
         A.inv_h = c->grid_inv_h;
         if (nq == 0 || m0 == 0) continue;
-        set_off(A.q_i1, pk.add(p.q_i1.data(), sizeof(int32_t) * nq));
-        set_off(A.desc1, pk.add(a->desc, (size_t)a->n * 32));
-        set_off(A.ang1, pk.add(a->kp_angle, sizeof(float) * a->n));
-        set_off(A.prev, pk.add(prev_xy + 2 * o_base[b], sizeof(float) * 2 * a->n));
-        set_off(A.desc2, pk.add(c->desc, (size_t)c->n * 32));
-        set_off(A.x2, pk.add(c->kp_x, sizeof(float) * c->n));
-        set_off(A.y2, pk.add(c->kp_y, sizeof(float) * c->n));
-        set_off(A.ang2, pk.add(c->kp_angle, sizeof(float) * c->n));
-        set_off(A.gs0, pk.add(p.gs0.data(), sizeof(int32_t) * (OSG_GRID_CELLS + 1)));
-        set_off(A.gi0, pk.add(p.gi0.data(), sizeof(int32_t) * m0));
-        set_off(A.l0_i2, pk.add(p.l0_i2.data(), sizeof(int32_t) * m0));
+        pk.bind(A.q_i1, p.q_i1.data(), sizeof(int32_t) * nq);
+        pk.bind(A.desc1, a->desc, (size_t)a->n * 32);
+        pk.bind(A.ang1, a->kp_angle, sizeof(float) * a->n);
+        pk.bind(A.prev, prev_xy + 2 * o_base[b], sizeof(float) * 2 * a->n);
+        pk.bind(A.desc2, c->desc, (size_t)c->n * 32);
+        pk.bind(A.x2, c->kp_x, sizeof(float) * c->n);
+        pk.bind(A.y2, c->kp_y, sizeof(float) * c->n);
+        pk.bind(A.ang2, c->kp_angle, sizeof(float) * c->n);
+        pk.bind(A.gs0, p.gs0.data(), sizeof(int32_t) * (OSG_GRID_CELLS + 1));
+        pk.bind(A.gi0, p.gi0.data(), sizeof(int32_t) * m0);
+        pk.bind(A.l0_i2, p.l0_i2.data(), sizeof(int32_t) * m0);
     }
     for (size_t i = 0; i < o_base[B]; i++) m12[i] = -1;
     for (int b = 0; b < B; b++) nmatches[b] = 0;
     if (pk.total == 0) return OSG_OK;
-    const size_t in_bytes = (pk.total + 255) & ~size_t(255);
-    const size_t args_bytes = (sizeof(InitArgs) * (size_t)B + 255) & ~size_t(255);
-    const size_t out_bytes = sizeof(int32_t) * (o_base[B] + 2 * (size_t)B);
-    char *pin = (char *)osg_pinned(ctx, in_bytes + args_bytes + out_bytes + 256);
-    if (!pin) return osg_set_error(ctx, OSG_E_NOMEM, "pinned alloc failed");
-    OSG_RC(osg_idle(ctx));  // the pinned block may still be in use
-    pk.fill_parallel(pin, 8);
-    InitArgs *pin_args = (InitArgs *)(pin + in_bytes);
-    int32_t *pin_out = (int32_t *)((char *)pin_args + args_bytes);
-    char *dev_in = nullptr;
-    InitArgs *dev_args = nullptr;
-    int32_t *dev_out = nullptr, *dev_qoff = nullptr;
+    osg_packed_launch L(ctx, pk);
+    OSG_RC(L.stage(sizeof(InitArgs) * (size_t)B, sizeof(int32_t) * (o_base[B] + 2 * (size_t)B)));
+    OSG_RC(L.alloc());
+    int32_t *dev_out = L.dev_out<int32_t>(), *dev_qoff = nullptr;
     uint32_t *dev_cand = nullptr;
-    OSG_ALLOC(ctx, dev_in, SLOT_TMP0, pk.total + 256);
-    OSG_ALLOC(ctx, dev_args, SLOT_TMP1, args_bytes);
-    OSG_ALLOC(ctx, dev_out, SLOT_TMP2, out_bytes);
     OSG_ALLOC(ctx, dev_cand, SLOT_TMP3, sizeof(uint32_t) * (c_base[B] + 1));
     OSG_ALLOC(ctx, dev_qoff, SLOT_TMP4, sizeof(int32_t) * (q_base[B] + 1));
     for (int b = 0; b < B; b++) {
         InitArgs &A = args[b];
-        relocate(A.q_i1, dev_in);
-        relocate(A.desc1, dev_in);
-        relocate(A.ang1, dev_in);
-        relocate(A.prev, dev_in);
-        relocate(A.desc2, dev_in);
-        relocate(A.x2, dev_in);
-        relocate(A.y2, dev_in);
-        relocate(A.ang2, dev_in);
-        relocate(A.gs0, dev_in);
-        relocate(A.gi0, dev_in);
-        relocate(A.l0_i2, dev_in);
         A.cand = (GLOBAL uint32_t *)(dev_cand + c_base[b]);
         A.qoff = (GLOBAL int32_t *)(dev_qoff + q_base[b]);
         A.m12 = (GLOBAL int32_t *)(dev_out + o_base[b]);
         A.stats = (GLOBAL int32_t *)(dev_out + o_base[B] + 2 * b);
         if (A.nq == 0 || A.m0 == 0) A.nq = 0;  // nothing to match: the kernel only writes the stats
-        pin_args[b] = A;
     }
-    OSG_HIP_CHECK(ctx, hipMemcpyAsync(dev_in, pin, pk.total, hipMemcpyHostToDevice, ctx->stream));
-    OSG_HIP_CHECK(ctx, hipMemcpyAsync(dev_args, pin_args, sizeof(InitArgs) * (size_t)B, hipMemcpyHostToDevice,
-                                      ctx->stream));
-    hipEvent_t *ev = osg_ctx_events(ctx);
-    if (!ev) return osg_set_error(ctx, OSG_E_HIP, "event create failed");
-    OSG_HIP_CHECK(ctx, hipEventRecord(ev[0], ctx->stream));
-    hipLaunchKernelGGL(k_init, dim3(B), dim3(IT), 0, ctx->stream, dev_args);
-    OSG_HIP_CHECK(ctx, hipGetLastError());
-    OSG_HIP_CHECK(ctx, hipEventRecord(ev[1], ctx->stream));
-    OSG_RC(osg_download(ctx, pin_out, dev_out, out_bytes));
-    OSG_RC(osg_wait(ctx));
-    float ms = 0.f;
-    OSG_HIP_CHECK(ctx, hipEventElapsedTime(&ms, ev[0], ev[1]));
-    ctx->last_kernel_ms = ms;
+    OSG_RC(L.upload(args.data()));
+    OSG_RC(L.start());
+    hipLaunchKernelGGL(k_init, dim3(B), dim3(IT), 0, ctx->stream, L.dev_args<InitArgs>());
+    OSG_RC(L.finish());
+    const int32_t *pin_out = L.out<int32_t>();
     int32_t rounds_max = 0, serial = 0;
     for (int b = 0; b < B; b++) {
         const osg_frame *c = &F2[b];

@@ -1404,35 +1404,10 @@ __global__ __launch_bounds__(MT) void k_match(const MatchArgs *__restrict__ args
     }
 }
 
-// Pointer fields of MatchArgs are first filled with packer offsets (+1 so that offset 0 is not
-// confused with "absent"), then relocated against the device block.
-template <typename T>
-void set_off(T *&field, size_t off)
-{
-    field = (off == SIZE_MAX) ? nullptr : (T *)(uintptr_t)(off + 1);
-}
-template <typename T>
-void relocate(T *&field, char *base)
-{
-    if (field) field = (T *)(base + ((uintptr_t)field - 1));
-}
-
-#define OSG_RELOCATE_ALL(A, base)                                                                            \
-    do {                                                                                                     \
-        relocate(A.fdesc, base); relocate(A.kp_x, base); relocate(A.kp_y, base); relocate(A.slot_angle, base); \
-        relocate(A.kp_octave, base); relocate(A.u_right, base); relocate(A.grid_start, base);                \
-        relocate(A.grid_idx, base); relocate(A.scale, base); relocate(A.qdesc, base); relocate(A.q_mp, base); \
-        relocate(A.q_has_obs, base); relocate(A.q_angle, base); relocate(A.q_x, base); relocate(A.q_y, base); \
-        relocate(A.q_f0, base); relocate(A.q_f1, base); relocate(A.q_f2, base); relocate(A.q_lvl, base);     \
-        relocate(A.q_m0, base); relocate(A.q_m1, base); relocate(A.q_cb, base); relocate(A.q_ce, base);     \
-        relocate(A.cand_list, base); relocate(A.slot_ok, base); relocate(A.slot_mp2, base);                  \
-        relocate(A.slot_taken, base); relocate(A.grid_start_r, base); relocate(A.grid_idx_r, base);          \
-        relocate(A.l2r, base); relocate(A.r2l, base); relocate(A.q_xr, base); relocate(A.q_yr, base);       \
-        relocate(A.q_f0r, base); relocate(A.q_lvl_r, base); relocate(A.q_m0r, base);                         \
-    } while (0)
-
 // One problem of a launch: its packed arguments plus host-side bookkeeping.  The vectors hold
-// host-built inputs (BoW query arrays) that must stay alive until the packer copies them.
+// host-built inputs (BoW query arrays) that must stay alive until the packer copies them.  The packer binds
+// the pointer fields of A by address: a Problem lives in MatchCache's deque, which only grows at its end and
+// before a call's first prep, so A does not move between its bindings and run_batch's relocate.
 struct Problem {
     MatchArgs A = {};
     int32_t *host_slot = nullptr;  // slot array (in/out), n_slot entries
@@ -1550,10 +1525,9 @@ int run_batch(osg_ctx *ctx, std::deque<Problem> &P, int B, const osg_packer &pk,
     const char *pe = getenv("OSG_MATCH_PREPASS");  // read per call: tests switch it
     const int prepass_env = pe ? atoi(pe) : -1;
     const bool grid_pre = !BOW && (prepass_env >= 0 ? prepass_env != 0 : B <= GRID_PREPASS_MAX_B);
+    pk.relocate(dev_in);  // every packed input, once (SearchByBoW's host CSR q_off among them)
     for (int b = 0; b < B; b++) {
         MatchArgs &A = P[b].A;
-        OSG_RELOCATE_ALL(A, dev_in);
-        if (BOW && A.prefilled) relocate(A.q_off, dev_in);  // the host CSR (packed input)
         if (grid_pre) A.prefilled = 1;
         A.status = (GLOBAL int32_t *)dev_io + STATUS_INTS * b;
         A.slot_mp = (GLOBAL int32_t *)(dev_io + status_bytes) + slot_off[b];
@@ -1725,22 +1699,22 @@ void frame_into_args(MatchArgs &A, osg_packer &pk, const osg_frame *F)
 {
     A.n_slots = F->n;
     A.nleft = F->nleft;
-    set_off(A.fdesc, pk.add(F->desc, (size_t)F->n * 32));
-    set_off(A.kp_x, pk.add(F->kp_x, sizeof(float) * F->n));
-    set_off(A.kp_y, pk.add(F->kp_y, sizeof(float) * F->n));
-    set_off(A.slot_angle, pk.add(F->kp_angle, sizeof(float) * F->n));
-    set_off(A.kp_octave, pk.add(F->kp_octave, sizeof(int32_t) * F->n));
+    pk.bind(A.fdesc, F->desc, (size_t)F->n * 32);
+    pk.bind(A.kp_x, F->kp_x, sizeof(float) * F->n);
+    pk.bind(A.kp_y, F->kp_y, sizeof(float) * F->n);
+    pk.bind(A.slot_angle, F->kp_angle, sizeof(float) * F->n);
+    pk.bind(A.kp_octave, F->kp_octave, sizeof(int32_t) * F->n);
     // the u_R check runs only for Nleft == -1 (ref:src/ORBmatcher.cc:97, :2055)
-    set_off(A.u_right, F->nleft == -1 ? pk.add(F->u_right, sizeof(float) * F->n) : SIZE_MAX);
-    set_off(A.grid_start, pk.add(F->grid_start, sizeof(int32_t) * (OSG_GRID_CELLS + 1)));
-    set_off(A.grid_idx, pk.add(F->grid_idx, sizeof(int32_t) * F->grid_start[OSG_GRID_CELLS]));
+    pk.bind(A.u_right, F->nleft == -1 ? F->u_right : nullptr, sizeof(float) * F->n);
+    pk.bind(A.grid_start, F->grid_start, sizeof(int32_t) * (OSG_GRID_CELLS + 1));
+    pk.bind(A.grid_idx, F->grid_idx, sizeof(int32_t) * F->grid_start[OSG_GRID_CELLS]);
     if (F->nleft != -1) {
-        set_off(A.grid_start_r, pk.add(F->grid_start_r, sizeof(int32_t) * (OSG_GRID_CELLS + 1)));
-        set_off(A.grid_idx_r, pk.add(F->grid_idx_r, sizeof(int32_t) * F->grid_start_r[OSG_GRID_CELLS]));
-        set_off(A.l2r, pk.add(F->left_to_right, sizeof(int32_t) * F->nleft));
-        set_off(A.r2l, pk.add(F->right_to_left, sizeof(int32_t) * (F->n - F->nleft)));
+        pk.bind(A.grid_start_r, F->grid_start_r, sizeof(int32_t) * (OSG_GRID_CELLS + 1));
+        pk.bind(A.grid_idx_r, F->grid_idx_r, sizeof(int32_t) * F->grid_start_r[OSG_GRID_CELLS]);
+        pk.bind(A.l2r, F->left_to_right, sizeof(int32_t) * F->nleft);
+        pk.bind(A.r2l, F->right_to_left, sizeof(int32_t) * (F->n - F->nleft));
     }
-    set_off(A.scale, pk.add(F->scale_factors, sizeof(float) * F->n_levels));
+    pk.bind(A.scale, F->scale_factors, sizeof(float) * F->n_levels);
     A.n_levels = F->n_levels;
     A.min_x = F->min_x;
     A.max_x = F->max_x;
@@ -1819,24 +1793,24 @@ int prep_mps(osg_ctx *ctx, Problem &P, osg_packer &pk, const osg_frame *F, const
             if (Q->in_view_r[i] && (Q->pred_level_r[i] < -1 || Q->pred_level_r[i] >= F->n_levels))
                 return osg_set_error(ctx, OSG_E_INVALID, "pred_level_r[%d] = %d out of range", i, Q->pred_level_r[i]);
     }
-    set_off(A.qdesc, pk.add(Q->desc, (size_t)n * 32));
-    set_off(A.q_mp, pk.add(Q->mp_id, sizeof(int32_t) * n));
-    set_off(A.q_has_obs, pk.add(Q->has_obs, n));
-    set_off(A.q_m0, pk.add(Q->in_view, n));
-    set_off(A.q_m1, pk.add(Q->usable, n));
-    set_off(A.q_x, pk.add(Q->proj_x, sizeof(float) * n));
-    set_off(A.q_y, pk.add(Q->proj_y, sizeof(float) * n));
-    set_off(A.q_f0, pk.add(Q->view_cos, sizeof(float) * n));
-    set_off(A.q_f1, pk.add(Q->proj_xr, sizeof(float) * n));
-    set_off(A.q_f2, pk.add(Q->track_depth, sizeof(float) * n));
-    set_off(A.q_lvl, pk.add(Q->pred_level, sizeof(int32_t) * n));
-    set_off(A.slot_taken, pk.add(slot_taken, F->n));
+    pk.bind(A.qdesc, Q->desc, (size_t)n * 32);
+    pk.bind(A.q_mp, Q->mp_id, sizeof(int32_t) * n);
+    pk.bind(A.q_has_obs, Q->has_obs, n);
+    pk.bind(A.q_m0, Q->in_view, n);
+    pk.bind(A.q_m1, Q->usable, n);
+    pk.bind(A.q_x, Q->proj_x, sizeof(float) * n);
+    pk.bind(A.q_y, Q->proj_y, sizeof(float) * n);
+    pk.bind(A.q_f0, Q->view_cos, sizeof(float) * n);
+    const size_t o_xr = pk.bind(A.q_f1, Q->proj_xr, sizeof(float) * n);
+    pk.bind(A.q_f2, Q->track_depth, sizeof(float) * n);
+    pk.bind(A.q_lvl, Q->pred_level, sizeof(int32_t) * n);
+    pk.bind(A.slot_taken, slot_taken, F->n);
     if (F->nleft != -1) {
-        A.q_xr = A.q_f1;  // mTrackProjXR
-        set_off(A.q_yr, pk.add(Q->proj_yr, sizeof(float) * n));
-        set_off(A.q_f0r, pk.add(Q->view_cos_r, sizeof(float) * n));
-        set_off(A.q_lvl_r, pk.add(Q->pred_level_r, sizeof(int32_t) * n));
-        set_off(A.q_m0r, pk.add(Q->in_view_r, n));
+        pk.bind_at(A.q_xr, o_xr);  // mTrackProjXR
+        pk.bind(A.q_yr, Q->proj_yr, sizeof(float) * n);
+        pk.bind(A.q_f0r, Q->view_cos_r, sizeof(float) * n);
+        pk.bind(A.q_lvl_r, Q->pred_level_r, sizeof(int32_t) * n);
+        pk.bind(A.q_m0r, Q->in_view_r, n);
     }
     return OSG_OK;
 }
@@ -1863,20 +1837,20 @@ int prep_last(osg_ctx *ctx, Problem &P, osg_packer &pk, const osg_frame *CF, con
     for (int i = 0; i < n; i++)
         if (L->valid[i] && (L->octave[i] < 0 || L->octave[i] >= CF->n_levels))
             return osg_set_error(ctx, OSG_E_INVALID, "octave[%d] out of range", i);
-    set_off(A.qdesc, pk.add(L->desc, (size_t)n * 32));
-    set_off(A.q_mp, pk.add(L->mp_id, sizeof(int32_t) * n));
-    set_off(A.q_has_obs, pk.add(L->has_obs, n));
-    set_off(A.q_m0, pk.add(L->valid, n));
-    set_off(A.q_x, pk.add(L->u, sizeof(float) * n));
-    set_off(A.q_y, pk.add(L->v, sizeof(float) * n));
-    set_off(A.q_f0, pk.add(L->invz, sizeof(float) * n));
-    set_off(A.q_lvl, pk.add(L->octave, sizeof(int32_t) * n));
-    set_off(A.q_angle, pk.add(L->angle, sizeof(float) * n));
-    set_off(A.slot_taken, pk.add(slot_taken, CF->n));
+    pk.bind(A.qdesc, L->desc, (size_t)n * 32);
+    pk.bind(A.q_mp, L->mp_id, sizeof(int32_t) * n);
+    pk.bind(A.q_has_obs, L->has_obs, n);
+    pk.bind(A.q_m0, L->valid, n);
+    pk.bind(A.q_x, L->u, sizeof(float) * n);
+    pk.bind(A.q_y, L->v, sizeof(float) * n);
+    pk.bind(A.q_f0, L->invz, sizeof(float) * n);
+    pk.bind(A.q_lvl, L->octave, sizeof(int32_t) * n);
+    pk.bind(A.q_angle, L->angle, sizeof(float) * n);
+    pk.bind(A.slot_taken, slot_taken, CF->n);
     if (CF->nleft != -1) {
         OSG_REQUIRE(ctx, L->u_r && L->v_r, "right-camera projections (u_r, v_r)");
-        set_off(A.q_xr, pk.add(L->u_r, sizeof(float) * n));
-        set_off(A.q_yr, pk.add(L->v_r, sizeof(float) * n));
+        pk.bind(A.q_xr, L->u_r, sizeof(float) * n);
+        pk.bind(A.q_yr, L->v_r, sizeof(float) * n);
     }
     return OSG_OK;
 }
@@ -1901,13 +1875,13 @@ int prep_kf(osg_ctx *ctx, Problem &P, osg_packer &pk, const osg_frame *CF, const
     for (int i = 0; i < n; i++)
         if (K->valid[i] && (K->pred_level[i] < 0 || K->pred_level[i] >= CF->n_levels))
             return osg_set_error(ctx, OSG_E_INVALID, "pred_level[%d] out of range", i);
-    set_off(A.qdesc, pk.add(K->desc, (size_t)n * 32));
-    set_off(A.q_mp, pk.add(K->mp_id, sizeof(int32_t) * n));
-    set_off(A.q_m0, pk.add(K->valid, n));
-    set_off(A.q_x, pk.add(K->u, sizeof(float) * n));
-    set_off(A.q_y, pk.add(K->v, sizeof(float) * n));
-    set_off(A.q_lvl, pk.add(K->pred_level, sizeof(int32_t) * n));
-    set_off(A.q_angle, pk.add(K->angle, sizeof(float) * n));
+    pk.bind(A.qdesc, K->desc, (size_t)n * 32);
+    pk.bind(A.q_mp, K->mp_id, sizeof(int32_t) * n);
+    pk.bind(A.q_m0, K->valid, n);
+    pk.bind(A.q_x, K->u, sizeof(float) * n);
+    pk.bind(A.q_y, K->v, sizeof(float) * n);
+    pk.bind(A.q_lvl, K->pred_level, sizeof(int32_t) * n);
+    pk.bind(A.q_angle, K->angle, sizeof(float) * n);
     return OSG_OK;
 }
 
@@ -1991,19 +1965,19 @@ int prep_bow_kf_f(osg_ctx *ctx, Problem &P, osg_packer &pk, const osg_bow_side *
     A.nnratio = nnratio;
     A.check_ori = check_orientation;
     if (n == 0) return OSG_OK;
-    set_off(A.fdesc, pk.add(f->desc, (size_t)f->n * 32));
-    set_off(A.slot_angle, pk.add(f->angle, sizeof(float) * f->n));
+    pk.bind(A.fdesc, f->desc, (size_t)f->n * 32);
+    pk.bind(A.slot_angle, f->angle, sizeof(float) * f->n);
     // the queries' descriptor rows, MapPoint ids and angles are gathered from the KeyFrame's arrays
     // straight into the pinned block (P.q_feat lives until the fill)
-    set_off(A.qdesc, pk.add_rows(kf->desc, P.q_feat.data(), n, 32));
-    set_off(A.q_mp, pk.add_rows(kf->mp_id, P.q_feat.data(), n, sizeof(int32_t)));
-    set_off(A.q_angle, pk.add_rows(kf->angle, P.q_feat.data(), n, sizeof(float)));
-    set_off(A.q_cb, pk.add(P.q_cb.data(), sizeof(int32_t) * n));
-    set_off(A.q_ce, pk.add(P.q_ce.data(), sizeof(int32_t) * n));
-    set_off(A.cand_list, pk.add(f->fv.feat, sizeof(int32_t) * f->fv.node_start[f->fv.n_nodes]));
+    pk.bind_rows(A.qdesc, kf->desc, P.q_feat.data(), n, 32);
+    pk.bind_rows(A.q_mp, kf->mp_id, P.q_feat.data(), n, sizeof(int32_t));
+    pk.bind_rows(A.q_angle, kf->angle, P.q_feat.data(), n, sizeof(float));
+    pk.bind(A.q_cb, P.q_cb.data(), sizeof(int32_t) * n);
+    pk.bind(A.q_ce, P.q_ce.data(), sizeof(int32_t) * n);
+    pk.bind(A.cand_list, f->fv.feat, sizeof(int32_t) * f->fv.node_start[f->fv.n_nodes]);
     P.q_off.assign(n + 1, 0);
     for (int i = 0; i < n; i++) P.q_off[i + 1] = P.q_off[i] + (P.q_ce[i] - P.q_cb[i]);
-    set_off(A.q_off, pk.add(P.q_off.data(), sizeof(int32_t) * (n + 1)));
+    pk.bind(A.q_off, P.q_off.data(), sizeof(int32_t) * (n + 1));
     A.prefilled = 1;
     return OSG_OK;
 }
@@ -2033,19 +2007,19 @@ int prep_bow_kf_kf(osg_ctx *ctx, Problem &P, osg_packer &pk, const osg_bow_side 
     A.nnratio = nnratio;
     A.check_ori = check_orientation;
     if (n == 0) return OSG_OK;
-    set_off(A.fdesc, pk.add(kf2->desc, (size_t)kf2->n * 32));
-    set_off(A.slot_angle, pk.add(kf2->angle, sizeof(float) * kf2->n));
-    set_off(A.slot_mp2, pk.add(kf2->mp_id, sizeof(int32_t) * kf2->n));
-    set_off(A.slot_ok, pk.add(P.slot_ok.data(), P.slot_ok.size()));
+    pk.bind(A.fdesc, kf2->desc, (size_t)kf2->n * 32);
+    pk.bind(A.slot_angle, kf2->angle, sizeof(float) * kf2->n);
+    pk.bind(A.slot_mp2, kf2->mp_id, sizeof(int32_t) * kf2->n);
+    pk.bind(A.slot_ok, P.slot_ok.data(), P.slot_ok.size());
     // KF1's query rows and angles gathered straight into the pinned block (as prep_bow_kf_f)
-    set_off(A.qdesc, pk.add_rows(kf1->desc, P.q_feat.data(), n, 32));
-    set_off(A.q_angle, pk.add_rows(kf1->angle, P.q_feat.data(), n, sizeof(float)));
-    set_off(A.q_cb, pk.add(P.q_cb.data(), sizeof(int32_t) * n));
-    set_off(A.q_ce, pk.add(P.q_ce.data(), sizeof(int32_t) * n));
-    set_off(A.cand_list, pk.add(kf2->fv.feat, sizeof(int32_t) * kf2->fv.node_start[kf2->fv.n_nodes]));
+    pk.bind_rows(A.qdesc, kf1->desc, P.q_feat.data(), n, 32);
+    pk.bind_rows(A.q_angle, kf1->angle, P.q_feat.data(), n, sizeof(float));
+    pk.bind(A.q_cb, P.q_cb.data(), sizeof(int32_t) * n);
+    pk.bind(A.q_ce, P.q_ce.data(), sizeof(int32_t) * n);
+    pk.bind(A.cand_list, kf2->fv.feat, sizeof(int32_t) * kf2->fv.node_start[kf2->fv.n_nodes]);
     P.q_off.assign(n + 1, 0);
     for (int i = 0; i < n; i++) P.q_off[i + 1] = P.q_off[i] + (P.q_ce[i] - P.q_cb[i]);
-    set_off(A.q_off, pk.add(P.q_off.data(), sizeof(int32_t) * (n + 1)));
+    pk.bind(A.q_off, P.q_off.data(), sizeof(int32_t) * (n + 1));
     A.prefilled = 1;
     return OSG_OK;
 }
@@ -2061,8 +2035,7 @@ int run_problems(osg_ctx *ctx, int B, int32_t *nmatches, Prep prep, BatchHook *h
     MatchCache &mc = *static_cast<MatchCache *>(ctx->match_cache.get());
     std::deque<Problem> &P = mc.P;
     osg_packer &pk = mc.pk;
-    pk.items.clear();
-    pk.total = 0;
+    pk.clear();
     while ((int)P.size() < B) P.emplace_back();
     static const int prof_level = getenv("OSG_MATCH_PROFILE") ? atoi(getenv("OSG_MATCH_PROFILE")) : 0;
     const auto tp = std::chrono::steady_clock::now();
@@ -2125,20 +2098,21 @@ struct LocalPointsHook : BatchHook {
             out_off[b] = pk.reserve(l.total - l.in_end);
             const size_t o = out_off[b] - l.in_end;  // o + l.x: output x in the packed block
             MatchArgs &A = P[b].A;
-            set_off(A.q_m0, o + l.in_view[0]);
-            set_off(A.q_m1, in_off[b] + l.cand);  // usable: a candidate is not bad
-            set_off(A.q_x, o + l.proj_x[0]);
-            set_off(A.q_y, o + l.proj_y[0]);
-            set_off(A.q_f0, o + l.view_cos[0]);
-            set_off(A.q_f1, o + (rig ? l.proj_x[1] : l.proj_xr));  // mTrackProjXR
-            set_off(A.q_f2, o + l.depth[0]);
-            set_off(A.q_lvl, o + l.level[0]);
+            pk.bind_at(A.q_m0, o + l.in_view[0]);
+            pk.bind_at(A.q_m1, in_off[b] + l.cand);  // usable: a candidate is not bad
+            pk.bind_at(A.q_x, o + l.proj_x[0]);
+            pk.bind_at(A.q_y, o + l.proj_y[0]);
+            pk.bind_at(A.q_f0, o + l.view_cos[0]);
+            const size_t o_xr = o + (rig ? l.proj_x[1] : l.proj_xr);  // mTrackProjXR
+            pk.bind_at(A.q_f1, o_xr);
+            pk.bind_at(A.q_f2, o + l.depth[0]);
+            pk.bind_at(A.q_lvl, o + l.level[0]);
             if (rig) {
-                A.q_xr = A.q_f1;
-                set_off(A.q_yr, o + l.proj_y[1]);
-                set_off(A.q_f0r, o + l.view_cos[1]);
-                set_off(A.q_lvl_r, o + l.level[1]);
-                set_off(A.q_m0r, o + l.in_view[1]);
+                pk.bind_at(A.q_xr, o_xr);
+                pk.bind_at(A.q_yr, o + l.proj_y[1]);
+                pk.bind_at(A.q_f0r, o + l.view_cos[1]);
+                pk.bind_at(A.q_lvl_r, o + l.level[1]);
+                pk.bind_at(A.q_m0r, o + l.in_view[1]);
             }
             max_lanes = std::max(max_lanes, n << (rig ? 1 : 0));
         }
@@ -2203,10 +2177,10 @@ int prep_local(osg_ctx *ctx, Problem &P, osg_packer &pk, LocalPointsHook &H, int
     A.th_far = th_far_points;
     if (n == 0) return OSG_OK;
     OSG_REQUIRE(ctx, lp->desc && lp->mp_id && lp->has_obs, "MapPoint arrays");
-    set_off(A.qdesc, pk.add(lp->desc, (size_t)n * 32));
-    set_off(A.q_mp, pk.add(lp->mp_id, sizeof(int32_t) * n));
-    set_off(A.q_has_obs, pk.add(lp->has_obs, n));
-    set_off(A.slot_taken, pk.add(slot_taken, F->n));
+    pk.bind(A.qdesc, lp->desc, (size_t)n * 32);
+    pk.bind(A.q_mp, lp->mp_id, sizeof(int32_t) * n);
+    pk.bind(A.q_has_obs, lp->has_obs, n);
+    pk.bind(A.slot_taken, slot_taken, F->n);
     H.L[b] = osg_frustum_block(n, ff->two_cam != 0);
     H.in_off[b] = pk.reserve(H.L[b].in_end);
     return OSG_OK;

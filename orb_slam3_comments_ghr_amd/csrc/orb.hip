@@ -149,17 +149,6 @@ __global__ __launch_bounds__(256) void k_orb_desc(const OrbArgs A)
     if ((byte & 3) == 0) A.desc[8 * k + (byte >> 2)] = val;
 }
 
-template <typename T>
-void set_off(T *&field, size_t off)
-{
-    field = (off == SIZE_MAX) ? nullptr : (T *)(uintptr_t)(off + 1);
-}
-template <typename T>
-void relocate(T *&field, char *base)
-{
-    if (field) field = (T *)(base + ((uintptr_t)field - 1));
-}
-
 int check_pyr(osg_ctx *ctx, const osg_image_pyramid *P, int n_levels, const char *which)
 {
     OSG_REQUIRE(ctx, P && P->n_levels >= n_levels && P->n_levels <= MAX_LEVELS && P->data && P->rows && P->cols &&
@@ -185,13 +174,13 @@ void add_levels(osg_packer &pk, const osg_image_pyramid *P, int n_levels, std::v
         }
         step[l] = cols[l];
         if (P->step[l] == cols[l]) {
-            set_off(img[l], pk.add(P->data[l], (size_t)rows[l] * cols[l]));
+            pk.bind(img[l], P->data[l], (size_t)rows[l] * cols[l]);
         } else {
             keep.emplace_back((size_t)rows[l] * cols[l]);
             std::vector<uint8_t> &buf = keep.back();
             for (int r = 0; r < rows[l]; r++)
                 std::memcpy(&buf[(size_t)r * cols[l]], P->data[l] + (size_t)r * P->step[l], cols[l]);
-            set_off(img[l], pk.add(buf.data(), buf.size()));
+            pk.bind(img[l], buf.data(), buf.size());
         }
     }
 }
@@ -244,16 +233,16 @@ int orb_run(osg_ctx *ctx, const osg_image_pyramid *raw, const osg_image_pyramid 
         add_levels(pk, raw, n_levels, keep, A.raw, A.raw_rows, A.raw_cols, A.raw_step);
     }
     add_levels(pk, blurred, n_levels, keep, A.blur, A.blur_rows, A.blur_cols, A.blur_step);
-    set_off(A.x, pk.add(K->x, sizeof(float) * n));
-    set_off(A.y, pk.add(K->y, sizeof(float) * n));
-    set_off(A.level, pk.add(K->level, sizeof(int32_t) * n));
+    pk.bind(A.x, K->x, sizeof(float) * n);
+    pk.bind(A.y, K->y, sizeof(float) * n);
+    pk.bind(A.level, K->level, sizeof(int32_t) * n);
     if (kimg) {
         OSG_REQUIRE(ctx, raw->on_device && blurred->on_device, "batched keypoints need device pyramids");
-        set_off(A.img, pk.add(kimg, sizeof(int32_t) * n));
+        pk.bind(A.img, kimg, sizeof(int32_t) * n);
         A.raw_bstride = raw_bstride;
         A.blur_bstride = blur_bstride;
     }
-    set_off(A.pattern, pk.add(pattern, sizeof(int32_t) * 2 * NPOINTS));
+    pk.bind(A.pattern, pattern, sizeof(int32_t) * 2 * NPOINTS);
     const size_t in_bytes = (pk.total + 255) & ~size_t(255);
     // outputs / exchange: angle n | cs 2n | bad 1 (256-aligned) | desc 32n
     const size_t o_cs = ((size_t)n * 4 + 255) & ~size_t(255);
@@ -268,15 +257,7 @@ int orb_run(osg_ctx *ctx, const osg_image_pyramid *raw, const osg_image_pyramid 
     char *dev_in = nullptr, *dev_out = nullptr;
     OSG_ALLOC(ctx, dev_in, SLOT_TMP0, pk.total + 256);
     OSG_ALLOC(ctx, dev_out, SLOT_TMP2, out_bytes);
-    relocate(A.x, dev_in);
-    relocate(A.y, dev_in);
-    relocate(A.level, dev_in);
-    relocate(A.img, dev_in);
-    relocate(A.pattern, dev_in);
-    for (int l = 0; l < n_levels; l++) {
-        if (compute_angle && !raw->on_device) relocate(A.raw[l], dev_in);
-        if (!blurred->on_device) relocate(A.blur[l], dev_in);
-    }
+    pk.relocate(dev_in);  // device pyramids' levels were never bound
     A.angle = (GLOBAL float *)dev_out;
     A.cs = (GLOBAL const float *)(dev_out + o_cs);
     A.bad = (GLOBAL int32_t *)(dev_out + o_bad);

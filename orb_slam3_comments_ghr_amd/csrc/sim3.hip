@@ -20,7 +20,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "match_common.h"
+#include "packed_launch.h"
 
 #define GLOBAL __attribute__((address_space(1)))
 
@@ -141,17 +141,6 @@ __global__ __launch_bounds__(ST) void k_sim3(const Sim3Args *__restrict__ args)
     if (tid == 0) A.stats[0] = rounds;
 }
 
-template <typename T>
-void set_off(T *&field, size_t off)
-{
-    field = (off == SIZE_MAX) ? nullptr : (T *)(uintptr_t)(off + 1);
-}
-template <typename T>
-void relocate(T *&field, char *base)
-{
-    if (field) field = (T *)(base + ((uintptr_t)field - 1));
-}
-
 // once = 0: the Sim3 projections (slot claims, thr = TH_LOW * ratio, results into slot_query);
 // once = 1: SearchBySim3's searches (thr = TH_HIGH, per-query results into query_best)
 int sim3_run(osg_ctx *ctx, const osg_frame *KF, const osg_fuse_queries *Q, int B, float th, float ratio,
@@ -189,79 +178,46 @@ int sim3_run(osg_ctx *ctx, const osg_frame *KF, const osg_fuse_queries *Q, int B
             OSG_REQUIRE(ctx, sq[i] == -1 || sq[i] == -2, "problem %d: slot_query[%d] must be -1 (free) or -2 (taken)", b, i);
             taken[b][i] = sq[i] == -2;
         }
-        if (S->n == 0) continue;
+        if (S->n == 0) {
+            A.n_slots = 0;  // nothing is packed for it: k_sim3 stages taken0[0 .. n_slots) whatever nq is
+            continue;
+        }
         OSG_REQUIRE(ctx, S->desc && S->valid && S->u && S->v && S->pred_level, "problem %d: query arrays", b);
         for (int i = 0; i < S->n; i++)
             if (S->valid[i] && (S->pred_level[i] < 0 || S->pred_level[i] >= F->n_levels))
                 return osg_set_error(ctx, OSG_E_INVALID, "problem %d: pred_level[%d] = %d out of range", b, i,
                                      S->pred_level[i]);
-        set_off(A.kdesc, pk.add(F->desc, (size_t)F->n * 32));
-        set_off(A.kp_x, pk.add(F->kp_x, sizeof(float) * F->n));
-        set_off(A.kp_y, pk.add(F->kp_y, sizeof(float) * F->n));
-        set_off(A.kp_octave, pk.add(F->kp_octave, sizeof(int32_t) * F->n));
-        set_off(A.gs, pk.add(F->grid_start, sizeof(int32_t) * (OSG_GRID_CELLS + 1)));
-        set_off(A.gi, pk.add(F->grid_idx, sizeof(int32_t) * F->grid_start[OSG_GRID_CELLS]));
-        set_off(A.scale, pk.add(F->scale_factors, sizeof(float) * F->n_levels));
-        set_off(A.taken0, pk.add(taken[b].data(), F->n));
-        set_off(A.qdesc, pk.add(S->desc, (size_t)S->n * 32));
-        set_off(A.valid, pk.add(S->valid, S->n));
-        set_off(A.u, pk.add(S->u, sizeof(float) * S->n));
-        set_off(A.v, pk.add(S->v, sizeof(float) * S->n));
-        set_off(A.lvl, pk.add(S->pred_level, sizeof(int32_t) * S->n));
+        pk.bind(A.kdesc, F->desc, (size_t)F->n * 32);
+        pk.bind(A.kp_x, F->kp_x, sizeof(float) * F->n);
+        pk.bind(A.kp_y, F->kp_y, sizeof(float) * F->n);
+        pk.bind(A.kp_octave, F->kp_octave, sizeof(int32_t) * F->n);
+        pk.bind(A.gs, F->grid_start, sizeof(int32_t) * (OSG_GRID_CELLS + 1));
+        pk.bind(A.gi, F->grid_idx, sizeof(int32_t) * F->grid_start[OSG_GRID_CELLS]);
+        pk.bind(A.scale, F->scale_factors, sizeof(float) * F->n_levels);
+        pk.bind(A.taken0, taken[b].data(), F->n);
+        pk.bind(A.qdesc, S->desc, (size_t)S->n * 32);
+        pk.bind(A.valid, S->valid, S->n);
+        pk.bind(A.u, S->u, sizeof(float) * S->n);
+        pk.bind(A.v, S->v, sizeof(float) * S->n);
+        pk.bind(A.lvl, S->pred_level, sizeof(int32_t) * S->n);
     }
     for (int b = 0; b < B; b++) nmatches[b] = 0;
     const size_t nq_total = q_base[B];
     if (query_best)
         for (size_t i = 0; i < nq_total; i++) query_best[i] = -1;
     if (nq_total == 0) return OSG_OK;
-    const size_t in_bytes = (pk.total + 255) & ~size_t(255);
-    const size_t args_bytes = (sizeof(Sim3Args) * (size_t)B + 255) & ~size_t(255);
-    const size_t out_bytes = sizeof(int32_t) * (nq_total + B);
-    char *pin = (char *)osg_pinned(ctx, in_bytes + args_bytes + out_bytes + 256);
-    if (!pin) return osg_set_error(ctx, OSG_E_NOMEM, "pinned alloc failed");
-    OSG_RC(osg_idle(ctx));  // the pinned block may still be in use
-    pk.fill_parallel(pin, 8);
-    Sim3Args *pin_args = (Sim3Args *)(pin + in_bytes);
-    int32_t *pin_out = (int32_t *)((char *)pin_args + args_bytes);
-    char *dev_in = nullptr;
-    Sim3Args *dev_args = nullptr;
-    int32_t *dev_out = nullptr;
-    OSG_ALLOC(ctx, dev_in, SLOT_TMP0, pk.total + 256);
-    OSG_ALLOC(ctx, dev_args, SLOT_TMP1, args_bytes);
-    OSG_ALLOC(ctx, dev_out, SLOT_TMP2, out_bytes);
+    osg_packed_launch L(ctx, pk);
+    OSG_RC(L.stage(sizeof(Sim3Args) * (size_t)B, sizeof(int32_t) * (nq_total + B)));
+    OSG_RC(L.alloc());
     for (int b = 0; b < B; b++) {
-        Sim3Args &A = args[b];
-        relocate(A.kdesc, dev_in);
-        relocate(A.kp_x, dev_in);
-        relocate(A.kp_y, dev_in);
-        relocate(A.kp_octave, dev_in);
-        relocate(A.gs, dev_in);
-        relocate(A.gi, dev_in);
-        relocate(A.scale, dev_in);
-        relocate(A.taken0, dev_in);
-        relocate(A.qdesc, dev_in);
-        relocate(A.valid, dev_in);
-        relocate(A.u, dev_in);
-        relocate(A.v, dev_in);
-        relocate(A.lvl, dev_in);
-        A.best = (GLOBAL int32_t *)(dev_out + q_base[b]);
-        A.stats = (GLOBAL int32_t *)(dev_out + nq_total + b);
-        pin_args[b] = A;
+        args[b].best = (GLOBAL int32_t *)(L.dev_out<int32_t>() + q_base[b]);
+        args[b].stats = (GLOBAL int32_t *)(L.dev_out<int32_t>() + nq_total + b);
     }
-    OSG_HIP_CHECK(ctx, hipMemcpyAsync(dev_in, pin, pk.total, hipMemcpyHostToDevice, ctx->stream));
-    OSG_HIP_CHECK(ctx, hipMemcpyAsync(dev_args, pin_args, sizeof(Sim3Args) * (size_t)B, hipMemcpyHostToDevice,
-                                      ctx->stream));
-    hipEvent_t *ev = osg_ctx_events(ctx);
-    if (!ev) return osg_set_error(ctx, OSG_E_HIP, "event create failed");
-    OSG_HIP_CHECK(ctx, hipEventRecord(ev[0], ctx->stream));
-    hipLaunchKernelGGL(k_sim3, dim3(B), dim3(ST), 0, ctx->stream, dev_args);
-    OSG_HIP_CHECK(ctx, hipGetLastError());
-    OSG_HIP_CHECK(ctx, hipEventRecord(ev[1], ctx->stream));
-    OSG_RC(osg_download(ctx, pin_out, dev_out, out_bytes));
-    OSG_RC(osg_wait(ctx));
-    float ms = 0.f;
-    OSG_HIP_CHECK(ctx, hipEventElapsedTime(&ms, ev[0], ev[1]));
-    ctx->last_kernel_ms = ms;
+    OSG_RC(L.upload(args.data()));
+    OSG_RC(L.start());
+    hipLaunchKernelGGL(k_sim3, dim3(B), dim3(ST), 0, ctx->stream, L.dev_args<Sim3Args>());
+    OSG_RC(L.finish());
+    const int32_t *pin_out = L.out<int32_t>();
     int32_t rounds_max = 0;
     if (query_best) {
         for (size_t i = 0; i < nq_total; i++) query_best[i] = pin_out[i];

@@ -23,7 +23,7 @@
 #include <cmath>
 #include <vector>
 
-#include "match_common.h"
+#include "packed_launch.h"
 
 #define GLOBAL __attribute__((address_space(1)))
 
@@ -318,20 +318,8 @@ __global__ __launch_bounds__(1024) void k_stereo_filter(const StereoArgs *__rest
     if (tid == 0) A.nmatch[0] = s_cnt;
 }
 
-template <typename T>
-void set_off(T *&field, size_t off)
-{
-    field = (off == SIZE_MAX) ? nullptr : (T *)(uintptr_t)(off + 1);
-}
-template <typename T>
-void relocate(T *&field, char *base)
-{
-    if (field) field = (T *)(base + ((uintptr_t)field - 1));
-}
-
 struct Problem {
     std::vector<std::vector<uint8_t>> lv;  // packed host levels (left 0..L-1, right 0..L-1)
-    bool dev[2] = {false, false};          // pyramid read in place (left, right)
     size_t rs_off = 0, rl_off = 0;         // this frame's vRowIndices CSR in the device row buffer (ints)
 };
 
@@ -396,27 +384,26 @@ int stereo_run(osg_ctx *ctx, const osg_stereo_frame *F, int B, float *u_right, f
         row_ints = p.rl_off + (size_t)S.n_right * (size_t)((int)std::ceil(4.0f * smax) + 3);
         A.rows0 = nRows;
         A.n_right = S.n_right;
-        set_off(A.x, pk.add(S.x, sizeof(float) * S.n));
-        set_off(A.y, pk.add(S.y, sizeof(float) * S.n));
-        set_off(A.oct, pk.add(S.octave, sizeof(int32_t) * S.n));
-        set_off(A.desc, pk.add(S.desc, (size_t)S.n * 32));
-        set_off(A.xr, pk.add(S.xr, sizeof(float) * S.n_right));
-        set_off(A.yr, pk.add(S.yr, sizeof(float) * S.n_right));
-        set_off(A.oct_r, pk.add(S.octave_r, sizeof(int32_t) * S.n_right));
-        set_off(A.desc_r, pk.add(S.desc_r, (size_t)S.n_right * 32));
-        set_off(A.scale, pk.add(S.scale_factors, sizeof(float) * S.n_levels));
-        set_off(A.inv_scale, pk.add(S.inv_scale_factors, sizeof(float) * S.n_levels));
+        pk.bind(A.x, S.x, sizeof(float) * S.n);
+        pk.bind(A.y, S.y, sizeof(float) * S.n);
+        pk.bind(A.oct, S.octave, sizeof(int32_t) * S.n);
+        pk.bind(A.desc, S.desc, (size_t)S.n * 32);
+        pk.bind(A.xr, S.xr, sizeof(float) * S.n_right);
+        pk.bind(A.yr, S.yr, sizeof(float) * S.n_right);
+        pk.bind(A.oct_r, S.octave_r, sizeof(int32_t) * S.n_right);
+        pk.bind(A.desc_r, S.desc_r, (size_t)S.n_right * 32);
+        pk.bind(A.scale, S.scale_factors, sizeof(float) * S.n_levels);
+        pk.bind(A.inv_scale, S.inv_scale_factors, sizeof(float) * S.n_levels);
         p.lv.resize(2 * S.n_levels);
         for (int side = 0; side < 2; side++) {
             const osg_image_pyramid &Y = side ? S.right : S.left;
-            p.dev[side] = Y.on_device != 0;
             for (int l = 0; l < S.n_levels; l++) {
                 const int rows = Y.rows[l], cols = Y.cols[l];
                 (side ? A.rows_r : A.rows_l)[l] = rows;
                 (side ? A.cols_r : A.cols_l)[l] = cols;
                 GLOBAL const uint8_t *&img = side ? A.img_r[l] : A.img_l[l];
                 int &step = side ? A.step_r[l] : A.step_l[l];
-                if (p.dev[side]) {  // device address, kept as is
+                if (Y.on_device) {  // device address, never bound: relocate leaves it as it is
                     img = (GLOBAL const uint8_t *)Y.data[l];
                     step = Y.step[l];
                     continue;
@@ -424,12 +411,12 @@ int stereo_run(osg_ctx *ctx, const osg_stereo_frame *F, int B, float *u_right, f
                 step = cols;
                 const uint8_t *src = Y.data[l];
                 if (Y.step[l] == cols) {
-                    set_off(img, pk.add(src, (size_t)rows * cols));
+                    pk.bind(img, src, (size_t)rows * cols);
                 } else {
                     std::vector<uint8_t> &buf = p.lv[side * S.n_levels + l];
                     buf.resize((size_t)rows * cols);
                     for (int r = 0; r < rows; r++) std::memcpy(&buf[(size_t)r * cols], src + (size_t)r * Y.step[l], cols);
-                    set_off(img, pk.add(buf.data(), buf.size()));
+                    pk.bind(img, buf.data(), buf.size());
                 }
             }
         }
@@ -441,69 +428,38 @@ int stereo_run(osg_ctx *ctx, const osg_stereo_frame *F, int B, float *u_right, f
     for (int b = 0; b < B; b++) nmatches[b] = 0;
     if (o_base[B] == 0) return OSG_OK;
     OSG_REQUIRE(ctx, u_right && depth, "null output");
-    const size_t in_bytes = (pk.total + 255) & ~size_t(255);
-    const size_t args_bytes = (sizeof(StereoArgs) * (size_t)B + 255) & ~size_t(255);
-    const size_t out_bytes = sizeof(int32_t) * (3 * o_base[B] + B);
-    char *pin = (char *)osg_pinned(ctx, in_bytes + args_bytes + out_bytes + 256);
-    if (!pin) return osg_set_error(ctx, OSG_E_NOMEM, "pinned alloc failed");
-    OSG_RC(osg_idle(ctx));  // the pinned block may still be in use
+    osg_packed_launch L(ctx, pk);
+    OSG_RC(L.reserve(sizeof(StereoArgs) * (size_t)B, sizeof(int32_t) * (3 * o_base[B] + B)));
     const hclock::time_point t1 = hclock::now();
-    pk.fill_parallel(pin, 8);
+    L.fill(true);
     const hclock::time_point t2 = hclock::now();
-    StereoArgs *pin_args = (StereoArgs *)(pin + in_bytes);
-    int32_t *pin_out = (int32_t *)((char *)pin_args + args_bytes);
-    char *dev_in = nullptr;
-    StereoArgs *dev_args = nullptr;
-    int32_t *dev_out = nullptr, *dev_rows = nullptr;
-    OSG_ALLOC(ctx, dev_in, SLOT_TMP0, pk.total + 256);
-    OSG_ALLOC(ctx, dev_args, SLOT_TMP1, args_bytes);
-    OSG_ALLOC(ctx, dev_out, SLOT_TMP2, out_bytes);
+    OSG_RC(L.alloc());
+    int32_t *dev_out = L.dev_out<int32_t>(), *dev_rows = nullptr;
     OSG_ALLOC(ctx, dev_rows, SLOT_TMP3, sizeof(int32_t) * row_ints + 256);
     const size_t N = o_base[B];
     for (int b = 0; b < B; b++) {
         StereoArgs &A = args[b];
-        relocate(A.x, dev_in);
-        relocate(A.y, dev_in);
-        relocate(A.oct, dev_in);
-        relocate(A.desc, dev_in);
-        relocate(A.xr, dev_in);
-        relocate(A.yr, dev_in);
-        relocate(A.oct_r, dev_in);
-        relocate(A.desc_r, dev_in);
         A.row_start = (GLOBAL int32_t *)(dev_rows + P[b].rs_off);
         A.row_list = (GLOBAL int32_t *)(dev_rows + P[b].rl_off);
-        relocate(A.scale, dev_in);
-        relocate(A.inv_scale, dev_in);
-        for (int l = 0; l < MAX_LEVELS; l++) {
-            if (!P[b].dev[0]) relocate(A.img_l[l], dev_in);
-            if (!P[b].dev[1]) relocate(A.img_r[l], dev_in);
-        }
         A.ur = (GLOBAL float *)(dev_out + o_base[b]);
         A.depth = (GLOBAL float *)(dev_out + N + o_base[b]);
         A.sad = (GLOBAL int32_t *)(dev_out + 2 * N + o_base[b]);
         A.nmatch = (GLOBAL int32_t *)(dev_out + 3 * N + b);
-        pin_args[b] = A;
     }
-    if (pk.total) OSG_HIP_CHECK(ctx, hipMemcpyAsync(dev_in, pin, pk.total, hipMemcpyHostToDevice, ctx->stream));
-    OSG_HIP_CHECK(ctx, hipMemcpyAsync(dev_args, pin_args, sizeof(StereoArgs) * (size_t)B, hipMemcpyHostToDevice,
-                                      ctx->stream));
-    hipEvent_t *ev = osg_ctx_events(ctx);
-    if (!ev) return osg_set_error(ctx, OSG_E_HIP, "event create failed");
-    OSG_HIP_CHECK(ctx, hipEventRecord(ev[0], ctx->stream));
+    OSG_RC(L.upload(args.data()));
+    OSG_RC(L.start());
+    StereoArgs *dev_args = L.dev_args<StereoArgs>();
     hipLaunchKernelGGL(k_stereo_rows, dim3(B), dim3(1024), 0, ctx->stream, dev_args);
     OSG_HIP_CHECK(ctx, hipGetLastError());
     hipLaunchKernelGGL(k_stereo_match, dim3((maxn + 3) / 4, B), dim3(256), 0, ctx->stream, dev_args);
     OSG_HIP_CHECK(ctx, hipGetLastError());
     hipLaunchKernelGGL(k_stereo_filter, dim3(B), dim3(1024), 0, ctx->stream, dev_args);
-    OSG_HIP_CHECK(ctx, hipGetLastError());
-    OSG_HIP_CHECK(ctx, hipEventRecord(ev[1], ctx->stream));
-    OSG_RC(osg_download(ctx, pin_out, dev_out, out_bytes));
+    OSG_RC(L.download());
     const hclock::time_point t3 = hclock::now();
-    OSG_RC(osg_wait(ctx));
+    OSG_RC(L.wait());
     const hclock::time_point t4 = hclock::now();
-    float ms = 0.f;
-    OSG_HIP_CHECK(ctx, hipEventElapsedTime(&ms, ev[0], ev[1]));
-    ctx->last_kernel_ms = ms;
+    const float ms = L.kernel_ms;
+    const int32_t *pin_out = L.out<int32_t>();
     std::memcpy(u_right, pin_out, sizeof(float) * N);
     std::memcpy(depth, pin_out + N, sizeof(float) * N);
     for (int b = 0; b < B; b++) nmatches[b] = pin_out[3 * N + b];

@@ -21,7 +21,7 @@
 #include <vector>
 
 #include "kb8_epipolar.h"
-#include "match_common.h"
+#include "packed_launch.h"
 
 #define GLOBAL __attribute__((address_space(1)))
 
@@ -182,17 +182,6 @@ __global__ __launch_bounds__(TT) void k_triang(const TriArgs *__restrict__ args)
     if (tid == 0) A.nmatch[0] = s_cnt;
 }
 
-template <typename T>
-void set_off(T *&field, size_t off)
-{
-    field = (off == SIZE_MAX) ? nullptr : (T *)(uintptr_t)(off + 1);
-}
-template <typename T>
-void relocate(T *&field, char *base)
-{
-    if (field) field = (T *)(base + ((uintptr_t)field - 1));
-}
-
 int check_side(osg_ctx *ctx, const osg_kf_side *S, const char *which, int b)
 {
     OSG_REQUIRE(ctx, S->n >= 0, "problem %d: %s n", b, which);
@@ -310,81 +299,41 @@ int triang_run(osg_ctx *ctx, const osg_kf_side *K1, const osg_kf_side *K2, const
             const bool ok = !k2->has_mp[j] && (!only_stereo || stereo2);
             p.flag2[j] = (uint8_t)((ok ? 1 : 0) | (stereo2 ? 2 : 0) | (right2 ? 4 : 0));
         }
-        set_off(A.qdesc, pk.add(p.qdesc.data(), sizeof(uint32_t) * p.qdesc.size()));
-        set_off(A.qx, pk.add(p.qx.data(), sizeof(float) * nq));
-        set_off(A.qy, pk.add(p.qy.data(), sizeof(float) * nq));
-        set_off(A.qang, pk.add(p.qang.data(), sizeof(float) * nq));
-        set_off(A.qsig, pk.add(p.qsig.data(), sizeof(float) * nq));
-        set_off(A.qflag, pk.add(p.qflag.data(), nq));
-        set_off(A.q_cb, pk.add(p.q_cb.data(), sizeof(int32_t) * nq));
-        set_off(A.q_ce, pk.add(p.q_ce.data(), sizeof(int32_t) * nq));
-        set_off(A.cand, pk.add(k2->fv.feat, sizeof(int32_t) * k2->fv.node_start[k2->fv.n_nodes]));
-        set_off(A.desc2, pk.add(k2->desc, (size_t)k2->n * 32));
-        set_off(A.x2, pk.add(k2->kp_x, sizeof(float) * k2->n));
-        set_off(A.y2, pk.add(k2->kp_y, sizeof(float) * k2->n));
-        set_off(A.ang2, pk.add(k2->kp_angle, sizeof(float) * k2->n));
-        set_off(A.oct2, pk.add(k2->kp_octave, sizeof(int32_t) * k2->n));
-        set_off(A.flag2, pk.add(p.flag2.data(), k2->n));
-        set_off(A.scale2, pk.add(k2->scale_factors, sizeof(float) * k2->n_levels));
-        set_off(A.sigma2_2, pk.add(k2->level_sigma2, sizeof(float) * k2->n_levels));
+        pk.bind(A.qdesc, p.qdesc.data(), sizeof(uint32_t) * p.qdesc.size());
+        pk.bind(A.qx, p.qx.data(), sizeof(float) * nq);
+        pk.bind(A.qy, p.qy.data(), sizeof(float) * nq);
+        pk.bind(A.qang, p.qang.data(), sizeof(float) * nq);
+        pk.bind(A.qsig, p.qsig.data(), sizeof(float) * nq);
+        pk.bind(A.qflag, p.qflag.data(), nq);
+        pk.bind(A.q_cb, p.q_cb.data(), sizeof(int32_t) * nq);
+        pk.bind(A.q_ce, p.q_ce.data(), sizeof(int32_t) * nq);
+        pk.bind(A.cand, k2->fv.feat, sizeof(int32_t) * k2->fv.node_start[k2->fv.n_nodes]);
+        pk.bind(A.desc2, k2->desc, (size_t)k2->n * 32);
+        pk.bind(A.x2, k2->kp_x, sizeof(float) * k2->n);
+        pk.bind(A.y2, k2->kp_y, sizeof(float) * k2->n);
+        pk.bind(A.ang2, k2->kp_angle, sizeof(float) * k2->n);
+        pk.bind(A.oct2, k2->kp_octave, sizeof(int32_t) * k2->n);
+        pk.bind(A.flag2, p.flag2.data(), k2->n);
+        pk.bind(A.scale2, k2->scale_factors, sizeof(float) * k2->n_levels);
+        pk.bind(A.sigma2_2, k2->level_sigma2, sizeof(float) * k2->n_levels);
     }
     if (B > 0) OSG_REQUIRE(ctx, match12 || o_base[B] == 0, "null match12");
     for (size_t i = 0; i < o_base[B]; i++) match12[i] = -1;
     for (int b = 0; b < B; b++) nmatches[b] = 0;
     const size_t nq_total = q_base[B];
     if (nq_total == 0) return OSG_OK;
-    const size_t in_bytes = (pk.total + 255) & ~size_t(255);
-    const size_t args_bytes = (sizeof(TriArgs) * (size_t)B + 255) & ~size_t(255);
-    const size_t out_bytes = sizeof(int32_t) * (nq_total + B);
-    char *pin = (char *)osg_pinned(ctx, in_bytes + args_bytes + out_bytes + 256);
-    if (!pin) return osg_set_error(ctx, OSG_E_NOMEM, "pinned alloc failed");
-    OSG_RC(osg_idle(ctx));  // the pinned block may still be in use
-    pk.fill_parallel(pin, 8);
-    TriArgs *pin_args = (TriArgs *)(pin + in_bytes);
-    int32_t *pin_out = (int32_t *)((char *)pin_args + args_bytes);
-    char *dev_in = nullptr;
-    TriArgs *dev_args = nullptr;
-    int32_t *dev_out = nullptr;
-    OSG_ALLOC(ctx, dev_in, SLOT_TMP0, pk.total + 256);
-    OSG_ALLOC(ctx, dev_args, SLOT_TMP1, args_bytes);
-    OSG_ALLOC(ctx, dev_out, SLOT_TMP2, out_bytes);
+    osg_packed_launch L(ctx, pk);
+    OSG_RC(L.stage(sizeof(TriArgs) * (size_t)B, sizeof(int32_t) * (nq_total + B)));
+    OSG_RC(L.alloc());
     for (int b = 0; b < B; b++) {
-        TriArgs &A = args[b];
-        relocate(A.qdesc, dev_in);
-        relocate(A.qx, dev_in);
-        relocate(A.qy, dev_in);
-        relocate(A.qang, dev_in);
-        relocate(A.qsig, dev_in);
-        relocate(A.qflag, dev_in);
-        relocate(A.q_cb, dev_in);
-        relocate(A.q_ce, dev_in);
-        relocate(A.cand, dev_in);
-        relocate(A.desc2, dev_in);
-        relocate(A.x2, dev_in);
-        relocate(A.y2, dev_in);
-        relocate(A.ang2, dev_in);
-        relocate(A.oct2, dev_in);
-        relocate(A.flag2, dev_in);
-        relocate(A.scale2, dev_in);
-        relocate(A.sigma2_2, dev_in);
-        A.out = (GLOBAL int32_t *)(dev_out + q_base[b]);
-        A.nmatch = (GLOBAL int32_t *)(dev_out + nq_total + b);
-        pin_args[b] = A;
+        args[b].out = (GLOBAL int32_t *)(L.dev_out<int32_t>() + q_base[b]);
+        args[b].nmatch = (GLOBAL int32_t *)(L.dev_out<int32_t>() + nq_total + b);
     }
-    OSG_HIP_CHECK(ctx, hipMemcpyAsync(dev_in, pin, pk.total, hipMemcpyHostToDevice, ctx->stream));
-    OSG_HIP_CHECK(ctx, hipMemcpyAsync(dev_args, pin_args, sizeof(TriArgs) * (size_t)B, hipMemcpyHostToDevice,
-                                      ctx->stream));
-    hipEvent_t *ev = osg_ctx_events(ctx);
-    if (!ev) return osg_set_error(ctx, OSG_E_HIP, "event create failed");
-    OSG_HIP_CHECK(ctx, hipEventRecord(ev[0], ctx->stream));
-    hipLaunchKernelGGL(k_triang, dim3(B), dim3(TT), 0, ctx->stream, dev_args);
-    OSG_HIP_CHECK(ctx, hipGetLastError());
-    OSG_HIP_CHECK(ctx, hipEventRecord(ev[1], ctx->stream));
-    OSG_RC(osg_download(ctx, pin_out, dev_out, out_bytes));
-    OSG_RC(osg_wait(ctx));
-    float ms = 0.f;
-    OSG_HIP_CHECK(ctx, hipEventElapsedTime(&ms, ev[0], ev[1]));
-    ctx->last_kernel_ms = ms;
+    OSG_RC(L.upload(args.data()));
+    OSG_RC(L.start());
+    hipLaunchKernelGGL(k_triang, dim3(B), dim3(TT), 0, ctx->stream, L.dev_args<TriArgs>());
+    OSG_RC(L.finish());
+    const int32_t *pin_out = L.out<int32_t>();
     for (int b = 0; b < B; b++) {
         const Problem &p = P[b];
         int32_t *m = match12 + o_base[b];
@@ -498,29 +447,19 @@ int stereo_fisheye_run(osg_ctx *ctx, int32_t n_left, int32_t mono_left, const ui
         OSG_REQUIRE(ctx, oct_right[j] >= 0 && oct_right[j] < n_levels, "right octave %d of row %d", oct_right[j],
                     j);
     osg_packer pk;
-    const size_t o_dl = pk.add(desc_left, 32 * (size_t)n_left), o_dr = pk.add(desc_right, 32 * (size_t)n_right);
-    const size_t o_kl = pk.add(kp_left, 8 * (size_t)n_left), o_kr = pk.add(kp_right, 8 * (size_t)n_right);
-    const size_t o_ol = pk.add(oct_left, 4 * (size_t)n_left), o_or = pk.add(oct_right, 4 * (size_t)n_right);
-    const size_t o_sg = pk.add(level_sigma2, 4 * (size_t)n_levels);
+    FishArgs A{};  // passed by value: bound here, never moved before the launch
+    pk.bind(A.dl, desc_left, 32 * (size_t)n_left);
+    pk.bind(A.dr, desc_right, 32 * (size_t)n_right);
+    pk.bind(A.kl, kp_left, 8 * (size_t)n_left);
+    pk.bind(A.kr, kp_right, 8 * (size_t)n_right);
+    pk.bind(A.ol, oct_left, 4 * (size_t)n_left);
+    pk.bind(A.orr, oct_right, 4 * (size_t)n_right);
+    pk.bind(A.sig2, level_sigma2, 4 * (size_t)n_levels);
     const size_t int_bytes = 4 * ((size_t)n_left + n_right + 1);
-    const size_t out_bytes = int_bytes + 16 * (size_t)n_left;
-    const size_t in_bytes = (pk.total + 255) & ~size_t(255);
-    char *pin = (char *)osg_pinned(ctx, in_bytes + out_bytes + 256);
-    if (!pin) return osg_set_error(ctx, OSG_E_NOMEM, "pinned alloc failed");
-    OSG_RC(osg_idle(ctx));  // the pinned block may still be in use
-    pk.fill(pin);
-    char *pin_out = pin + in_bytes;
-    char *dev_in = nullptr, *dev_out = nullptr;
-    OSG_ALLOC(ctx, dev_in, SLOT_TMP0, pk.total + 256);
-    OSG_ALLOC(ctx, dev_out, SLOT_TMP2, out_bytes);
-    FishArgs A{};
-    A.dl = (const uint4 *)(dev_in + o_dl);
-    A.dr = (const uint4 *)(dev_in + o_dr);
-    A.kl = (const float2 *)(dev_in + o_kl);
-    A.kr = (const float2 *)(dev_in + o_kr);
-    A.ol = (const int32_t *)(dev_in + o_ol);
-    A.orr = (const int32_t *)(dev_in + o_or);
-    A.sig2 = (const float *)(dev_in + o_sg);
+    osg_packed_launch L(ctx, pk);
+    OSG_RC(L.stage(0, int_bytes + 16 * (size_t)n_left, false));
+    OSG_RC(L.alloc());
+    char *dev_out = L.dev_out<char>();
     std::copy(cam_left, cam_left + 8, A.caml);
     std::copy(cam_right, cam_right + 8, A.camr);
     std::copy(Rlr, Rlr + 9, A.R);
@@ -534,20 +473,13 @@ int stereo_fisheye_run(osg_ctx *ctx, int32_t n_left, int32_t mono_left, const ui
     A.nmatch = A.r2l + n_right;
     A.depth = (GLOBAL float *)(dev_out + int_bytes);
     A.p3d = A.depth + n_left;
-    OSG_HIP_CHECK(ctx, hipMemcpyAsync(dev_in, pin, pk.total, hipMemcpyHostToDevice, ctx->stream));
+    OSG_RC(L.upload(nullptr));
     OSG_HIP_CHECK(ctx, hipMemsetAsync(dev_out, 0xff, 4 * ((size_t)n_left + n_right), ctx->stream));
     OSG_HIP_CHECK(ctx, hipMemsetAsync(dev_out + 4 * ((size_t)n_left + n_right), 0, 4, ctx->stream));
-    hipEvent_t *ev = osg_ctx_events(ctx);
-    if (!ev) return osg_set_error(ctx, OSG_E_HIP, "event create failed");
-    OSG_HIP_CHECK(ctx, hipEventRecord(ev[0], ctx->stream));
+    OSG_RC(L.start());
     hipLaunchKernelGGL(k_stereo_fisheye, dim3((nq + 3) / 4), dim3(256), 0, ctx->stream, A);
-    OSG_HIP_CHECK(ctx, hipGetLastError());
-    OSG_HIP_CHECK(ctx, hipEventRecord(ev[1], ctx->stream));
-    OSG_RC(osg_download(ctx, pin_out, dev_out, out_bytes));
-    OSG_RC(osg_wait(ctx));
-    float ms = 0.f;
-    OSG_HIP_CHECK(ctx, hipEventElapsedTime(&ms, ev[0], ev[1]));
-    ctx->last_kernel_ms = ms;
+    OSG_RC(L.finish());
+    const char *pin_out = L.out<char>();
     const int32_t *o_l2r = (const int32_t *)pin_out, *o_r2l = o_l2r + n_left;
     const float *o_depth = (const float *)(pin_out + int_bytes), *o_p3d = o_depth + n_left;
     for (int i = mono_left; i < n_left; i++) {

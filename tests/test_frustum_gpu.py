@@ -134,3 +134,20 @@ def test_nothing_to_match_leaves_slots_alone(ctx):
     nm, out = T.search_local_points(ctx, c.F, frame, pts, th=15.0, slot_mp=slot, slot_taken=c.slot_taken)
     assert out.n_to_match == 0 and nm == 0 and np.array_equal(slot, c.slot_mp)
     assert FX.compare("none", out) == []
+
+
+def test_fused_batch_of_three_with_an_empty_middle(ctx):
+    """a one-camera and a two-camera problem around one without local points (no query array reserved or bound):
+    every problem equals its single call and the reference, the middle one keeps its slots"""
+    names = ("fused_ps", "kr_n0", "fused_kr")
+    cs = [FX.build_fused(n) for n in names]
+    assert [c.points.n > 0 for c in cs] == [True, False, True]
+    slots = [c.slot_mp.copy() for c in cs]
+    nm, outs = T.search_local_points_batch(ctx, [c.F for c in cs], [c.frame for c in cs], [c.points for c in cs],
+                                           th=1.0, slot_mps=slots, slot_takens=[c.slot_taken for c in cs])
+    for b, (name, c) in enumerate(zip(names, cs)):
+        slot = c.slot_mp.copy()
+        n, out = T.search_local_points(ctx, c.F, c.frame, c.points, th=1.0, slot_mp=slot, slot_taken=c.slot_taken)
+        assert n == nm[b] and np.array_equal(slot, slots[b]) and FX.same_bits(out, outs[b]) == [], b
+        assert FX.compare(name, outs[b]) == []
+    assert nm[0] > 0 and nm[2] > 0 and nm[1] == 0 and np.array_equal(slots[1], cs[1].slot_mp)

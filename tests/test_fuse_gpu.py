@@ -71,3 +71,24 @@ def test_fuse_batch(ctx, oracle):
     nf, bis, bds = ORBmatcher(ctx).FuseBatch(KFs, Qs, 3.0)
     for K, Q, n, bi, bd in zip(KFs, Qs, nf, bis, bds):
         check((n, bi, bd), oc.fuse(oracle, K, Q, 3.0), "batch")
+
+
+@pytest.mark.parametrize("kind", ["gated-stereo", "sim3", "right"])
+def test_fuse_batch_of_three_with_an_empty_middle(ctx, oracle, kind):
+    """64-keypoint keyframes with 32 / 0 / 32 MapPoints: every problem of the batch equals its single call and
+    the oracle, and the middle problem, which packs nothing, is left alone.  gated-stereo reads u_right,
+    inv_level_sigma2 and ur; right the right camera's grid and keypoints."""
+    rng = np.random.default_rng(4400)
+    right, sim3 = kind == "right", kind == "sim3"
+    KFs = [fr.synth_frame_two_cam(rng, n_left=64, n_right=64, stereo_frac=0.5) if right
+           else fr.synth_frame(rng, n=64, stereo=True) for _ in range(3)]
+    Qs = [fr.synth_fuse_queries(rng, K, m=n, noise_px=0.5, match_frac=0.9, right=right) for K, n in zip(KFs, (32, 0, 32))]
+    if kind == "gated-stereo":
+        assert all((K.u_right >= 0).any() for K in KFs) and Qs[0].ur is not None
+    m = ORBmatcher(ctx)
+    nf, bis, bds = m.FuseBatch(KFs, Qs, 3.0, bRight=right, sim3=sim3)
+    for K, Q, n, bi, bd in zip(KFs, Qs, nf, bis, bds):
+        ref = oc.fuse(oracle, K, Q, 3.0, right=right, gated=not sim3)
+        check((n, bi, bd), ref, kind + " batch")
+        check(m.Fuse(K, Q, 3.0, bRight=right, sim3=sim3), ref, kind + " single")
+    assert nf[0] > 0 and nf[1] == 0 and nf[2] > 0

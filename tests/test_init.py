@@ -110,3 +110,31 @@ def test_gpu_hand_case_and_edges(ctx, oracle):
     ref = oc.initialization(oracle, F1, F2, far, 100, 0.9, True)
     got = m.SearchForInitialization(F1, F2, far.copy(), 100)
     assert got[0] == ref[0] == 0
+
+
+@pytest.mark.gpu
+def test_gpu_batch_of_three_with_an_empty_middle(ctx, oracle):
+    """osg_search_for_initialization_batch: 64-keypoint pairs, the middle pair with no level-0 F1 keypoint (no
+    query, nothing packed); every problem equals its single call and the oracle."""
+    import ctypes as C
+    from orb_slam3_comments_ghr_amd import _abi
+    rng = np.random.default_rng(9900)
+    trips = [fr.synth_init_pair(rng, n1=64, n2=64, level0=0.5) for _ in range(3)]
+    F1m = trips[1][0]
+    trips[1] = (fr.FrameSoA(desc=F1m.desc, kp_x=F1m.kp_x, kp_y=F1m.kp_y, kp_angle=F1m.kp_angle,
+                            kp_octave=np.maximum(F1m.kp_octave, 1)), trips[1][1], trips[1][2])
+    fa = (_abi.OsgFrame * 3)(*[t[0].struct() for t in trips])
+    fb = (_abi.OsgFrame * 3)(*[t[1].struct() for t in trips])
+    prev = np.ascontiguousarray(np.concatenate([t[2] for t in trips]), np.float32)
+    m12 = np.full(3 * 64, -9, np.int32)
+    nm = np.full(3, -7, np.int32)
+    ctx.check(ctx.lib.osg_search_for_initialization_batch(ctx.handle, C.addressof(fa), C.addressof(fb), 3,
+                                                          prev.ctypes.data, 100, 0.9, 1, m12.ctypes.data,
+                                                          nm.ctypes.data), "SearchForInitialization batch")
+    single = ORBmatcher(ctx, nnratio=0.9, checkOri=True)
+    for b, (F1, F2, p0) in enumerate(trips):
+        ref = oc.initialization(oracle, F1, F2, p0, 100, 0.9, True)
+        same((nm[b], m12[64 * b:64 * (b + 1)], prev[64 * b:64 * (b + 1)]), ref)
+        p = p0.copy()
+        same((*single.SearchForInitialization(F1, F2, p, 100), p), ref)
+    assert nm[0] > 0 and nm[1] == 0 and nm[2] > 0

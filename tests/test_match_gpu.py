@@ -305,3 +305,19 @@ def test_pinned_staging_reused_back_to_back(ctx, oracle):
             s = slot_mp.copy()
             n = m.SearchByProjection(F, Q, 3.0, False, 20.0, slot_mp=s, slot_taken=taken)
             assert_same(f"rep {rep} case {i}", n, s, *ref)
+
+
+@pytest.mark.parametrize("kf2", [False, True])
+def test_batch_bow_of_three_with_an_empty_middle(ctx, oracle, kf2):
+    """64-keypoint pairs (the first a two-camera one), no good MapPoint in the middle pair's KeyFrame (no query,
+    nothing packed): every problem equals its single call and the oracle."""
+    rng = np.random.default_rng(9200 + kf2)
+    pairs = [fr.synth_bow_pair(rng, n_kf=64, n_f=64, n_nodes=6, f_is_kf=kf2, mp_frac=(0.0 if b == 1 else 0.8),
+                               nleft_kf=(32 if b == 0 else -1), nleft_f=(32 if b == 0 else -1)) for b in range(3)]
+    m = ORBmatcher(ctx, 0.9, True)
+    nm, outs = m.SearchByBoWBatch([p[0] for p in pairs], [p[1] for p in pairs], kf2=kf2)
+    for b, (A, Bs) in enumerate(pairs):
+        ref = (oc.bow_kf_kf if kf2 else oc.bow_kf_f)(oracle, A, Bs, 0.9, True)
+        assert_same(f"bow batch of three [{b}]", int(nm[b]), outs[b], *ref)
+        assert_same(f"bow single [{b}]", *m.SearchByBoW(A, Bs, kf2=kf2), *ref)
+    assert nm[0] > 0 and nm[1] == 0 and nm[2] > 0

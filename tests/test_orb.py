@@ -189,3 +189,15 @@ def test_gpu_edges(ctx, oracle):
     wide = torch.zeros((64, 80), dtype=torch.uint8, device="cuda")[:, :64]
     with pytest.raises(OsgError, match="continuous"):
         orb.ORBDescribe(ctx, None, orb.ImagePyramid([wide]), [32.0], [32.0], [0], pat, angle=[0.0])
+
+
+@pytest.mark.gpu
+def test_gpu_one_pyramid_on_the_device(ctx, oracle):
+    """64 keypoints, the raw pyramid alone on the device and then the blurred one alone, the other packed from the
+    host: a device level's address must reach the kernels as given."""
+    rng = np.random.default_rng(13)
+    raw, blur, x, y, level = orb.synth_orb_frame(rng, n=64, fractional=True)
+    pat = orb.synth_pattern(rng)
+    ref = oc.orb_describe(oracle, raw, blur, x, y, level, pat)
+    same(orb.ORBDescribe(ctx, orb.ImagePyramid(raw).to_device(), blur, x, y, level, pat), ref[:2])
+    same(orb.ORBDescribe(ctx, raw, orb.ImagePyramid(blur).to_device(), x, y, level, pat), ref[:2])

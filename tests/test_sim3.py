@@ -149,3 +149,28 @@ def test_search_by_sim3_gpu_empty(ctx):
     q12.valid[:] = 0
     n, m12 = ORBmatcher(ctx).SearchBySim3(K1, K2, q12, q21, 7.5)
     assert n == 0 and (m12 == -1).all()
+
+
+@pytest.mark.gpu
+def test_gpu_projection_batch_of_three_with_an_empty_middle(ctx, oracle):
+    """osg_search_by_projection_sim3_batch: 64-keypoint keyframes with 32 / 0 / 32 MapPoints; every problem equals
+    its single call and the oracle, the middle one (nothing packed) keeps its slots."""
+    import ctypes as C
+    from orb_slam3_comments_ghr_amd import _abi
+    worlds = [world(9250 + b, n=64, m=m) for b, m in enumerate((32, 0, 32))]
+    fa = (_abi.OsgFrame * 3)(*[F.struct() for F, _, _ in worlds])
+    qa = (_abi.OsgFuseQueries * 3)(*[Q.struct() for _, Q, _ in worlds])
+    sq = np.concatenate([s for _, _, s in worlds])
+    nm = np.full(3, -7, np.int32)
+    ctx.check(ctx.lib.osg_search_by_projection_sim3_batch(ctx.handle, C.addressof(fa), C.addressof(qa), 3, 8.0, 1.5,
+                                                          sq.ctypes.data, nm.ctypes.data), "Sim3 projection batch")
+    for b, (F, Q, s0) in enumerate(worlds):
+        n_ref, s_ref = oc.sim3(oracle, F, Q, 8, 1.5, s0)
+        assert nm[b] == n_ref
+        np.testing.assert_array_equal(sq[64 * b:64 * (b + 1)], s_ref)
+        s1 = s0.copy()
+        fs, qs = F.struct(), Q.struct()
+        assert ctx.check(ctx.lib.osg_search_by_projection_sim3(ctx.handle, C.byref(fs), C.byref(qs), 8.0, 1.5,
+                                                               s1.ctypes.data), "Sim3 projection") == n_ref
+        np.testing.assert_array_equal(s1, s_ref)
+    assert nm[0] > 0 and nm[1] == 0 and nm[2] > 0

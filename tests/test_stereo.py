@@ -148,3 +148,25 @@ def test_gpu_device_row_index(ctx, oracle):
     outs, nm = st.ComputeStereoMatchesBatch(ctx, [F, F])
     for (ur, d), k in zip(outs, nm):
         same((ur, d, k), ref)
+
+
+@pytest.mark.gpu
+def test_gpu_batch_of_three_and_one_pyramid_on_the_device(ctx, oracle):
+    """64 keypoints per side.  A batch whose middle frame has no left keypoint (nothing packed) equals the single
+    calls and the oracle; then each side's pyramid alone on the device, the other packed from the host (strided
+    levels of bordered buffers included): a device level's address must reach the kernel as given."""
+    from dataclasses import replace
+    rng = np.random.default_rng(9990)
+    frames = [st.synth_stereo_frame(rng, n=64, bordered=bool(i == 2)) for i in range(3)]
+    F = frames[1]
+    frames[1] = st.StereoFrame(desc=F.desc[:0], x=[], y=[], octave=[], desc_r=F.desc_r, xr=F.xr, yr=F.yr,
+                               octave_r=F.octave_r, left=F.left, right=F.right)
+    refs = [oc.stereo(oracle, f) for f in frames]
+    outs, nm = st.ComputeStereoMatchesBatch(ctx, frames)
+    for f, (ur, d), k, r in zip(frames, outs, nm, refs):
+        same((ur, d, k), r)
+        same(st.ComputeStereoMatches(ctx, f), r)
+    assert refs[0][2] > 0 and refs[1][2] == 0 and refs[2][2] > 0
+    for f, r in ((frames[0], refs[0]), (frames[2], refs[2])):
+        same(st.ComputeStereoMatches(ctx, replace(f, left=f.left.to_device())), r)
+        same(st.ComputeStereoMatches(ctx, replace(f, right=f.right.to_device())), r)

@@ -93,3 +93,18 @@ def test_triang_kb8(ctx, oracle, seed, two_cam, coarse):
     ref = oc.triangulation(oracle, K1, K2, g, coarse=coarse)
     check(ORBmatcher(ctx).SearchForTriangulation(K1, K2, g, bCoarse=coarse), ref, "KB8")
     assert ref[0] > 50
+
+
+def test_triang_batch_of_three_with_an_empty_middle(ctx, oracle):
+    """64-keypoint pairs, every KF1 keypoint of the middle pair with a MapPoint already (no query, nothing
+    packed): every problem equals its single call and the oracle."""
+    rng = np.random.default_rng(7700)
+    pairs = [fr.synth_triang_pair(rng, n1=64, n2=64, n_nodes=8, mp_frac=0.3) for _ in range(3)]
+    pairs[1][0].has_mp[:] = 1
+    m = ORBmatcher(ctx)
+    nm, got = m.SearchForTriangulationBatch([p[0] for p in pairs], [p[1] for p in pairs], [p[2] for p in pairs])
+    for (K1, K2, g), n, pr_ in zip(pairs, nm, got):
+        ref = oc.triangulation(oracle, K1, K2, g)
+        check((n, pr_), ref, "batch of three")
+        check(m.SearchForTriangulation(K1, K2, g), ref, "single")
+    assert nm[0] > 0 and nm[1] == 0 and nm[2] > 0
