@@ -1,0 +1,516 @@
+"""Hand-built boundary fixtures for fuse.hip, sim3.hip, triang.hip's k_triang and init.hip (DESIGN.md,
+"Matcher decisions").  Each case puts named decisions of the reference on both sides of equality; no RNG,
+descriptors are bits(k) so that a distance is a difference of two small integers.  Where a case relies on a
+float landing on one side of a threshold, its builder asserts that in float32 arithmetic.
+
+tests/test_matcher_boundaries.py proves on the CPU that every case is discriminating (the Python
+restatement with that one decision flipped leaves the oracle); tests/test_matcher_boundaries_gpu.py runs the
+kernels on them."""
+from dataclasses import dataclass
+
+import numpy as np
+
+from orb_slam3_comments_ghr_amd import frames as fr
+from tests import oracle_calls as oc
+from tests import pyref_match as pr
+
+f32 = np.float32
+TH = 3.0                  # every Fuse / Sim3 case: the batched entry points take one th
+WINDOW, NNRATIO = 20, 0.9  # every SearchForInitialization case
+FUSE_MODES = ((False, True), (False, False), (True, True), (True, False))  # (bRight, gated)
+SIM3_MODES = (0.7, 1.0, 1.5)                                               # ratioHamming
+TRI_MODES = ((False, False), (True, False), (False, True))                 # (bOnlyStereo, bCoarse)
+PILE_XY = (720.0, 440.0)  # kept free by every initialisation case (pile_up)
+
+
+def bits(k):
+    b = np.zeros(256, np.uint8)
+    b[:k] = 1
+    return np.packbits(b)
+
+
+def up(x):
+    return np.nextafter(f32(x), f32(np.inf))
+
+
+def down(x):
+    return np.nextafter(f32(x), f32(-np.inf))
+
+
+@dataclass
+class Case:
+    name: str
+    kind: str     # fuse | sim3 | bysim3 | tri | init
+    args: tuple   # fuse (F, Q)  sim3 (F, Q, slot_query)  bysim3 (F1, F2, q12, q21)  tri (K1, K2, geom)  init (F1, F2, prev)
+    flips: tuple  # the decisions (pyref_match.FLIPS) the case discriminates
+
+    @property
+    def id(self):
+        return f"{self.kind}-{self.name}"
+
+
+def frame(kps, u_right=None, nleft=-1):
+    """kps: (x, y, octave, descriptor[, angle]) per keypoint."""
+    return fr.FrameSoA(desc=np.stack([k[3] for k in kps]), kp_x=[k[0] for k in kps], kp_y=[k[1] for k in kps],
+                       kp_angle=[k[4] if len(k) > 4 else 0.0 for k in kps], kp_octave=[k[2] for k in kps],
+                       u_right=u_right, nleft=nleft)
+
+
+def queries(qs, F, ur=None, inv=None, valid=None):
+    """qs: (u, v, pred_level, descriptor) per MapPoint."""
+    n = len(qs)
+    return fr.FuseQueries(desc=np.stack([q[3] for q in qs]), valid=np.ones(n, np.uint8) if valid is None else valid,
+                          u=[q[0] for q in qs], v=[q[1] for q in qs], ur=ur, pred_level=[q[2] for q in qs],
+                          inv_level_sigma2=fr.inv_level_sigma2(F.scale) if inv is None else inv)
+
+
+def cell_of(F, x, y):
+    cx, cy = fr.pos_in_grid(np.array([x], f32), np.array([y], f32), F.min_x, F.min_y, F.inv_w, F.inv_h)
+    return int(cx[0]), int(cy[0])
+
+
+# ------------------------------------------------------------------------------------ running a case
+
+def modes(case):
+    if case.kind == "fuse":
+        return tuple(m for m in FUSE_MODES if not m[0] or case.args[0].nleft != -1)
+    return {"sim3": SIM3_MODES, "tri": TRI_MODES}.get(case.kind, (None,))
+
+
+def run_oracle(oracle, case, mode):
+    a = case.args
+    if case.kind == "fuse":
+        return oc.fuse(oracle, a[0], a[1], TH, right=mode[0], gated=mode[1])
+    if case.kind == "sim3":
+        return oc.sim3(oracle, a[0], a[1], TH, mode, a[2])
+    if case.kind == "bysim3":
+        return oc.search_by_sim3(oracle, *a, TH)
+    if case.kind == "tri":
+        return oc.triangulation(oracle, *a, only_stereo=mode[0], coarse=mode[1], ori=True)
+    return oc.initialization(oracle, *a, WINDOW, NNRATIO, True)
+
+
+def run_pyref(case, mode, flip=None):
+    a = case.args
+    if case.kind == "fuse":
+        return pr.fuse_search(a[0], a[1], TH, right=mode[0], gated=mode[1], flip=flip)
+    if case.kind == "sim3":
+        return pr.search_sim3(a[0], a[1], TH, mode, a[2], flip=flip)
+    if case.kind == "bysim3":
+        return pr.search_by_sim3(*a, TH, flip=flip)
+    if case.kind == "tri":
+        return pr.search_for_triangulation(*a, only_stereo=mode[0], coarse=mode[1], ori=True, flip=flip)
+    return pr.search_for_initialization(*a, WINDOW, NNRATIO, True, flip=flip)
+
+
+def same(a, b):
+    return len(a) == len(b) and all(np.array_equal(np.asarray(x), np.asarray(y)) for x, y in zip(a, b))
+
+
+# ------------------------------------------------------------------------------------ the area walk
+
+def _area_worlds():
+    """(name, F, Q, owner of each keypoint = the query whose window it is in, flips).  th = 3: r = 3 at level 0."""
+    out = []
+    lax = np.full(8, 0.01, f32)  # the chi2 gate never decides an area case
+    # area.window: keypoint 0 at exactly u + r and keypoint 2 at exactly v + r are outside the strict window,
+    # keypoint 1 one float inside it
+    x_in = down(103.0)
+    assert f32(f32(103.0) - f32(100.0)) == f32(TH) and abs(f32(x_in - f32(100.0))) < f32(TH)
+    F = frame([(103.0, 100.0, 0, bits(1)), (x_in, 100.0, 0, bits(5)), (100.0, 103.0, 0, bits(2))])
+    out.append(("window", F, queries([(100.0, 100.0, 0, bits(0))], F, inv=lax), [0, 0, 0], ("area.window",)))
+    # area.order: level 7, r = 3 * 1.2^7 > 10; keypoint 1 lies in an earlier column and a later row than
+    # keypoint 0, at the same distance: the column-major walk meets keypoint 1 first
+    F = frame([(108.0, 94.0, 7, bits(10)), (95.0, 106.0, 7, bits(10))])
+    (c0, r0), (c1, r1) = cell_of(F, 108.0, 94.0), cell_of(F, 95.0, 106.0)
+    assert c1 < c0 and r1 > r0 and f32(TH) * F.scale[7] > 10
+    out.append(("order", F, queries([(100.0, 100.0, 7, bits(0))], F, inv=lax), [0, 0], ("area.order",)))
+    # area.clamp: windows leaving the grid on each side (the right and bottom ones hold a keypoint of the
+    # last column / row of cells), then four windows entirely outside it
+    F = frame([(1.0, 100.0, 0, bits(5)), (745.0, 100.0, 0, bits(5)), (100.0, 1.0, 0, bits(5)), (100.0, 474.0, 0, bits(5))])
+    assert cell_of(F, 745.0, 100.0)[0] == 63 and cell_of(F, 100.0, 474.0)[1] == 47
+    assert cell_of(F, 1.0, 100.0)[0] == 0 and cell_of(F, 100.0, 1.0)[1] == 0
+    Q = queries([(2.0, 100.0, 0, bits(0)), (747.0, 100.0, 0, bits(0)), (100.0, 2.0, 0, bits(0)), (100.0, 476.0, 0, bits(0)),
+                 (852.0, 100.0, 0, bits(0)), (-100.0, 100.0, 0, bits(0)), (100.0, 700.0, 0, bits(0)),
+                 (100.0, -100.0, 0, bits(0))], F, inv=lax)
+    assert (f32(747.0) + f32(TH)) * F.inv_w > 63 and (f32(476.0) + f32(TH)) * F.inv_h > 47   # clamped
+    assert (f32(852.0) - f32(TH)) * F.inv_w >= 64 and (f32(700.0) - f32(TH)) * F.inv_h >= 48  # minC >= COLS / ROWS
+    out.append(("clamp", F, Q, [0, 1, 2, 3], ("area.clamp",)))
+    return out
+
+
+def _as_bysim3(F2, q12, owner):
+    """SearchBySim3 around a one-direction world: KF1 has one keypoint per query of q12, far apart, and every
+    KF2 keypoint projects exactly onto the KF1 keypoint of its owner, so whichever keypoint q12 picks is mutual."""
+    pos = [(40.0 + 40.0 * (i % 16), 40.0 + 40.0 * (i // 16)) for i in range(q12.n)]
+    F1 = frame([(x, y, 0, bits(0)) for x, y in pos])
+    q21 = queries([(pos[o][0], pos[o][1], 0, bits(0)) for o in owner], F1)
+    return F1, F2, q12, q21
+
+
+# ------------------------------------------------------------------------------------ Fuse
+
+def _level_world():
+    """Candidates at pred - 2, pred - 1, pred and pred + 1 (the outer two closer), and a query with pred = 0."""
+    F = frame([(200.0, 200.0, 0, bits(1)), (201.0, 200.0, 1, bits(8)), (200.0, 201.0, 2, bits(9)),
+               (201.0, 201.0, 3, bits(2)), (300.0, 200.0, 0, bits(7)), (301.0, 200.0, 1, bits(3))])
+    return F, queries([(200.0, 200.0, 2, bits(0)), (300.0, 200.0, 0, bits(0))], F), [0, 0, 0, 0, 1, 1]
+
+
+def _tie_world():
+    F = frame([(100.0, 100.0, 0, bits(10)), (101.0, 100.0, 0, bits(10))])
+    assert cell_of(F, 100.0, 100.0) == cell_of(F, 101.0, 100.0)  # one cell: area order = index order
+    return F, queries([(100.0, 100.0, 0, bits(0))], F), [0, 0]
+
+
+def _fuse_cases():
+    out = []
+    F, Q, _ = _level_world()
+    out.append(Case("level", "fuse", (F, Q), ("fuse.level", "fuse.level:narrow")))
+    F, Q, _ = _tie_world()
+    out.append(Case("tie", "fuse", (F, Q), ("fuse.tie",)))
+    # fuse.accept: best exactly 50 and exactly 51
+    F = frame([(100.0, 100.0, 0, bits(50)), (300.0, 100.0, 0, bits(51))])
+    out.append(Case("accept", "fuse", (F, queries([(100.0, 100.0, 0, bits(0)), (300.0, 100.0, 0, bits(0))], F)),
+                    ("fuse.accept",)))
+    # fuse.chi2_mono: e2 = 1 against the two floats either side of 5.99 (octaves 0 / 1), and e2 = 6.3125 times
+    # an inv_sigma2 whose float product stays below 5.99 while the double product passes it (octave 2)
+    lo = f32(5.99) if float(f32(5.99)) <= 5.99 else down(5.99)
+    hi = up(lo)
+    x2 = f32(0.9489108920097351)
+    e2 = f32(f32(f32(-2.5) * f32(-2.5)) + f32(f32(-0.25) * f32(-0.25)))
+    assert float(f32(f32(1) * lo)) <= 5.99 < float(f32(f32(1) * hi))
+    assert e2 == f32(6.3125) and float(f32(e2 * x2)) <= 5.99 < float(e2) * float(x2)
+    inv = np.array([hi, lo, x2, 1, 1, 1, 1, 1], f32)
+    F = frame([(201.0, 200.0, 0, bits(1)), (200.0, 201.0, 1, bits(7)), (302.5, 200.25, 2, bits(3)),
+               (300.0, 200.0, 3, bits(9))])
+    Q = queries([(200.0, 200.0, 1, bits(0)), (300.0, 200.0, 3, bits(0))], F, inv=inv)
+    out.append(Case("chi2_mono", "fuse", (F, Q), ("fuse.chi2_mono",)))
+    # fuse.chi2_stereo: the same at 7.8 with e2 = 3.5 (float product above, double product below), and a
+    # keypoint with u_right == 0.0 exactly, which is a stereo keypoint (er = 3, rejected; as mono it would pass)
+    lo = f32(7.8) if float(f32(7.8)) <= 7.8 else down(7.8)
+    hi = up(lo)
+    x2 = f32(2.2285714149475098)
+    e2 = f32(f32(f32(f32(-1.5) * f32(-1.5)) + f32(f32(-1) * f32(-1))) + f32(f32(-0.5) * f32(-0.5)))
+    assert float(f32(f32(1) * lo)) <= 7.8 < float(f32(f32(1) * hi))
+    assert e2 == f32(3.5) and float(e2) * float(x2) <= 7.8 < float(f32(e2 * x2))
+    inv = np.array([hi, lo, x2, 1, 1, 1, 1, 1], f32)
+    F = frame([(201.0, 200.0, 0, bits(1)), (200.0, 201.0, 1, bits(7)), (301.5, 201.0, 2, bits(3)),
+               (300.0, 200.0, 3, bits(9)), (400.0, 200.0, 4, bits(2))], u_right=[150.0, 150.0, 100.5, 100.0, 0.0])
+    Q = queries([(200.0, 200.0, 1, bits(0)), (300.0, 200.0, 3, bits(0)), (400.0, 200.0, 5, bits(0))], F,
+                ur=[150.0, 100.0, 3.0], inv=inv)
+    out.append(Case("chi2_stereo", "fuse", (F, Q), ("fuse.chi2_stereo", "fuse.chi2_stereo:kpr")))
+    # fuse.right_index: Nleft = 3.  Right keypoint 1 (row 4) is monocular by mvuRight[1] and would be stereo,
+    # and rejected, by mvuRight[4]; right keypoint 2 (row 5) the other way round.  Left keypoint 1 sits under
+    # the first query for the left pass.
+    F = frame([(100.0, 100.0, 0, bits(20)), (200.0, 200.0, 0, bits(6)), (500.0, 100.0, 0, bits(20)),
+               (600.0, 300.0, 0, bits(9)), (200.0, 200.0, 0, bits(4)), (400.0, 200.0, 0, bits(4))],
+              u_right=[-1.0, -1.0, 10.0, -1.0, 10.0, -1.0], nleft=3)
+    Q = queries([(200.0, 200.0, 0, bits(0)), (400.0, 200.0, 0, bits(0))], F, ur=[999.0, 999.0])
+    out.append(Case("right_index", "fuse", (F, Q), ("fuse.right_index",)))
+    # the area walk of the right camera: the window case in mGridRight (left camera: one far keypoint)
+    _, Fa, Qa, _, _ = _area_worlds()[0]
+    F = frame([(600.0, 400.0, 0, bits(0))] + [(float(Fa.kp_x[i]), float(Fa.kp_y[i]), 0, Fa.desc[i]) for i in range(Fa.n)],
+              nleft=1)
+    out.append(Case("right_window", "fuse", (F, Qa), ("area.window",)))
+    return out
+
+
+# ------------------------------------------------------------------------------------ Sim3 projection
+
+def _sim3_cases():
+    out = []
+    free = lambda F: np.full(F.n, -1, np.int32)  # noqa: E731
+    F, Q, _ = _level_world()
+    out.append(Case("level", "sim3", (F, Q, free(F)), ("sim3.level", "sim3.level:narrow")))
+    F, Q, _ = _tie_world()
+    out.append(Case("tie", "sim3", (F, Q, free(F)), ("sim3.tie",)))
+    # sim3.accept: best 35 at ratio 0.7 (50 * 0.7f is 35.0 in float, 34.9999994 in double), 50 at 1.0, 75 and
+    # 76 at 1.5
+    assert float(f32(f32(50) * f32(0.7))) == 35.0 > 50.0 * float(f32(0.7))
+    F = frame([(100.0 * (i + 1), 100.0, 0, bits(d)) for i, d in enumerate((35, 50, 75, 76))])
+    Q = queries([(100.0 * (i + 1), 100.0, 0, bits(0)) for i in range(4)], F)
+    out.append(Case("accept", "sim3", (F, Q, free(F)), ("sim3.accept", "sim3.accept:double")))
+    # sim3.taken: slot 0 was taken before the call (its MapPoint would be the best of query 0, which falls back
+    # to slot 1).  Slots 2, 3, 4 form a chain: query 1 takes 2; query 2 prefers 2, finds it taken, takes 3;
+    # query 3 prefers 3, finds it taken by the LOWER-indexed query 2, takes 4.
+    F = frame([(100.0, 300.0, 0, bits(1)), (101.0, 300.0, 0, bits(20)),
+               (100.0, 100.0, 0, bits(0)), (104.0, 100.0, 0, bits(20)), (108.0, 100.0, 0, bits(40))])
+    Q = queries([(100.0, 300.0, 0, bits(0)), (100.0, 100.0, 0, bits(1)), (102.0, 100.0, 0, bits(5)),
+                 (106.0, 100.0, 0, bits(25))], F)
+    out.append(Case("taken", "sim3", (F, Q, np.array([-2, -1, -1, -1, -1], np.int32)),
+                    ("sim3.taken", "sim3.taken:never")))
+    return out
+
+
+def _bysim3_cases():
+    out = []
+    # bysim3.accept: best exactly 100 and exactly 101
+    F2 = frame([(100.0, 100.0, 0, bits(100)), (300.0, 100.0, 0, bits(101))])
+    q12 = queries([(100.0, 100.0, 0, bits(0)), (300.0, 100.0, 0, bits(0))], F2)
+    out.append(Case("accept", "bysim3", _as_bysim3(F2, q12, [0, 1]), ("bysim3.accept",)))
+    # bysim3.mutual: KF1 keypoint 1 is the better one-way match of KF2 keypoint 0 (d 1 against 3), but KF2
+    # keypoint 0 points back at KF1 keypoint 0
+    F1 = frame([(100.0, 100.0, 0, bits(0)), (140.0, 100.0, 0, bits(90))])
+    F2 = frame([(200.0, 200.0, 0, bits(2))])
+    q12 = queries([(200.0, 200.0, 0, bits(5)), (200.0, 200.0, 0, bits(1))], F2)
+    q21 = queries([(100.0, 100.0, 0, bits(2))], F1)
+    out.append(Case("mutual", "bysim3", (F1, F2, q12, q21), ("bysim3.mutual",)))
+    return out
+
+
+# ------------------------------------------------------------------------------------ triangulation
+
+LINE_F = np.array([[0, 0, 0], [0, 0, -1], [0, 1, 0]], f32)[None]  # the epipolar line of (x1, y1) is y2 = y1: dsqr = (y2 - y1)^2
+FAR_EP = (-1000.0, -1000.0)
+
+
+def side(kps, nodes=None, u_right=None, has_mp=None, two_cam=0, nleft=-1):
+    """kps: (x, y, octave, descriptor[, angle]); nodes: vocabulary node per keypoint (default: all in node 7)."""
+    n = len(kps)
+    nodes = [7] * n if nodes is None else nodes
+    ids = sorted(set(nodes))
+    feat = [i for nd in ids for i in range(n) if nodes[i] == nd]
+    start = np.cumsum([0] + [nodes.count(nd) for nd in ids])
+    return fr.KFSide(desc=np.stack([k[3] for k in kps]), kp_x=[k[0] for k in kps], kp_y=[k[1] for k in kps],
+                     kp_angle=[k[4] if len(k) > 4 else 0.0 for k in kps], kp_octave=[k[2] for k in kps],
+                     u_right=u_right, has_mp=np.zeros(n, np.uint8) if has_mp is None else has_mp, node_id=ids,
+                     node_start=start, feat=feat, two_cam=two_cam, nleft=nleft)
+
+
+def _tri_cases():
+    out = []
+    g = fr.TriangGeom(ep=FAR_EP, F12=LINE_F)
+    # tri.tie: three candidates at distance 10 in node order; 0 and 1 on the epipolar line, 2 off it: the
+    # last of equal distances wins only if it passes the epipolar test
+    K1 = side([(100.0, 100.0, 0, bits(0))])
+    K2 = side([(150.0, 100.0, 0, bits(10)), (180.0, 100.0, 0, bits(10)), (200.0, 110.0, 0, bits(10))])
+    out.append(Case("tie", "tri", (K1, K2, g), ("tri.tie",)))
+    # tri.accept: distance exactly 50 and exactly 51 (bits(101) is 51 from bits(50))
+    K1 = side([(100.0, 100.0, 0, bits(0)), (200.0, 100.0, 0, bits(101))], nodes=[1, 2])
+    K2 = side([(150.0, 100.0, 0, bits(50)), (250.0, 100.0, 0, bits(50))], nodes=[1, 2])
+    out.append(Case("accept", "tri", (K1, K2, g), ("tri.accept",)))
+    # tri.epipole: epipole (0, 0); keypoint 0 at (10, 0), octave 0: 100 < 100 * 1 is false, kept; keypoint 1 at
+    # (9.5, 0) is closer in descriptor and inside the circle.  With a stereo KF1 keypoint, or a two-camera
+    # rig, the test does not apply and keypoint 1 wins.
+    g0 = fr.TriangGeom(ep=(0.0, 0.0), F12=np.repeat(LINE_F, 4, axis=0))
+    k2 = [(10.0, 0.0, 0, bits(10)), (9.5, 0.0, 0, bits(5))]
+    assert f32(f32(10.0) * f32(10.0)) == f32(100) * fr.scale_factors()[0]
+    out.append(Case("epipole_mono", "tri", (side([(50.0, 0.0, 0, bits(0))]), side(k2), g0), ("tri.epipole",)))
+    out.append(Case("epipole_stereo", "tri", (side([(50.0, 0.0, 0, bits(0))], u_right=[20.0]), side(k2), g0),
+                    ("tri.epipole:always",)))
+    out.append(Case("epipole_two_cam", "tri", (side([(50.0, 0.0, 0, bits(0))], two_cam=1, nleft=1),
+                                               side(k2, two_cam=1, nleft=2), g0), ("tri.epipole:always",)))
+    # tri.epipolar: dsqr = 4 against 3.84 * sigma2 (double) with sigma2 the two floats either side of 4 / 3.84;
+    # the upper one passes in double and fails when the product is rounded to float
+    s_pass = f32(4.0 / 3.84)
+    while not 4.0 < 3.84 * float(s_pass):
+        s_pass = up(s_pass)
+    while 4.0 < 3.84 * float(down(s_pass)):
+        s_pass = down(s_pass)
+    s_fail = down(s_pass)
+    assert 4.0 < 3.84 * float(s_pass) and not 4.0 < 3.84 * float(s_fail)
+    assert not f32(4.0) < f32(f32(3.84) * s_pass)
+    K1 = side([(100.0, 100.0, 0, bits(0)), (300.0, 100.0, 0, bits(0))], nodes=[1, 2])
+    K2 = side([(150.0, 102.0, 1, bits(9)), (350.0, 102.0, 2, bits(9))], nodes=[1, 2])
+    K2.level_sigma2 = K2.level_sigma2.copy()
+    K2.level_sigma2[1], K2.level_sigma2[2] = s_fail, s_pass
+    out.append(Case("epipolar", "tri", (K1, K2, g), ("tri.epipolar",)))
+    # den == 0 (an all-zero F12) is no match; bCoarse never asks
+    K1 = side([(100.0, 100.0, 0, bits(0))])
+    K2 = side([(150.0, 100.0, 0, bits(3))])
+    out.append(Case("den0", "tri", (K1, K2, fr.TriangGeom(ep=FAR_EP, F12=np.zeros((1, 3, 3), f32))), ()))
+    # tri.filters: KF1 keypoint 0 has a MapPoint, 1 is monocular, 2 stereo.  KF2 keypoint 0 (d 1) has a MapPoint,
+    # 1 is monocular (d 5), 2 stereo (d 8), 3 monocular, closest (d 2) and off the epipolar line.
+    K1 = side([(100.0, 100.0, 0, bits(0)), (100.0, 100.0, 0, bits(0)), (100.0, 100.0, 0, bits(0))],
+              u_right=[-1.0, -1.0, 60.0], has_mp=[1, 0, 0])
+    K2 = side([(150.0, 100.0, 0, bits(1)), (160.0, 100.0, 0, bits(5)), (170.0, 100.0, 0, bits(8)),
+               (180.0, 110.0, 0, bits(2))], u_right=[-1.0, -1.0, 120.0, -1.0], has_mp=[1, 0, 0, 0])
+    out.append(Case("filters", "tri", (K1, K2, g), ("tri.filters", "tri.filters:mp1", "tri.filters:stereo1",
+                                                     "tri.filters:stereo2", "tri.filters:coarse")))
+    return out
+
+
+# ------------------------------------------------------------------------------------ rotation histogram
+
+def _hist_worlds():
+    """(name, [(angle1, angle2)] per match, flips): the matches of a case differ in nothing but their angles,
+    so the three surviving bins are the whole result."""
+    fac = f32(f32(1.0) / f32(30))
+    assert float(f32(f32(15) * fac)) == 0.5 and float(f32(f32(45) * fac)) > 1.5   # 45 degrees is not a tie in float
+    assert float(f32(f32(60) * fac)) == 2.0 and round(float(f32(f32(90) * fac))) == 3
+    assert f32(0.1) * f32(10) == f32(1) and f32(0.1) * f32(30) == f32(3)
+    out = []
+    # bins 0, 2, 3 with three matches each; 15 degrees (0.5: bin 1 by roundf, bin 0 by rintf), the same through
+    # the rot < 0 wrap (10 - 355), and 45 degrees (bin 2 either way): bin 1 holds two matches and is dropped
+    out.append(("round", [(0.0, 0.0)] * 3 + [(60.0, 0.0)] * 3 + [(90.0, 0.0)] * 3
+                + [(15.0, 0.0), (10.0, 355.0), (45.0, 0.0)], ("rot.round",)))
+    # a difference of exactly 0 does not wrap: bin 0 holds four matches and leads; wrapped, two of them go to bin 12
+    out.append(("wrap", [(7.0, 7.0)] * 2 + [(5.0, 0.0)] * 2 + [(60.0, 0.0)] * 3 + [(90.0, 0.0)] * 3
+                + [(120.0, 0.0)] * 3, ("rot.round:wrap",)))
+    # four bins of two: the first three survive
+    out.append(("order", [(d, 0.0) for d in (0.0, 60.0, 90.0, 120.0) for _ in range(2)], ("maxima.order",)))
+    # max1 = 10, max2 = 1: 1 < 0.1f * 10 is false, bin 2 stays
+    out.append(("tenth10", [(0.0, 0.0)] * 10 + [(60.0, 0.0)], ("maxima.tenth",)))
+    # max1 = 30, max2 = 5, max3 = 3: 3 < 0.1f * 30 is false, bin 3 stays
+    out.append(("tenth30", [(0.0, 0.0)] * 30 + [(60.0, 0.0)] * 5 + [(90.0, 0.0)] * 3, ("maxima.tenth",)))
+    return out
+
+
+def _lattice(i):
+    return 40.0 + 40.0 * (i % 16), 40.0 + 40.0 * (i // 16)
+
+
+def _hist_cases():
+    out = []
+    for name, pairs, flips in _hist_worlds():
+        n = len(pairs)
+        assert n <= 64
+        pos = [_lattice(i) for i in range(n)]
+        # triangulation: match i alone in node i, on its epipolar line
+        K1 = side([(x, y, 0, bits(0), a[0]) for (x, y), a in zip(pos, pairs)], nodes=list(range(n)))
+        K2 = side([(x, y, 0, bits(0), a[1]) for (x, y), a in zip(pos, pairs)], nodes=list(range(n)))
+        out.append(Case("hist_" + name, "tri", (K1, K2, fr.TriangGeom(ep=FAR_EP, F12=LINE_F)), flips))
+        # initialisation: match i alone in its window (40 px apart, windowSize 20)
+        F1 = frame([(x, y, 0, bits(0), a[0]) for (x, y), a in zip(pos, pairs)])
+        F2 = frame([(x, y, 0, bits(0), a[1]) for (x, y), a in zip(pos, pairs)])
+        out.append(Case("hist_" + name, "init", (F1, F2, np.array(pos, f32)), flips))
+    return out
+
+
+# ------------------------------------------------------------------------------------ initialisation
+
+def _init_case(name, k1, k2, flips):
+    F1, F2 = frame(k1), frame(k2)
+    assert all(abs(k[0] - PILE_XY[0]) > 2 * WINDOW for k in k1 + k2)
+    return Case(name, "init", (F1, F2, np.stack([F1.kp_x, F1.kp_y], axis=1).astype(f32)), flips)
+
+
+def _init_cases():
+    out = []
+    # init.level0: F1 keypoint 0 is at level 1 (F2 keypoint 0 would match it); F1 keypoint 1 has a level-1
+    # candidate at d 1 and a level-0 candidate at d 5
+    out.append(_init_case("level0", [(100.0, 100.0, 1, bits(0)), (300.0, 100.0, 0, bits(0))],
+                          [(100.0, 100.0, 0, bits(3)), (300.0, 100.0, 1, bits(1)), (301.0, 100.0, 0, bits(5))],
+                          ("init.level0", "init.level0:f2")))
+    # init.md: F1 keypoints 0 and 1 are both 4 from F2 keypoint 0: vMatchedDistance 4 <= 4 skips the second
+    out.append(_init_case("md", [(100.0, 100.0, 0, bits(4)), (100.0, 100.0, 0, bits(4))],
+                          [(100.0, 100.0, 0, bits(0))], ("init.md",)))
+    # init.top2: two candidates at 10: the second becomes bestDist2 and 10 < 10 * 0.9 fails
+    out.append(_init_case("top2", [(100.0, 100.0, 0, bits(0))],
+                          [(100.0, 100.0, 0, bits(10)), (101.0, 100.0, 0, bits(10))], ("init.top2",)))
+    # init.accept: b1 = 50 alone, b1 = 51 alone, (9, 10) and (18, 20): 10 * 0.9f and 20 * 0.9f round to 9 and 18
+    assert f32(f32(10) * f32(NNRATIO)) == f32(9) and f32(f32(20) * f32(NNRATIO)) == f32(18)
+    k1 = [(100.0 * (i + 1), 100.0, 0, bits(0)) for i in range(4)]
+    k2 = [(100.0, 100.0, 0, bits(50)), (200.0, 100.0, 0, bits(51)), (300.0, 100.0, 0, bits(9)),
+          (301.0, 100.0, 0, bits(10)), (400.0, 100.0, 0, bits(18)), (401.0, 100.0, 0, bits(20))]
+    out.append(_init_case("accept", k1, k2, ("init.accept", "init.accept:ratio")))
+    # init.steal_hist: bins 1, 2, 3 hold three live matches each.  Bin 5 holds two live matches and the two
+    # matches they stole from: counted, it leads with four entries and bin 3 is dropped; uncounted, bin 5 is.
+    k1, k2 = [], []
+    for j in range(2):   # the owners first (d 4), their thieves last (d 2): same window, same bin
+        k1.append((100.0 + 100.0 * j, 300.0, 0, bits(4), 150.0))
+    for j, d in enumerate((30.0, 60.0, 90.0)):
+        for k in range(3):
+            x, y = _lattice(3 * j + k)
+            k1.append((x, y, 0, bits(0), d))
+            k2.append((x, y, 0, bits(0), 0.0))
+    for j in range(2):
+        k1.append((100.0 + 100.0 * j, 300.0, 0, bits(2), 150.0))
+        k2.append((100.0 + 100.0 * j, 300.0, 0, bits(0), 0.0))
+    assert round(float(f32(f32(150) * f32(f32(1.0) / f32(30))))) == 5
+    out.append(_init_case("steal_hist", k1, k2, ("init.steal_hist",)))
+    return out
+
+
+def pile_up(case, k=5):
+    """The case with k more F1 keypoints that all claim one more F2 keypoint in the first round, each closer
+    than the one before (each steals it in turn), far from the case's own keypoints: k > FP_K claimants
+    force k_init's serial walk."""
+    F1, F2, prev = case.args
+    x, y = PILE_XY
+
+    def grown(F, descs):
+        m = len(descs)
+        return fr.FrameSoA(desc=np.concatenate([F.desc, np.stack(descs)]), kp_x=np.concatenate([F.kp_x, [x] * m]),
+                           kp_y=np.concatenate([F.kp_y, [y] * m]), kp_angle=np.concatenate([F.kp_angle, [0.0] * m]),
+                           kp_octave=np.concatenate([F.kp_octave, [0] * m]))
+    G1, G2 = grown(F1, [bits(2 * (k - j)) for j in range(k)]), grown(F2, [bits(0)])
+    return Case(f"{case.name}+pile{k}", "init", (G1, G2, np.concatenate([prev, [[x, y]] * k]).astype(f32)), case.flips)
+
+
+# ------------------------------------------------------------------------------------ all of them
+
+def _build():
+    out = []
+    for name, F, Q, owner, flips in _area_worlds():
+        out.append(Case("area_" + name, "fuse", (F, Q), flips))
+        out.append(Case("area_" + name, "sim3", (F, Q, np.full(F.n, -1, np.int32)), flips))
+        out.append(Case("area_" + name, "bysim3", _as_bysim3(F, Q, owner), flips))
+    out += _fuse_cases() + _sim3_cases() + _bysim3_cases() + _tri_cases() + _hist_cases() + _init_cases()
+    assert len({c.id for c in out}) == len(out)
+    return out
+
+
+CASES = _build()
+
+
+def of_kind(kind):
+    return [c for c in CASES if c.kind == kind]
+
+
+# ------------------------------------------------------------------------------------ GPU-only shapes
+
+def lattice_frame(n, cols, level=0, dx=5.5, dy=7.0):
+    """n keypoints on a cols-wide lattice, all at one level, descriptors bits(i % 40)."""
+    i = np.arange(n)
+    return fr.FrameSoA(desc=np.stack([bits(k) for k in range(40)])[i % 40], kp_x=(20.0 + dx * (i % cols)).astype(f32),
+                       kp_y=(10.0 + dy * (i // cols)).astype(f32), kp_angle=(i % 7 * 50.0).astype(f32),
+                       kp_octave=np.full(n, level, np.int32))
+
+
+def lattice_picks(F, m=64, step=127):
+    """m keypoints of a lattice frame: every step-th, and the last one."""
+    j = (np.arange(m) * step) % F.n
+    j[-1] = F.n - 1
+    return j
+
+
+def lattice_queries(F, lvl, m=64):
+    """m MapPoints on top of lattice_picks(F), descriptors two bits from the keypoint's."""
+    return queries([(float(F.kp_x[k]), float(F.kp_y[k]), lvl, bits(int(k) % 40 + 2)) for k in lattice_picks(F, m)], F)
+
+
+def lattice_init_pair(n2, m=64):
+    """F2: n2 level-0 keypoints on a lattice; F1: m level-0 keypoints on top of lattice_picks(F2)."""
+    F2 = lattice_frame(n2, 128)
+    j = lattice_picks(F2, m)
+    F1 = frame([(float(F2.kp_x[k]), float(F2.kp_y[k]), 0, bits(int(k) % 40 + 2), float(k % 5) * 70.0) for k in j])
+    return F1, F2, np.stack([F1.kp_x, F1.kp_y], axis=1).astype(f32)
+
+
+def sim3_chain(L=40, stride=1024):
+    """L MapPoints at query indices 0, stride - 1, stride, 2 * stride - 1, ... (every query between them
+    invalid).  Slot j sits at x = 100 + 4 j; MapPoint 0 sees slot 0 alone, MapPoint i slots i - 1 (d 1) and i
+    (d 3): each finds its first choice taken by the MapPoint before it, so the sequential result (MapPoint i
+    in slot i) needs one round of the fixed point per MapPoint."""
+    F = frame([(100.0 + 4.0 * j, 100.0, 0, bits(4 * j)) for j in range(L)])
+    at = [(i // 2 + i % 2) * stride - i % 2 for i in range(L)]
+    n = at[-1] + 1
+    u, v = np.zeros(n, f32), np.zeros(n, f32)
+    desc = np.zeros((n, 32), np.uint8)
+    valid = np.zeros(n, np.uint8)
+    for i, q in enumerate(at):
+        u[q], v[q] = (100.0, 100.0) if i == 0 else (100.0 + 4.0 * i - 2.0, 100.0)
+        desc[q] = bits(1) if i == 0 else bits(4 * i - 3)
+        valid[q] = 1
+    Q = fr.FuseQueries(desc=desc, valid=valid, u=u, v=v, ur=None, pred_level=np.zeros(n, np.int32),
+                       inv_level_sigma2=fr.inv_level_sigma2(F.scale))
+    return F, Q, np.full(F.n, -1, np.int32), at
+
+
+def init_claimants(k):
+    """k F1 keypoints that all choose F2 keypoint 0 in the first round, each closer than the one before."""
+    F1 = frame([(100.0, 100.0, 0, bits(2 * (k - j))) for j in range(k)])
+    F2 = frame([(100.0, 100.0, 0, bits(0)), (300.0, 300.0, 0, bits(0))])
+    return F1, F2, np.stack([F1.kp_x, F1.kp_y], axis=1).astype(f32)

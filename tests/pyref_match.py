@@ -8,12 +8,64 @@ import numpy as np
 f32 = np.float32
 TH_HIGH, TH_LOW, HISTO = 100, 50, 30
 
+# One-decision variants ("Matcher decisions"): ``flip="<name>"`` evaluates exactly one
+# named decision of the reference in a wrong form, so that tests/test_matcher_boundaries.py can prove
+# that a fixture sits on that decision.  ``name`` is the decision's nearest wrong form; ``name:variant``
+# another wrong form of the same decision.  ``flip=None`` is the reference.
+FLIPS = {
+    "area.window": "|dx| <= r && |dy| <= r",
+    "area.order": "iy outer, ix inner",
+    "area.clamp": "max cell clamped to COLS - 2 / ROWS - 2",
+    "fuse.level": "octave in [pred - 1, pred + 1]",
+    "fuse.level:narrow": "octave in [pred, pred]",
+    "fuse.chi2_mono": "e2 * inv_sigma2 in double against 5.99",
+    "fuse.chi2_stereo": "e2 * inv_sigma2 in double against 7.8",
+    "fuse.chi2_stereo:kpr": "stereo gate iff u_right > 0",
+    "fuse.tie": "dist <= best: the last candidate wins",
+    "fuse.accept": "best < TH_LOW",
+    "fuse.right_index": "mvuRight read at idx + nleft",
+    "sim3.accept": "best < TH_LOW * ratio",
+    "sim3.accept:double": "TH_LOW * ratio in double",
+    "sim3.taken": "a slot claimed by any other MapPoint is skipped",
+    "sim3.taken:never": "taken slots are not skipped",
+    "sim3.tie": "dist <= best",
+    "sim3.level": "octave in [pred - 1, pred + 1]",
+    "sim3.level:narrow": "octave in [pred, pred]",
+    "bysim3.accept": "best < TH_HIGH",
+    "bysim3.mutual": "one-way matches kept",
+    "tri.tie": "the first of equal distances wins",
+    "tri.accept": "dist >= TH_LOW skips",
+    "tri.epipole": "dist^2 <= 100 * scale skips",
+    "tri.epipole:always": "epipole test with a stereo side or a two-camera rig too",
+    "tri.epipolar": "3.84 * sigma2 in float",
+    "tri.filters": "KF2 keypoints with a MapPoint kept",
+    "tri.filters:mp1": "KF1 keypoints with a MapPoint kept",
+    "tri.filters:stereo1": "bOnlyStereo not applied to KF1",
+    "tri.filters:stereo2": "bOnlyStereo not applied to KF2",
+    "tri.filters:coarse": "bCoarse does not bypass the epipolar test",
+    "rot.round": "rintf (half to even)",
+    "rot.round:wrap": "rot <= 0 wraps",
+    "maxima.order": ">=: the later of two equal bins ranks higher",
+    "maxima.tenth": "max < 0.1f * max1 as <=",
+    "init.level0": "F1 keypoints of every level",
+    "init.level0:f2": "F2 candidates of every level",
+    "init.md": "vMatchedDistance < dist skips",
+    "init.top2": "a distance equal to the best is not the second best",
+    "init.accept": "b1 < TH_LOW",
+    "init.accept:ratio": "b1 <= b2 * nnratio",
+    "init.steal_hist": "only live matches counted in the histogram",
+}
+
+
+def _chk(flip):
+    assert flip is None or flip in FLIPS, flip
+
 
 def dist(a, b):
     return int(np.bitwise_count(np.bitwise_xor(a, b)).sum())
 
 
-def features_in_area(F, x, y, r, minL=-1, maxL=-1, right=False):
+def features_in_area(F, x, y, r, minL=-1, maxL=-1, right=False, flip=None):
     """Frame::GetFeaturesInArea; ``right`` walks mGridRight (indices relative to Nleft)."""
     x, y, r = f32(x), f32(y), f32(r)
     out = []
@@ -32,53 +84,62 @@ def features_in_area(F, x, y, r, minL=-1, maxL=-1, right=False):
     chk = (minL > 0) or (maxL >= 0)
     gs, gi = (F.grid_start_r, F.grid_idx_r) if right else (F.grid_start, F.grid_idx)
     off = F.nleft if right else 0
-    for ix in range(minCX, maxCX + 1):
-        for iy in range(minCY, maxCY + 1):
-            c = ix * 48 + iy
-            for j in range(gs[c], gs[c + 1]):
-                idx = int(gi[j])
-                k = idx + off
-                o = int(F.kp_octave[k])
-                if chk:
-                    if o < minL:
-                        continue
-                    if maxL >= 0 and o > maxL:
-                        continue
-                if abs(f32(F.kp_x[k] - x)) < r and abs(f32(F.kp_y[k] - y)) < r:
-                    out.append(idx)
+    if flip == "area.clamp":
+        maxCX, maxCY = min(maxCX, 62), min(maxCY, 46)
+    cells = [(ix, iy) for ix in range(minCX, maxCX + 1) for iy in range(minCY, maxCY + 1)]
+    if flip == "area.order":
+        cells.sort(key=lambda c: (c[1], c[0]))
+    for ix, iy in cells:
+        c = ix * 48 + iy
+        for j in range(gs[c], gs[c + 1]):
+            idx = int(gi[j])
+            k = idx + off
+            o = int(F.kp_octave[k])
+            if chk:
+                if o < minL:
+                    continue
+                if maxL >= 0 and o > maxL:
+                    continue
+            dx, dy = abs(f32(F.kp_x[k] - x)), abs(f32(F.kp_y[k] - y))
+            if (dx <= r and dy <= r) if flip == "area.window" else (dx < r and dy < r):
+                out.append(idx)
     return out
 
 
-def rot_bin(a, b):
+def rot_bin(a, b, flip=None):
     rot = f32(f32(a) - f32(b))
-    if rot < 0.0:
+    if rot <= 0.0 if flip == "rot.round:wrap" else rot < 0.0:
         rot = f32(rot + f32(360.0))
     v = float(f32(rot * f32(f32(1.0) / f32(30))))
     b_ = int(math.floor(v + 0.5))  # round half away from zero, v >= 0
+    if flip == "rot.round":
+        b_ = int(np.rint(v))
     return 0 if b_ == 30 else b_
 
 
-def three_maxima(sizes):
+def three_maxima(sizes, flip=None):
     m1 = m2 = m3 = 0
     i1 = i2 = i3 = -1
+    gt = (lambda a, b: a >= b) if flip == "maxima.order" else (lambda a, b: a > b)
+    lt = (lambda a, b: a <= b) if flip == "maxima.tenth" else (lambda a, b: a < b)
     for i, s in enumerate(sizes):
-        if s > m1:
+        if gt(s, m1):
             m3, m2, m1 = m2, m1, s
             i3, i2, i1 = i2, i1, i
-        elif s > m2:
+        elif gt(s, m2):
             m3, m2 = m2, s
             i3, i2 = i2, i
-        elif s > m3:
+        elif gt(s, m3):
             m3, i3 = s, i
-    if m2 < f32(0.1) * f32(m1):
+    if lt(m2, f32(0.1) * f32(m1)):
         i2 = i3 = -1
-    elif m3 < f32(0.1) * f32(m1):
+    elif lt(m3, f32(0.1) * f32(m1)):
         i3 = -1
     return i1, i2, i3
 
 
-def apply_hist(hist, slots, nm):
-    keep = three_maxima([len(h) for h in hist])
+def apply_hist(hist, slots, nm, flip=None):
+    keep = three_maxima([len(h) for h in hist], flip)
     for i in range(HISTO):
         if i in keep:
             continue
@@ -336,9 +397,18 @@ def search_bow_kf_kf(K1, K2, nn, ori):
     return nm, out
 
 
-def fuse_search(F, Q, th, right=False, gated=True):
+def _level_window(lvl, flip, name):
+    if flip == name:
+        return lvl - 1, lvl + 1
+    if flip == name + ":narrow":
+        return lvl, lvl
+    return lvl - 1, lvl
+
+
+def fuse_search(F, Q, th, right=False, gated=True, flip=None):
     """Search half of ORBmatcher::Fuse (both overloads): KeyFrame::GetFeaturesInArea (no levels),
     level window [pred-1, pred], chi2 gate (gated), strict '<' best, accept <= TH_LOW."""
+    _chk(flip)
     n = len(Q.valid)
     bi = np.full(n, -1, np.int32)
     bd = np.full(n, 256, np.int32)
@@ -351,40 +421,44 @@ def fuse_search(F, Q, th, right=False, gated=True):
         rad = f32(f32(th) * F.scale[lvl])
         u, v = f32(Q.u[i]), f32(Q.v[i])
         best, besti = (256 if gated else 2 ** 31 - 1), -1
-        for idx in features_in_area(F, u, v, rad, -1, -1, right=right):
+        lo, hi = _level_window(lvl, flip, "fuse.level")
+        for idx in features_in_area(F, u, v, rad, -1, -1, right=right, flip=flip):
             k = idx + off
             o = int(F.kp_octave[k])
-            if o < lvl - 1 or o > lvl:
+            if o < lo or o > hi:
                 continue
             if gated:
                 ex, ey = f32(u - F.kp_x[k]), f32(v - F.kp_y[k])
                 inv = f32(Q.inv_level_sigma2[o])
-                kr = F.u_right[idx] if F.u_right is not None else f32(-1)
-                if kr >= 0:
+                kr = F.u_right[k if flip == "fuse.right_index" else idx] if F.u_right is not None else f32(-1)
+                if kr > 0 if flip == "fuse.chi2_stereo:kpr" else kr >= 0:
                     er = f32(f32(Q.ur[i]) - f32(kr))
                     e2 = f32(f32(f32(ex * ex) + f32(ey * ey)) + f32(er * er))
-                    if float(f32(e2 * inv)) > 7.8:
+                    chi2 = float(e2) * float(inv) if flip == "fuse.chi2_stereo" else float(f32(e2 * inv))
+                    if chi2 > 7.8:
                         continue
                 else:
                     e2 = f32(f32(ex * ex) + f32(ey * ey))
-                    if float(f32(e2 * inv)) > 5.99:
+                    chi2 = float(e2) * float(inv) if flip == "fuse.chi2_mono" else float(f32(e2 * inv))
+                    if chi2 > 5.99:
                         continue
             d = dist(Q.desc[i], F.desc[k])
-            if d < best:
+            if d <= best if flip == "fuse.tie" else d < best:
                 best, besti = d, k
         bd[i] = min(best, 256)
-        if best <= TH_LOW:
+        if best < TH_LOW if flip == "fuse.accept" else best <= TH_LOW:
             bi[i] = besti
             nf += 1
     return nf, bi, bd
 
 
-def search_for_triangulation(K1, K2, geom, only_stereo=False, coarse=False, ori=True):
+def search_for_triangulation(K1, K2, geom, only_stereo=False, coarse=False, ori=True, flip=None):
     """ORBmatcher::SearchForTriangulation (ref:src/ORBmatcher.cc:1045-1328) with
     Pinhole::epipolarConstrain (ref:src/CameraModels/Pinhole.cpp:189-219).  Node pairing by set
     intersection (not the reference's lower_bound walk); returns (nmatches, pairs)."""
     nodes1 = {int(K1.node_id[k]): K1.feat[K1.node_start[k]:K1.node_start[k + 1]] for k in range(len(K1.node_id))}
     nodes2 = {int(K2.node_id[k]): K2.feat[K2.node_start[k]:K2.node_start[k + 1]] for k in range(len(K2.node_id))}
+    _chk(flip)
     m12 = [-1] * K1.n
     hist = [[] for _ in range(HISTO)]
     nm = 0
@@ -399,32 +473,45 @@ def search_for_triangulation(K1, K2, geom, only_stereo=False, coarse=False, ori=
     for node in sorted(set(nodes1) & set(nodes2)):
         for idx1 in nodes1[node]:
             idx1 = int(idx1)
-            if K1.has_mp[idx1]:
+            if K1.has_mp[idx1] and flip != "tri.filters:mp1":
                 continue
             s1 = stereo(K1, idx1)
-            if only_stereo and not s1:
+            if only_stereo and not s1 and flip != "tri.filters:stereo1":
                 continue
             x1, y1 = f32(K1.kp_x[idx1]), f32(K1.kp_y[idx1])
             best_d, best = TH_LOW, -1
             for idx2 in nodes2[node]:
                 idx2 = int(idx2)
-                if K2.has_mp[idx2]:
+                if K2.has_mp[idx2] and flip != "tri.filters":
                     continue
                 s2 = stereo(K2, idx2)
-                if only_stereo and not s2:
+                if only_stereo and not s2 and flip != "tri.filters:stereo2":
                     continue
                 d = dist(K1.desc[idx1], K2.desc[idx2])
+                if flip == "tri.accept" and d >= TH_LOW:
+                    continue
+                if flip == "tri.tie" and best >= 0 and d == best_d:
+                    continue
                 if d > TH_LOW or d > best_d:
                     continue
                 x2, y2 = f32(K2.kp_x[idx2]), f32(K2.kp_y[idx2])
                 o2 = int(K2.kp_octave[idx2])
-                if not s1 and not s2 and not K1.two_cam:
+                if (not s1 and not s2 and not K1.two_cam) or flip == "tri.epipole:always":
                     ex, ey = f32(f32(geom.ep[0]) - x2), f32(f32(geom.ep[1]) - y2)
-                    if f32(f32(ex * ex) + f32(ey * ey)) < f32(f32(100) * K2.scale[o2]):
+                    e2, lim = f32(f32(ex * ex) + f32(ey * ey)), f32(f32(100) * K2.scale[o2])
+                    if e2 <= lim if flip == "tri.epipole" else e2 < lim:
                         continue
                 k = (2 * right(K1, idx1) + right(K2, idx2)) if (K1.two_cam and K2.two_cam) else 0
-                ok = coarse
-                if not ok:
+                ok = coarse and flip != "tri.filters:coarse"
+                if not ok and flip == "tri.epipolar":
+                    Fk = F[k]
+                    a = f32(f32(f32(x1 * Fk[0, 0]) + f32(y1 * Fk[1, 0])) + Fk[2, 0])
+                    b = f32(f32(f32(x1 * Fk[0, 1]) + f32(y1 * Fk[1, 1])) + Fk[2, 1])
+                    c = f32(f32(f32(x1 * Fk[0, 2]) + f32(y1 * Fk[1, 2])) + Fk[2, 2])
+                    num = f32(f32(f32(a * x2) + f32(b * y2)) + c)
+                    den = f32(f32(a * a) + f32(b * b))
+                    ok = den != 0 and f32(f32(num * num) / den) < f32(f32(3.84) * K2.level_sigma2[o2])
+                elif not ok:
                     Fk = F[k]
                     a = f32(f32(f32(x1 * Fk[0, 0]) + f32(y1 * Fk[1, 0])) + Fk[2, 0])
                     b = f32(f32(f32(x1 * Fk[0, 1]) + f32(y1 * Fk[1, 1])) + Fk[2, 1])
@@ -438,9 +525,9 @@ def search_for_triangulation(K1, K2, geom, only_stereo=False, coarse=False, ori=
                 m12[idx1] = best
                 nm += 1
                 if ori:
-                    hist[rot_bin(K1.kp_angle[idx1], K2.kp_angle[best])].append(idx1)
+                    hist[rot_bin(K1.kp_angle[idx1], K2.kp_angle[best], flip)].append(idx1)
     if ori:
-        nm = apply_hist(hist, m12, nm)
+        nm = apply_hist(hist, m12, nm, flip)
     pairs = [(i, j) for i, j in enumerate(m12) if j >= 0]
     return nm, np.array(pairs, np.int64).reshape(-1, 2)
 
@@ -461,35 +548,65 @@ def distinctive(desc_lists):
     return np.array(out, np.int32)
 
 
-def search_sim3(F, Q, th, ratio, slot_query):
+def search_sim3(F, Q, th, ratio, slot_query, flip=None):
     """SearchByProjection(KeyFrame*, Sim3f&, ...) (ref:src/ORBmatcher.cc:498-621) from the area walk on:
     vpMatched written as soon as a MapPoint is accepted.  slot_query: -2 taken, -1 free."""
+    _chk(flip)
     s = np.array(slot_query, np.int32).copy()
+    thr = float(f32(f32(TH_LOW) * f32(ratio)))
+    if flip == "sim3.accept:double":
+        thr = float(TH_LOW) * float(f32(ratio))
+
+    def choose(q, blocked):
+        lvl = int(Q.pred_level[q])
+        r = f32(f32(th) * F.scale[lvl])
+        lo, hi = _level_window(lvl, flip, "sim3.level")
+        bd, bi = 256, -1
+        for idx in features_in_area(F, Q.u[q], Q.v[q], r, flip=flip):
+            if blocked(idx):
+                continue
+            o = int(F.kp_octave[idx])
+            if o < lo or o > hi:
+                continue
+            d = dist(Q.desc[q], F.desc[idx])
+            if d <= bd if flip == "sim3.tie" else d < bd:
+                bd, bi = d, idx
+        return bi if (float(bd) < thr if flip == "sim3.accept" else float(bd) <= thr) else -1
+
+    if flip == "sim3.taken":
+        # the wrong rule has no sequential form: iterate it as the kernel's rounds would (every MapPoint
+        # against the lowest-indexed claimant of each slot in the previous round) until nothing changes
+        best = [-1] * Q.n
+        for _ in range(2 * Q.n + 4):
+            claim = {}
+            for q, b in enumerate(best):
+                if b >= 0:
+                    claim[b] = min(claim.get(b, q), q)
+            new = [choose(q, lambda idx: s[idx] != -1 or claim.get(idx, q) != q) if Q.valid[q] else -1
+                   for q in range(Q.n)]
+            if new == best:
+                break
+            best = new
+        for q, b in enumerate(best):
+            if b >= 0:
+                s[b] = q
+        return sum(1 for b in best if b >= 0), s
     n = 0
     for q in range(Q.n):
         if not Q.valid[q]:
             continue
-        lvl = int(Q.pred_level[q])
-        r = f32(f32(th) * F.scale[lvl])
-        bd, bi = 256, -1
-        for idx in features_in_area(F, Q.u[q], Q.v[q], r):
-            if s[idx] != -1:
-                continue
-            o = int(F.kp_octave[idx])
-            if o < lvl - 1 or o > lvl:
-                continue
-            d = dist(Q.desc[q], F.desc[idx])
-            if d < bd:
-                bd, bi = d, idx
-        if float(bd) <= float(f32(f32(TH_LOW) * f32(ratio))):
+        bi = choose(q, (lambda idx: False) if flip == "sim3.taken:never" else (lambda idx: s[idx] != -1))
+        if bi >= 0:
             s[bi] = q
             n += 1
     return n, s
 
 
-def search_by_sim3(F1, F2, Q12, Q21, th):
+def search_by_sim3(F1, F2, Q12, Q21, th, flip=None):
     """ORBmatcher::SearchBySim3 (ref:src/ORBmatcher.cc:1696-1939) from the area walk on: each direction's
     strict-'<' minimum from INT_MAX, accepted iff <= TH_HIGH; the mutual pairs in KF1 order."""
+    _chk(flip)
+
     def direction(F, Q):
         out = [-1] * Q.n
         for q in range(Q.n):
@@ -498,23 +615,24 @@ def search_by_sim3(F1, F2, Q12, Q21, th):
             lvl = int(Q.pred_level[q])
             r = f32(f32(th) * F.scale[lvl])
             bd, bi = 2147483647, -1
-            for idx in features_in_area(F, Q.u[q], Q.v[q], r):
+            for idx in features_in_area(F, Q.u[q], Q.v[q], r, flip=flip):
                 o = int(F.kp_octave[idx])
                 if o < lvl - 1 or o > lvl:
                     continue
                 d = dist(Q.desc[q], F.desc[idx])
                 if d < bd:
                     bd, bi = d, idx
-            if bd <= TH_HIGH:
+            if bd < TH_HIGH if flip == "bysim3.accept" else bd <= TH_HIGH:
                 out[q] = bi
         return out
     m1, m2 = direction(F2, Q12), direction(F1, Q21)
-    m12 = [(i2 if i2 >= 0 and m2[i2] == i1 else -1) for i1, i2 in enumerate(m1)]
+    m12 = [(i2 if i2 >= 0 and (m2[i2] == i1 or flip == "bysim3.mutual") else -1) for i1, i2 in enumerate(m1)]
     return sum(1 for x in m12 if x >= 0), np.array(m12, np.int32)
 
 
-def search_for_initialization(F1, F2, prev, window=100, nn=0.9, ori=True):
+def search_for_initialization(F1, F2, prev, window=100, nn=0.9, ori=True, flip=None):
     """ORBmatcher::SearchForInitialization (ref:src/ORBmatcher.cc:735-878): (nmatches, vnMatches12, prev)."""
+    _chk(flip)
     INT_MAX = 2147483647
     n1, n2 = F1.n, F2.n
     m12 = [-1] * n1
@@ -522,23 +640,26 @@ def search_for_initialization(F1, F2, prev, window=100, nn=0.9, ori=True):
     m21 = [-1] * n2
     hist = [[] for _ in range(HISTO)]
     nm = 0
+    lv = (-1, -1) if flip == "init.level0:f2" else (0, 0)
     for i1 in range(n1):
-        if F1.kp_octave[i1] > 0:
+        if F1.kp_octave[i1] > 0 and flip != "init.level0":
             continue
-        cand = features_in_area(F2, prev[i1, 0], prev[i1, 1], float(window), 0, 0)
+        cand = features_in_area(F2, prev[i1, 0], prev[i1, 1], float(window), lv[0], lv[1], flip=flip)
         if not cand:
             continue
         b1 = b2 = INT_MAX
         bi = -1
         for i2 in cand:
             d = dist(F1.desc[i1], F2.desc[i2])
-            if md[i2] <= d:
+            if md[i2] < d if flip == "init.md" else md[i2] <= d:
                 continue
             if d < b1:
                 b1, b2, bi = d, b1, i2
-            elif d < b2:
+            elif d < b2 and not (flip == "init.top2" and d == b1):
                 b2 = d
-        if b1 <= TH_LOW and float(f32(b1)) < float(f32(f32(b2) * f32(nn))):
+        r1, r2 = float(f32(b1)), float(f32(f32(b2) * f32(nn)))
+        if (b1 < TH_LOW if flip == "init.accept" else b1 <= TH_LOW) and \
+                (r1 <= r2 if flip == "init.accept:ratio" else r1 < r2):
             if m21[bi] >= 0:
                 m12[m21[bi]] = -1
                 nm -= 1
@@ -547,9 +668,11 @@ def search_for_initialization(F1, F2, prev, window=100, nn=0.9, ori=True):
             md[bi] = b1
             nm += 1
             if ori:
-                hist[rot_bin(F1.kp_angle[i1], F2.kp_angle[bi])].append(i1)
+                hist[rot_bin(F1.kp_angle[i1], F2.kp_angle[bi], flip)].append(i1)
     if ori:
-        keep = three_maxima([len(h) for h in hist])
+        if flip == "init.steal_hist":
+            hist = [[i1 for i1 in h if m12[i1] >= 0] for h in hist]
+        keep = three_maxima([len(h) for h in hist], flip)
         for i in range(HISTO):
             if i in keep:
                 continue
