@@ -368,6 +368,13 @@ constexpr int MX_SCALE_ONE = 127;           // E8M0 1.0
 constexpr float MX_BIAS = 10485760.0f;      // 2^23 + 2^21: keys of [-2^21, 2^21 + 32) land in [2^23, 2^24)
 // MX_KEY0, the bit pattern of MX_BIAS (bits = key + MX_KEY0): top2_key.h
 constexpr float MX_PAD = 1073741824.0f;     // rows past nt: above every real key (2^30)
+// k_top2_fp4q2 runs the instruction without block scales, v_mfma_f32_32x32x64_f8f6f4 (both scales 1.0), and gives
+// C the same values 2^-12 times as large (MX_DOWN, top2_key.h): every product, partial sum and key is then the
+// scaled form's times 2^-12, as exact as there (keys in [2^11, 2^12), ulp 2^-12), and its bit pattern the scaled
+// form's minus MX_DOWN_BITS, so the integer updates and the rebase by 32 are the same instructions.  The block
+// scales cost vector issue: the scale operands come through a second instruction word, and in this kernel's
+// step pattern a row tile takes a wave 312 cycles with them and 291 without (tools/micro/mfma_fp4_16_rate.hip,
+// profiles/mfma_fp4_16_rate.jsonl).
 
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -924,8 +931,10 @@ __global__ __launch_bounds__(NW * 64) void k_top2_fp4p(const uint32_t *__restric
 // had while it formed its offsets again from the lane id at every seam and selected zero for rows past nt).  So
 // the seam holds no offset arithmetic: the staging and fragment offsets live in registers through the blocks,
 // the packed rows come through a buffer descriptor whose range check returns zero past row nt, chunk and slot
-// bases are scalar, and both MFMA scales share one register.  The last two blocks of a workgroup, which have no
-// chunk left to expand, are copies of the block without the expansion.
+// bases are scalar, and the MFMA takes no block scales (MX_DOWN above; with them a row tile's step
+// measured 2.6 cycles longer per MFMA than the 8 counted here).  The last two blocks of a workgroup, which have no chunk left to expand, are
+// copies of the block without the expansion.  Per chunk the ISA holds 64 MFMA, 346 VALU, 42 LDS instructions
+// and 13 s_nop, as it did with the scales.
 template <int NW, int CR>
 __global__ __launch_bounds__(NW * 64) void k_top2_fp4q2(const uint32_t *__restrict__ query, int nq,
                                                          const uint32_t *__restrict__ train, int nt,
@@ -1004,11 +1013,11 @@ __global__ __launch_bounds__(NW * 64) void k_top2_fp4q2(const uint32_t *__restri
 #pragma unroll
             for (int d = 4; d < 8; d++) bq[j][s][d] = 0;
         }
-        k1[j] = k2[j] = ((256 - pc) << MF_SHIFT) + MX_KEY0;   // |q| is taken again from the query at the end
+        k1[j] = k2[j] = ((256 - pc) << MF_SHIFT) + MX_KEY0 - MX_DOWN_BITS;   // |q| is taken again from the query at the end
     }
     f32x16 crow;
 #pragma unroll
-    for (int i = 0; i < 16; i++) crow[i] = MX_BIAS + (float)((i & 3) + 8 * (i >> 2) + 4 * h);
+    for (int i = 0; i < 16; i++) crow[i] = (MX_BIAS + (float)((i & 3) + 8 * (i >> 2) + 4 * h)) * MX_DOWN;
     int lbase = r * MX_RS + h * 16;   // the fragment offset within a slot
 
     // the table's word shift as a scalar register the compiler cannot see through: the byte-select shifts that form
@@ -1030,11 +1039,9 @@ __global__ __launch_bounds__(NW * 64) void k_top2_fp4q2(const uint32_t *__restri
         const i32x4 v = *(const i32x4 *)(s_buf + lbase + off + 32 * s);
         return i32x8{v[0], v[1], v[2], v[3], 0, 0, 0, 0};
     };
-    // both E8M0 scales in one register: the train operand's in byte 0 (byte select 0), the query operand's 1.0 in
-    // byte 1 (byte select 1, op_sel:[0,1,0] in the ISA) and once more in byte 2
-    constexpr int MX_SCALES = MX_SCALE_TRAIN | (MX_SCALE_ONE << 8) | (MX_SCALE_ONE << 16);
+    // constant zero scale operands: the compiler emits the instruction without block scales (MX_DOWN above)
     auto mfma = [&](const i32x8 &a, const i32x8 &bb, const f32x16 &c) {
-        return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, bb, c, 4, 4, 0, MX_SCALES, 1, MX_SCALES);
+        return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, bb, c, 4, 4, 0, 0, 0, 0);
     };
     // key pairs 2 s and 2 s + 1 of query tile j's accumulator; after the last pair the first key moves to the
     // next row tile's base.  The second key is never rebased (only its distance is output; top2_key.h has the
@@ -1114,7 +1121,7 @@ __global__ __launch_bounds__(NW * 64) void k_top2_fp4q2(const uint32_t *__restri
 #pragma unroll
             for (int s = 0; s < 4; s++) a[s] = frag(slot * SLOTB, s);
 #pragma unroll
-            for (int i = 0; i < 16; i++) acc1[i] = MX_PAD;
+            for (int i = 0; i < 16; i++) acc1[i] = MX_PAD * MX_DOWN;
             k1[1] += TOP2_TILE_ROWS;
             auto block = [&](int c, auto expand) {
                 // query tile 0 on the first row tile of chunk c (its fragments came with the last row tile of
@@ -1197,18 +1204,19 @@ __global__ __launch_bounds__(NW * 64) void k_top2_fp4q2(const uint32_t *__restri
                 f32x16 cin;
 #pragma unroll
                 for (int i = 0; i < 16; i++)
-                    cin[i] = crow[i] + (4 * h >= lim - ((i & 3) + 8 * (i >> 2)) ? MX_PAD : 0.f);
+                    cin[i] = crow[i] + (4 * h >= lim - ((i & 3) + 8 * (i >> 2)) ? MX_PAD * MX_DOWN : 0.f);
                 tile(sb + nfull * 32 * MX_RS, cin);
             }
         }
     }
     if (!act0) return;
     const int base = 32 * ((nt + 31) / 32);
-    // the lane id taken again here instead of kept in a register through the chunks
-    const int lane_end = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    // the lane id, kept in a register through the chunks where the scales' register was: taken again here from
+    // v_mbcnt, the allocator spilled a query granule (20 B of scratch, reloaded in every block)
+    const int lane_end = lane;
 #pragma unroll
     for (int j = 0; j < 2; j++) {
-        int m1 = k1[j], m2 = k2[j];
+        int m1 = k1[j] + MX_DOWN_BITS, m2 = k2[j] + MX_DOWN_BITS;   // the scaled form's bit patterns (top2_key.h)
         const int a1 = __shfl_xor(m1, 32), a2 = __shfl_xor(m2, 32);
         // key_merge with the first keys' last rebase taken back where one of them becomes a second key
         m2 = min(min(m2, a2), max(m1, a1) + TOP2_K2_LAST_REBASE);

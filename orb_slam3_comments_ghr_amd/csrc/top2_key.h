@@ -22,6 +22,11 @@ constexpr int MX_KEY0 = 0x4B000000 + (1 << 21);    // bit pattern of MX_BIAS (2^
 constexpr int TOP2_TILE_ROWS = 32;                 // rows per tile = the rebase step of k1
 constexpr int TOP2_K2_OFFSET = TOP2_TILE_ROWS * (MF_MAX_ROWS / TOP2_TILE_ROWS - 1);   // 8160
 constexpr int TOP2_K2_LAST_REBASE = TOP2_TILE_ROWS;
+// k_top2_fp4q2 computes every key 2^-12 times as large (MFMA without block scales, C scaled down to match): a
+// float in [2^11, 2^12), whose bit pattern is the one above minus 12 in the exponent field.  The kernel holds
+// bits - MX_DOWN_BITS through the row tiles and adds MX_DOWN_BITS back before the merge and the decode below.
+constexpr float MX_DOWN = 1.0f / 4096.0f;
+constexpr int MX_DOWN_BITS = 12 << 23;
 
 // D * 2^13 + row of a rebased first key (FP4 bit pattern) after the last tile; base = 32 * ceil(nt / 32)
 constexpr int top2_k1_value(int bits, int base) { return bits - MX_KEY0 + base; }
