@@ -1,4 +1,5 @@
-// Optimizer_osg.cc — drop-in bodies for Optimizer::PoseOptimization, the g2o part of
+// Optimizer_osg.cc — drop-in bodies for Optimizer::PoseOptimization, Optimizer::PoseInertialOptimizationLastKeyFrame /
+// LastFrame, the g2o part of
 // Optimizer::LocalBundleAdjustment (both overloads), Optimizer::BundleAdjustment (global BA) and
 // Optimizer::OptimizeSim3 and Optimizer::OptimizeEssentialGraph (the loop-closure overload) on the MI355X path (ORB-SLAM3 tree built with -DORB_SLAM3_OSG;
 // see INTEGRATION.md).  Signatures: ref:include/Optimizer.h:54-90.
@@ -11,6 +12,17 @@ int Optimizer::PoseOptimization(Frame *pFrame)
 {  // ref:src/Optimizer.cc:71-420; MapPoint::mGlobalMutex is held only while the edges are gathered
    // (:128-286), released before the GPU solve and the write-back
     return osg_orbslam3::pose_optimization<OsgHooks>(pFrame, &MapPoint::mGlobalMutex);
+}
+
+int Optimizer::PoseInertialOptimizationLastKeyFrame(Frame *pFrame, bool bRecInit)
+{  // ref:src/Optimizer.cc:435-987; MapPoint::mGlobalMutex is held while the edges are gathered (:506-635)
+    return osg_orbslam3::pose_inertial_optimization_last_keyframe<OsgHooks>(pFrame, bRecInit, &MapPoint::mGlobalMutex);
+}
+
+int Optimizer::PoseInertialOptimizationLastFrame(Frame *pFrame, bool bRecInit)
+{  // ref:src/Optimizer.cc:1002-1640; a previous frame without mpcpi is refused by the library (the reference
+   // dereferences null at :1275) and 0 is returned with the frame untouched
+    return osg_orbslam3::pose_inertial_optimization_last_frame<OsgHooks>(pFrame, bRecInit, &MapPoint::mGlobalMutex);
 }
 
 // The local window (ref:src/Optimizer.cc:1762-1873) is the reference's code unchanged; it ends with

@@ -5,6 +5,7 @@
 #define OSG_HOOKS_ORBSLAM3_H
 
 #include "Frame.h"
+#include "G2oTypes.h"
 #include "KeyFrame.h"
 #include "MapPoint.h"
 #include "Thirdparty/DBoW2/DUtils/Random.h"
@@ -394,6 +395,104 @@ struct OsgHooks {
         const Eigen::Vector3f P = p->GetWorldPos(), Pn = p->GetNormal();
         for (int k = 0; k < 3; k++) pos[k] = P(k), normal[k] = Pn(k);
         p->GetDistanceRange(max_dist, min_dist);
+    }
+    // ---- PoseInertialOptimization ("PoseInertialOptimization")
+    static void imu_state_from(const Eigen::Matrix3f &Rwb, const Eigen::Vector3f &twb, const Eigen::Vector3f &v,
+                               const Eigen::Vector3d &bg, const Eigen::Vector3d &ba, osg_pio_state &s)
+    {
+        const Eigen::Matrix3d R = Rwb.cast<double>();
+        const Eigen::Vector3d t = twb.cast<double>(), vd = v.cast<double>();
+        for (int r = 0; r < 3; r++) {
+            for (int c = 0; c < 3; c++) s.Rwb[3 * r + c] = R(r, c);
+            s.twb[r] = t(r), s.v[r] = vd(r), s.bg[r] = bg(r), s.ba[r] = ba(r);
+        }
+    }
+    // VertexPose / VertexVelocity / VertexGyroBias / VertexAccBias of a Frame (ref:src/G2oTypes.cc:81-127, 537-564)
+    static void imu_state(Frame &F, osg_pio_state &s)
+    {
+        Eigen::Vector3d bg, ba;
+        bg << F.mImuBias.bwx, F.mImuBias.bwy, F.mImuBias.bwz;
+        ba << F.mImuBias.bax, F.mImuBias.bay, F.mImuBias.baz;
+        imu_state_from(F.GetImuRotation(), F.GetImuPosition(), F.GetVelocity(), bg, ba, s);
+    }
+    // ... and of a KeyFrame (ref:src/G2oTypes.cc:29-75, 532-557)
+    static void imu_state(KeyFrame &K, osg_pio_state &s)
+    {
+        imu_state_from(K.GetImuRotation(), K.GetImuPosition(), K.GetVelocity(), K.GetGyroBias().cast<double>(),
+                       K.GetAccBias().cast<double>(), s);
+    }
+    // ImuCamPose(Frame*) (ref:src/G2oTypes.cc:81-127)
+    static void imu_cameras(Frame &F, osg_pose_inertial_problem &p)
+    {
+        auto put3 = [](const Eigen::Matrix3d &M, double *o) {
+            for (int r = 0; r < 3; r++)
+                for (int c = 0; c < 3; c++) o[3 * r + c] = M(r, c);
+        };
+        auto putv = [](const Eigen::Vector3d &v, double *o) {
+            for (int r = 0; r < 3; r++) o[r] = v(r);
+        };
+        p.n_cams = F.mpCamera2 ? 2 : 1;
+        const Eigen::Vector3d tcw0 = F.GetPose().translation().cast<double>();
+        const Eigen::Matrix3d Rcw0 = F.GetPose().rotationMatrix().cast<double>();
+        const Eigen::Vector3d tcb0 = F.mImuCalib.mTcb.translation().cast<double>();
+        const Eigen::Matrix3d Rcb0 = F.mImuCalib.mTcb.rotationMatrix().cast<double>();
+        camera(F, false, p.cams[0].cam);
+        put3(Rcw0, p.cams[0].Rcw), putv(tcw0, p.cams[0].tcw), put3(Rcb0, p.cams[0].Rcb), putv(tcb0, p.cams[0].tcb);
+        putv(F.mImuCalib.mTbc.translation().cast<double>(), p.cams[0].tbc);
+        p.bf = F.mbf;
+        if (p.n_cams > 1) {
+            const Eigen::Matrix4d Trl = F.GetRelativePoseTrl().matrix().cast<double>();
+            const Eigen::Matrix3d Rrl = Trl.block<3, 3>(0, 0);
+            const Eigen::Vector3d trl = Trl.block<3, 1>(0, 3);
+            const Eigen::Matrix3d Rcb1 = Rrl * Rcb0;
+            const Eigen::Vector3d tcb1 = Rrl * tcb0 + trl;
+            camera(F, true, p.cams[1].cam);
+            put3(Rrl * Rcw0, p.cams[1].Rcw), putv(Rrl * tcw0 + trl, p.cams[1].tcw);
+            put3(Rcb1, p.cams[1].Rcb), putv(tcb1, p.cams[1].tcb);
+            putv(-Rcb1.transpose() * tcb1, p.cams[1].tbc);
+        }
+    }
+    static void preintegrated(IMU::Preintegrated *pInt, osg_pio_preintegrated &q)
+    {
+        auto put3 = [](const Eigen::Matrix3f &M, float *o) {
+            for (int r = 0; r < 3; r++)
+                for (int c = 0; c < 3; c++) o[3 * r + c] = M(r, c);
+        };
+        put3(pInt->dR, q.dR), put3(pInt->JRg, q.JRg), put3(pInt->JVg, q.JVg), put3(pInt->JVa, q.JVa);
+        put3(pInt->JPg, q.JPg), put3(pInt->JPa, q.JPa);
+        for (int r = 0; r < 3; r++) q.dV[r] = pInt->dV(r), q.dP[r] = pInt->dP(r);
+        const IMU::Bias b = pInt->GetOriginalBias();
+        q.b[0] = b.bax, q.b[1] = b.bay, q.b[2] = b.baz, q.b[3] = b.bwx, q.b[4] = b.bwy, q.b[5] = b.bwz;
+        q.dT = pInt->dT;
+        for (int r = 0; r < 15; r++)
+            for (int c = 0; c < 15; c++) q.C[15 * r + c] = pInt->C(r, c);
+    }
+    static void constraint(const ConstraintPoseImu *c, osg_pio_prior &pr)
+    {
+        for (int r = 0; r < 3; r++) {
+            for (int k = 0; k < 3; k++) pr.Rwb[3 * r + k] = c->Rwb(r, k);
+            pr.twb[r] = c->twb(r), pr.vwb[r] = c->vwb(r), pr.bg[r] = c->bg(r), pr.ba[r] = c->ba(r);
+        }
+        for (int r = 0; r < 15; r++)
+            for (int k = 0; k < 15; k++) pr.H[15 * r + k] = c->H(r, k);
+    }
+    static float track_depth(MapPoint *p) { return p->mTrackDepth; }
+    // ref:src/Optimizer.cc:883-887 / 1466-1470
+    static void set_imu_state(Frame &F, const osg_pio_state &s)
+    {
+        const Eigen::Matrix3d R = Eigen::Map<const Eigen::Matrix<double, 3, 3, Eigen::RowMajor>>(s.Rwb);
+        const Eigen::Vector3d t(s.twb[0], s.twb[1], s.twb[2]), v(s.v[0], s.v[1], s.v[2]);
+        F.SetImuPoseVelocity(R.cast<float>(), t.cast<float>(), v.cast<float>());
+        Eigen::Matrix<double, 6, 1> b;
+        b << s.bg[0], s.bg[1], s.bg[2], s.ba[0], s.ba[1], s.ba[2];
+        F.mImuBias = IMU::Bias(b[3], b[4], b[5], b[0], b[1], b[2]);
+    }
+    static ConstraintPoseImu *new_constraint(const osg_pio_state &s, const double H[225])
+    {
+        const Eigen::Matrix3d R = Eigen::Map<const Eigen::Matrix<double, 3, 3, Eigen::RowMajor>>(s.Rwb);
+        const Eigen::Matrix<double, 15, 15> Hm = Eigen::Map<const Eigen::Matrix<double, 15, 15, Eigen::RowMajor>>(H);
+        return new ConstraintPoseImu(R, Eigen::Vector3d(s.twb[0], s.twb[1], s.twb[2]), Eigen::Vector3d(s.v[0], s.v[1], s.v[2]),
+                                     Eigen::Vector3d(s.bg[0], s.bg[1], s.bg[2]), Eigen::Vector3d(s.ba[0], s.ba[1], s.ba[2]), Hm);
     }
     // KeyFrameDatabase: the vocabulary on the device, set by System right after it loads ORBvoc
     // (osg_vocabulary_load_text) and before it constructs the database

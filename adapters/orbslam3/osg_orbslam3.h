@@ -1479,6 +1479,130 @@ int pose_optimization(FrameT *pFrame, MutexT *gather_mutex = nullptr)
     return g.apply(pFrame, r);
 }
 
+// ------------------------------------------------- a10i PoseInertialOptimizationLastKeyFrame / LastFrame
+// ref:src/Optimizer.cc:435-987, 1002-1640.  The gather is the reference's three-way slot rule (:508-633 / :1075-1199):
+// left or only mono (mvKeys when the frame is a rig, mvKeysUn otherwise), stereo, right mono of a rig, under
+// `gather_mutex` (MapPoint::mGlobalMutex); mvbOutlier of every gathered slot is cleared there.  The vertices, the
+// preintegration and (LastFrame) the previous frame's ConstraintPoseImu are read through the hooks:
+//   H::imu_state(frame_or_keyframe, osg_pio_state&)        VertexPose / Velocity / GyroBias / AccBias constructors
+//   H::imu_cameras(frame, osg_pose_inertial_problem&)      ImuCamPose(Frame*): n_cams, cams[], bf
+//   H::preintegrated(pInt, osg_pio_preintegrated&)         the float fields of IMU::Preintegrated
+//   H::constraint(mpcpi, osg_pio_prior&)                   ConstraintPoseImu as stored
+//   H::track_depth(MapPoint*)                              mTrackDepth
+//   H::set_imu_state(frame, const osg_pio_state&)          SetImuPoseVelocity with the float casts, and mImuBias
+//                                                          from b = (bg, ba) as IMU::Bias(b[3], b[4], b[5], b[0], b[1], b[2])
+//   H::new_constraint(const osg_pio_state&, const double H[225])   new ConstraintPoseImu(Rwb, twb, v, bg, ba, H)
+// uncertainty2 is 1 in both camera models, so the weight is mvInvLevelSigma2[octave].
+template <class H, class FrameT>
+struct PoseInertialGather {
+    std::vector<int8_t> kind;
+    std::vector<double> xw, obs;
+    std::vector<float> isig, depth;
+    std::vector<int> slot;
+    std::vector<uint8_t> outl;
+    osg_pio_preintegrated pre{};
+    float C_rw[225];
+    osg_pio_prior prior{};
+    osg_pose_inertial_problem p{};
+    bool has_prior = false;
+
+    template <class MutexT>
+    void assign(FrameT *pFrame, bool last_frame, bool bRecInit, MutexT *gather_mutex)
+    {
+        const int N = pFrame->N, Nleft = pFrame->Nleft;
+        const bool bRight = (Nleft != -1);
+        p = osg_pose_inertial_problem{};
+        kind.clear(), xw.clear(), obs.clear(), isig.clear(), depth.clear(), slot.clear();
+        auto add = [&](int i, int8_t k, const auto &kp, float ur) {
+            auto *pMP = pFrame->mvpMapPoints[i];
+            pFrame->mvbOutlier[i] = false;
+            double X[3];
+            H::world_pos(pMP, X);
+            xw.insert(xw.end(), X, X + 3);
+            obs.push_back(kp.pt.x);
+            obs.push_back(kp.pt.y);
+            obs.push_back(k == OSG_EDGE_STEREO ? (double)ur : 0.0);
+            kind.push_back(k);
+            isig.push_back(pFrame->mvInvLevelSigma2[kp.octave]);
+            depth.push_back(H::track_depth(pMP));
+            slot.push_back(i);
+        };
+        {
+            std::unique_lock<MutexT> gather_lock;
+            if (gather_mutex) gather_lock = std::unique_lock<MutexT>(*gather_mutex);
+            for (int i = 0; i < N; i++) {
+                if (!pFrame->mvpMapPoints[i]) continue;
+                if ((!bRight && pFrame->mvuRight[i] < 0) || i < Nleft)
+                    add(i, OSG_EDGE_MONO, i < Nleft ? pFrame->mvKeys[i] : pFrame->mvKeysUn[i], 0.f);
+                else if (!bRight)
+                    add(i, OSG_EDGE_STEREO, pFrame->mvKeysUn[i], pFrame->mvuRight[i]);
+                if (bRight && i >= Nleft) add(i, OSG_EDGE_BODY, pFrame->mvKeysRight[i - Nleft], 0.f);
+            }
+        }
+        p.mode = last_frame ? OSG_PIO_LAST_FRAME : OSG_PIO_LAST_KEYFRAME;
+        p.rec_init = bRecInit ? 1 : 0;
+        H::imu_state(*pFrame, p.cur);
+        H::imu_cameras(*pFrame, p);
+        if (last_frame) {
+            H::imu_state(*pFrame->mpPrevFrame, p.prev);
+            H::preintegrated(pFrame->mpImuPreintegratedFrame, pre);
+            has_prior = pFrame->mpPrevFrame->mpcpi != nullptr;
+            if (has_prior) H::constraint(pFrame->mpPrevFrame->mpcpi, prior);
+        } else {
+            H::imu_state(*pFrame->mpLastKeyFrame, p.prev);
+            H::preintegrated(pFrame->mpImuPreintegrated, pre);
+            has_prior = false;
+        }
+        {  // the random-walk informations read mpImuPreintegrated->C in both functions (:688, :1252)
+            osg_pio_preintegrated kf{};
+            H::preintegrated(pFrame->mpImuPreintegrated, kf);
+            std::memcpy(C_rw, kf.C, sizeof C_rw);
+        }
+        p.n_edges = (int32_t)kind.size();
+        p.kind = kind.data();
+        p.xw = xw.data();
+        p.obs = obs.data();
+        p.inv_sigma2 = isig.data();
+        p.track_depth = depth.data();
+        p.preint = &pre;
+        p.C_rw = C_rw;
+        p.prior = has_prior ? &prior : nullptr;  // LastFrame without mpcpi: the library answers OSG_E_INVALID
+        outl.assign(kind.size(), 0);
+    }
+};
+
+template <class H, class FrameT, class MutexT>
+int pose_inertial_optimization(FrameT *pFrame, bool last_frame, bool bRecInit, MutexT *gather_mutex)
+{
+    osg_ctx *ctx = thread_ctx();
+    PoseInertialGather<H, FrameT> g;
+    g.assign(pFrame, last_frame, bRecInit, gather_mutex);
+    osg_pose_inertial_result r{};
+    r.outlier = g.outl.data();
+    if (call(ctx, "osg_pose_inertial_optimization", [&] { return osg_pose_inertial_optimization(ctx, &g.p, &r); }) < 0)
+        return 0;
+    for (size_t e = 0; e < g.slot.size(); e++) pFrame->mvbOutlier[g.slot[e]] = g.outl[e] != 0;
+    H::set_imu_state(*pFrame, r.state);                     // :883-887 / :1466-1470
+    pFrame->mpcpi = H::new_constraint(r.state, r.H);        // :982 / :1635
+    if (last_frame) {                                       // :1637-1638
+        delete pFrame->mpPrevFrame->mpcpi;
+        pFrame->mpPrevFrame->mpcpi = nullptr;
+    }
+    return r.n_inliers;
+}
+
+template <class H, class FrameT, class MutexT = NoMutex>
+int pose_inertial_optimization_last_keyframe(FrameT *pFrame, bool bRecInit = false, MutexT *gather_mutex = nullptr)
+{
+    return pose_inertial_optimization<H>(pFrame, false, bRecInit, gather_mutex);
+}
+
+template <class H, class FrameT, class MutexT = NoMutex>
+int pose_inertial_optimization_last_frame(FrameT *pFrame, bool bRecInit = false, MutexT *gather_mutex = nullptr)
+{
+    return pose_inertial_optimization<H>(pFrame, true, bRecInit, gather_mutex);
+}
+
 // ---------------------------------------------------------- a11 LocalBundleAdjustment (g2o part)
 // The local window (ref:src/Optimizer.cc:1762-1873: lLocalKeyFrames, lLocalMapPoints,
 // lFixedCameras) is collected by the reference code unchanged; from the graph build on

@@ -2,6 +2,9 @@
  * osg_ba.h — C ABI of the bundle-adjustment half of the hot path.
  *
  *   osg_pose_optimization[_batch]  ← Optimizer::PoseOptimization(Frame*)        ref:src/Optimizer.cc:71-420
+ *   osg_pose_inertial_optimization[_batch]
+ *                                  ← Optimizer::PoseInertialOptimizationLastKeyFrame / LastFrame
+ *                                    (ref:src/Optimizer.cc:435-987, 1002-1744)
  *   osg_local_bundle_adjustment    ← the g2o part of Optimizer::LocalBundleAdjustment
  *                                    (ref:src/Optimizer.cc:1877-2203: graph → optimize(10) →
  *                                    outlier classification → estimates out)
@@ -71,6 +74,102 @@ int osg_pose_optimization(struct osg_ctx *ctx, const osg_pose_problem *p, osg_po
 /* n independent frames in one launch (frame-batched tracking, sequences sharded over GPUs). */
 int osg_pose_optimization_batch(struct osg_ctx *ctx, const osg_pose_problem *p, int32_t n,
                                 osg_pose_result *r);
+
+/* ---- PoseInertialOptimization ---------------------------------------------------------------
+ * Optimizer::PoseInertialOptimizationLastKeyFrame (ref:src/Optimizer.cc:435-987) and
+ * Optimizer::PoseInertialOptimizationLastFrame (ref:src/Optimizer.cc:1002-1640): what Tracking::TrackLocalMap
+ * calls in place of PoseOptimization once the IMU is initialised.  The current frame's VertexPose (body pose
+ * Rwb, twb), VertexVelocity, VertexGyroBias and VertexAccBias are free; the same four of the previous KeyFrame
+ * are fixed (LAST_KEYFRAME) or of the previous frame free (LAST_FRAME).  Edges: one EdgeMonoOnlyPose /
+ * EdgeStereoOnlyPose per gathered slot (Huber sqrt(5.991) / sqrt(7.815), removed after the third round),
+ * EdgeInertial over the preintegration, EdgeGyroRW, EdgeAccRW, and in LAST_FRAME EdgePriorPoseImu (Huber 5)
+ * on the previous frame.  g2o's Gauss-Newton (no damping, no trial loop) on the dense 15 x 15 / 30 x 30
+ * system, four rounds of optimize(10) with the reference's classification after each, the recovery pass, and
+ * the new prior's H (LAST_FRAME: marginalised onto the current frame) run in one launch, one workgroup per
+ * problem.  Parity with the reference is tolerance-based. */
+#define OSG_PIO_LAST_KEYFRAME 0
+#define OSG_PIO_LAST_FRAME 1
+
+typedef struct osg_pio_state {
+    double Rwb[9];            /* row-major, GetImuRotation().cast<double>() */
+    double twb[3];            /* GetImuPosition() */
+    double v[3];              /* GetVelocity() */
+    double bg[3];             /* gyro bias (bwx, bwy, bwz) */
+    double ba[3];             /* accelerometer bias (bax, bay, baz) */
+} osg_pio_state;
+
+/* one camera of ImuCamPose(Frame*) (ref:src/G2oTypes.cc:81-127); the second camera of a rig through Trl */
+typedef struct osg_pio_camera {
+    osg_camera cam;           /* pCamera[i]: type and p[] are read */
+    double Rcw[9], tcw[3];    /* as constructed from the Frame's pose; re-derived from Rwb, twb at every update */
+    double Rcb[9], tcb[3];
+    double tbc[3];            /* Rbc is Rcb transposed */
+} osg_pio_camera;
+
+/* IMU::Preintegrated as EdgeInertial reads it: the stored float fields (matrices row-major) */
+typedef struct osg_pio_preintegrated {
+    float dR[9], dV[3], dP[3];
+    float JRg[9], JVg[9], JVa[9], JPg[9], JPa[9];
+    float b[6];               /* the bias of the integration: (bax, bay, baz, bwx, bwy, bwz) */
+    float dT;
+    float C[225];             /* 15 x 15 covariance; EdgeInertial's information is derived from C[0:9, 0:9] */
+} osg_pio_preintegrated;
+
+/* ConstraintPoseImu of the previous frame (pFp->mpcpi), H as stored (after the constructor) */
+typedef struct osg_pio_prior {
+    double Rwb[9], twb[3], vwb[3], bg[3], ba[3];
+    double H[225];
+} osg_pio_prior;
+
+typedef struct osg_pose_inertial_problem {
+    int32_t mode;             /* OSG_PIO_* */
+    int32_t rec_init;         /* bRecInit: no recovery pass */
+    osg_pio_state cur;        /* pFrame */
+    osg_pio_state prev;       /* pFrame->mpLastKeyFrame (LAST_KEYFRAME) or pFrame->mpPrevFrame (LAST_FRAME) */
+    int32_t n_cams;           /* 1, or 2 when mpCamera2 */
+    osg_pio_camera cams[2];
+    double bf;                /* mbf cast to double */
+    int32_t n_edges;          /* one per gathered slot, in slot order */
+    const int8_t *kind;       /* OSG_EDGE_MONO: left or only camera; OSG_EDGE_STEREO; OSG_EDGE_BODY: right camera */
+    const double *xw;         /* 3 per edge: GetWorldPos().cast<double>() */
+    const double *obs;        /* 3 per edge: (u, v, ur), ur read for STEREO only */
+    const float *inv_sigma2;  /* mvInvLevelSigma2[octave] / uncertainty2 */
+    const float *track_depth; /* mTrackDepth, read for MONO and BODY edges only */
+    const osg_pio_preintegrated *preint; /* mpImuPreintegrated (LAST_KEYFRAME) / mpImuPreintegratedFrame (LAST_FRAME) */
+    const float *C_rw;        /* 225: mpImuPreintegrated->C, whose blocks (9, 9) and (12, 12) give the random-walk
+                                 informations in BOTH modes (ref:src/Optimizer.cc:688, 701, 1252, 1265) */
+    const osg_pio_prior *prior; /* LAST_FRAME only; NULL there is OSG_E_INVALID */
+} osg_pose_inertial_problem;
+
+typedef struct osg_pose_inertial_result {
+    osg_pio_state state;      /* the current frame after the optimisation (bg, ba: mImuBias in double) */
+    uint8_t *outlier;         /* n_edges: mvbOutlier of each edge's slot */
+    int32_t n_inliers;        /* the reference's return value: nInitialCorrespondences - nBad */
+    int32_t rounds_run;       /* 1..4 (the edges().size() < 10 break ends after the first) */
+    int32_t iterations;       /* linear solves performed */
+    int32_t solve_failed;     /* a pivot of the unpivoted LDL^T was not positive in some round */
+    int32_t recovered;        /* the recovery pass ran (nInliers < 30 and not rec_init) */
+    double H[225];            /* as passed to ConstraintPoseImu's constructor, whose own post-processing is the
+                                 caller's (constraint_pose_imu in the Python package, the adapter in C++) */
+    double *edge_chi2;        /* optional (NULL: not written), n_edges: as read by each edge's last classification */
+} osg_pose_inertial_result;
+
+/* Returns n_inliers or a negative OSG_E_* code.  OSG_E_INVALID (nothing written, the context stays usable): a
+ * null pointer, a negative count, an unknown mode or edge kind, n_cams outside {1, 2}, a BODY edge with one
+ * camera, LAST_FRAME without a prior, more than 16 384 edges. */
+int osg_pose_inertial_optimization(struct osg_ctx *ctx, const osg_pose_inertial_problem *p,
+                                   osg_pose_inertial_result *r);
+/* n independent frames in one launch (sequences sharded over a GPU).  Returns the summed n_inliers or a
+ * negative OSG_E_* code.  No reference counterpart. */
+int osg_pose_inertial_optimization_batch(struct osg_ctx *ctx, const osg_pose_inertial_problem *p, int32_t n,
+                                         osg_pose_inertial_result *r);
+/* The argument checks alone (needs no context): 0 or OSG_E_INVALID. */
+int osg_pose_inertial_check(const osg_pose_inertial_problem *p);
+/* EdgeInertial's information (ref:src/G2oTypes.cc:582-593) from a 15 x 15 float C: the inverse of its leading
+ * 9 x 9 in double, symmetrised, eigenvalues below 1e-12 set to 0 -> info9[81]; the inverses of blocks (9, 9)
+ * and (12, 12) of C_rw -> info_g[9], info_a[9].  Host only; any output may be NULL. */
+void osg_pose_inertial_informations(const float *C, const float *C_rw, double *info9, double *info_g,
+                                    double *info_a);
 
 /* ---- OptimizeSim3 --------------------------------------------------------------------------
  * Optimizer::OptimizeSim3 (ref:src/Optimizer.cc:4213-4512), LoopClosing's Sim3 refinement between two

@@ -197,6 +197,46 @@ class OsgPoseResult(C.Structure):
     ]
 
 
+class OsgPioState(C.Structure):
+    _fields_ = [("Rwb", f64 * 9), ("twb", f64 * 3), ("v", f64 * 3), ("bg", f64 * 3), ("ba", f64 * 3)]
+
+
+class OsgPioCamera(C.Structure):
+    _fields_ = [("cam", OsgCamera), ("Rcw", f64 * 9), ("tcw", f64 * 3), ("Rcb", f64 * 9), ("tcb", f64 * 3),
+                ("tbc", f64 * 3)]
+
+
+class OsgPioPreintegrated(C.Structure):
+    _fields_ = [
+        ("dR", f32 * 9), ("dV", f32 * 3), ("dP", f32 * 3), ("JRg", f32 * 9), ("JVg", f32 * 9), ("JVa", f32 * 9),
+        ("JPg", f32 * 9), ("JPa", f32 * 9), ("b", f32 * 6), ("dT", f32), ("C", f32 * 225),
+    ]
+
+
+class OsgPioPrior(C.Structure):
+    _fields_ = [("Rwb", f64 * 9), ("twb", f64 * 3), ("vwb", f64 * 3), ("bg", f64 * 3), ("ba", f64 * 3),
+                ("H", f64 * 225)]
+
+
+class OsgPoseInertialProblem(C.Structure):
+    _fields_ = [
+        ("mode", i32), ("rec_init", i32), ("cur", OsgPioState), ("prev", OsgPioState), ("n_cams", i32),
+        ("cams", OsgPioCamera * 2), ("bf", f64), ("n_edges", i32), ("kind", P), ("xw", P), ("obs", P),
+        ("inv_sigma2", P), ("track_depth", P), ("preint", P), ("C_rw", P), ("prior", P),
+    ]
+
+
+class OsgPoseInertialResult(C.Structure):
+    _fields_ = [
+        ("state", OsgPioState), ("outlier", P), ("n_inliers", i32), ("rounds_run", i32), ("iterations", i32),
+        ("solve_failed", i32), ("recovered", i32), ("H", f64 * 225), ("edge_chi2", P),
+    ]
+
+
+OSG_PIO_LAST_KEYFRAME = 0
+OSG_PIO_LAST_FRAME = 1
+
+
 class OsgSim3Problem(C.Structure):
     _fields_ = [
         ("q", f64 * 4), ("t", f64 * 3), ("s", f64), ("fix_scale", i32), ("th2", f32),
@@ -342,6 +382,8 @@ EXPORTS = [
     "osg_match_last_stats", "osg_match_last_path", "osg_debug_match_plan", "osg_ctx_last_kernel_ms", "osg_ctx_device_bytes", "osg_pose_optimization", "osg_pose_optimization_batch",
     "osg_local_bundle_adjustment", "osg_local_bundle_adjustment_batch", "osg_bundle_adjustment",
     "osg_lba_kernel_times", "osg_optimize_sim3", "osg_optimize_sim3_batch",
+    "osg_pose_inertial_optimization", "osg_pose_inertial_optimization_batch", "osg_pose_inertial_check",
+    "osg_pose_inertial_informations",
     "osg_sim3_ransac", "osg_sim3_ransac_batch", "osg_sim3_ransac_iterations",
     "osg_mlpnp_ransac", "osg_mlpnp_ransac_batch", "osg_mlpnp_ransac_parameters", "osg_mlpnp_check_samples",
     "osg_optimize_essential_graph", "osg_essgraph_correct_points", "osg_essgraph_kernel_times",
@@ -410,6 +452,13 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.osg_pose_optimization.argtypes = [vp, C.POINTER(OsgPoseProblem), C.POINTER(OsgPoseResult)]
     lib.osg_pose_optimization_batch.argtypes = [vp, C.POINTER(OsgPoseProblem), i32,
                                                 C.POINTER(OsgPoseResult)]
+    lib.osg_pose_inertial_optimization.argtypes = [vp, C.POINTER(OsgPoseInertialProblem),
+                                                   C.POINTER(OsgPoseInertialResult)]
+    lib.osg_pose_inertial_optimization_batch.argtypes = [vp, C.POINTER(OsgPoseInertialProblem), i32,
+                                                         C.POINTER(OsgPoseInertialResult)]
+    lib.osg_pose_inertial_check.argtypes = [C.POINTER(OsgPoseInertialProblem)]
+    lib.osg_pose_inertial_informations.argtypes = [vp, vp, vp, vp, vp]
+    lib.osg_pose_inertial_informations.restype = None
     lib.osg_optimize_sim3.argtypes = [vp, C.POINTER(OsgSim3Problem), C.POINTER(OsgSim3Result)]
     lib.osg_optimize_sim3_batch.argtypes = [vp, C.POINTER(OsgSim3Problem), i32, C.POINTER(OsgSim3Result)]
     lib.osg_sim3_ransac.argtypes = [vp, C.POINTER(OsgSim3RansacProblem), C.POINTER(OsgSim3RansacResult)]

@@ -395,6 +395,31 @@ class Optimizer:
         self.ctx.check(rc, "PoseOptimization")
         return out[0] if single else out
 
+    def _pose_inertial(self, problems, mode):
+        single = isinstance(problems, PoseInertialProblem)
+        probs = [problems] if single else list(problems)
+        for q in probs:
+            if q.mode != mode:
+                raise ValueError("a problem of the other mode")
+        out = run_pose_inertial(self.ctx, probs)
+        return out[0] if single else out
+
+    def PoseInertialOptimizationLastKeyFrame(self, problems):
+        """``Optimizer::PoseInertialOptimizationLastKeyFrame`` (ref:src/Optimizer.cc:435-987) for one
+        PoseInertialProblem or a list of them (one launch, a workgroup per frame).  The reference's return value
+        is ``n_inliers``; ``constraint_pose_imu(result.H)`` is the new frame's ``mpcpi``."""
+        return self._pose_inertial(problems, _abi.OSG_PIO_LAST_KEYFRAME)
+
+    def PoseInertialOptimizationLastFrame(self, problems):
+        """``Optimizer::PoseInertialOptimizationLastFrame`` (ref:src/Optimizer.cc:1002-1640), as above; every
+        problem carries the previous frame's prior."""
+        return self._pose_inertial(problems, _abi.OSG_PIO_LAST_FRAME)
+
+    def pose_inertial_optimization_mixed(self, problems):
+        """A batch that mixes both modes in one launch (no reference counterpart; the C batch entry point takes
+        any mixture)."""
+        return run_pose_inertial(self.ctx, list(problems))
+
     def OptimizeSim3(self, problems):
         """``Optimizer::OptimizeSim3`` (ref:src/Optimizer.cc:4213-4512) for one Sim3Problem or a list of
         them (one launch, a workgroup per problem).  The caller nulls ``vpMatches1`` where ``pair_state``
@@ -1015,3 +1040,344 @@ def merge_local_bundle_adjustment(G: BAGraph, run, stop_flag=None, mp_bad=None):
     th = np.where(G.e_kind[l1] == _abi.EDGE_STEREO, 7.815, 5.991)
     bad[l1] = (r1.edge_chi2[l1] > th) | ~depth_positive(G, r2.pose, r2.point, l1)
     return r2.pose, r2.point, (bad & ~skip).astype(np.uint8), False
+
+
+# ----------------------------------------------------------------------------- PoseInertialOptimization
+def _f32(a):
+    """A Frame / KeyFrame / Preintegrated field: stored as float, read through .cast<double>()."""
+    return np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
+
+
+@dataclass
+class ImuState:
+    """VertexPose (body pose), VertexVelocity, VertexGyroBias, VertexAccBias of one frame, in double."""
+    Rwb: np.ndarray
+    twb: np.ndarray
+    v: np.ndarray
+    bg: np.ndarray
+    ba: np.ndarray
+
+    def __post_init__(self):
+        self.Rwb = np.ascontiguousarray(self.Rwb, np.float64).reshape(3, 3)
+        self.twb, self.v, self.bg, self.ba = (np.ascontiguousarray(a, np.float64).reshape(3)
+                                              for a in (self.twb, self.v, self.bg, self.ba))
+
+    def fill(self, st):
+        st.Rwb[:] = self.Rwb.ravel().tolist()
+        st.twb[:], st.v[:], st.bg[:], st.ba[:] = (a.tolist() for a in (self.twb, self.v, self.bg, self.ba))
+
+    @staticmethod
+    def of(st):
+        return ImuState(np.array(st.Rwb[:]), np.array(st.twb[:]), np.array(st.v[:]), np.array(st.bg[:]),
+                        np.array(st.ba[:]))
+
+
+@dataclass
+class ImuCamera:
+    """One camera of ImuCamPose (ref:src/G2oTypes.cc:81-127)."""
+    cam: object
+    Rcw: np.ndarray
+    tcw: np.ndarray
+    Rcb: np.ndarray
+    tcb: np.ndarray
+    tbc: np.ndarray
+
+
+@dataclass
+class Preintegrated:
+    """IMU::Preintegrated as EdgeInertial reads it: float32 fields."""
+    dR: np.ndarray
+    dV: np.ndarray
+    dP: np.ndarray
+    JRg: np.ndarray
+    JVg: np.ndarray
+    JVa: np.ndarray
+    JPg: np.ndarray
+    JPa: np.ndarray
+    b: np.ndarray             # (bax, bay, baz, bwx, bwy, bwz)
+    dT: float
+    C: np.ndarray             # 15 x 15
+
+    def __post_init__(self):
+        for k in ("dR", "JRg", "JVg", "JVa", "JPg", "JPa"):
+            setattr(self, k, np.ascontiguousarray(getattr(self, k), np.float32).reshape(3, 3))
+        self.dV, self.dP = (np.ascontiguousarray(a, np.float32).reshape(3) for a in (self.dV, self.dP))
+        self.b = np.ascontiguousarray(self.b, np.float32).reshape(6)
+        self.dT = np.float32(self.dT)
+        self.C = np.ascontiguousarray(self.C, np.float32).reshape(15, 15)
+
+    def struct(self):
+        st = _abi.OsgPioPreintegrated()
+        for k in ("dR", "dV", "dP", "JRg", "JVg", "JVa", "JPg", "JPa", "b", "C"):
+            getattr(st, k)[:] = getattr(self, k).ravel().tolist()
+        st.dT = float(self.dT)
+        return st
+
+
+@dataclass
+class ImuPrior:
+    """ConstraintPoseImu (ref:include/G2oTypes.h:820-846): H as stored, after the constructor."""
+    Rwb: np.ndarray
+    twb: np.ndarray
+    vwb: np.ndarray
+    bg: np.ndarray
+    ba: np.ndarray
+    H: np.ndarray
+
+    def struct(self):
+        st = _abi.OsgPioPrior()
+        st.Rwb[:] = np.asarray(self.Rwb, np.float64).ravel().tolist()
+        for k in ("twb", "vwb", "bg", "ba"):
+            getattr(st, k)[:] = np.asarray(getattr(self, k), np.float64).ravel().tolist()
+        st.H[:] = np.asarray(self.H, np.float64).ravel().tolist()
+        return st
+
+
+@dataclass
+class PoseInertialProblem:
+    """One ``PoseInertialOptimizationLastKeyFrame`` / ``LastFrame`` call as the adapter gathers it
+    (include/osg_ba.h): the edges in slot order, every Frame field a float-valued double."""
+    mode: int
+    cur: ImuState
+    prev: ImuState
+    cams: list                # one or two ImuCamera
+    bf: float
+    kind: np.ndarray          # int8 per edge: EDGE_MONO (left / only), EDGE_STEREO, EDGE_BODY (right)
+    xw: np.ndarray            # n x 3 double
+    obs: np.ndarray           # n x 3 double
+    inv_sigma2: np.ndarray    # float32 per edge
+    track_depth: np.ndarray   # float32 per edge
+    preint: Preintegrated
+    C_rw: np.ndarray          # 15 x 15 float32: mpImuPreintegrated->C (the random-walk informations)
+    prior: ImuPrior | None = None
+    rec_init: bool = False
+    truth: ImuState | None = None  # generator only
+
+    def __post_init__(self):
+        self.kind = np.ascontiguousarray(self.kind, np.int8)
+        self.xw = np.ascontiguousarray(self.xw, np.float64).reshape(-1, 3)
+        self.obs = np.ascontiguousarray(self.obs, np.float64).reshape(-1, 3)
+        self.inv_sigma2 = np.ascontiguousarray(self.inv_sigma2, np.float32)
+        self.track_depth = np.ascontiguousarray(self.track_depth, np.float32)
+        self.C_rw = np.ascontiguousarray(self.C_rw, np.float32).reshape(15, 15)
+
+    @property
+    def n(self):
+        return len(self.kind)
+
+    def struct(self, keep):
+        """The C struct; ``keep`` collects the objects whose memory it points into."""
+        st = _abi.OsgPoseInertialProblem()
+        st.mode, st.rec_init = int(self.mode), int(bool(self.rec_init))
+        self.cur.fill(st.cur)
+        self.prev.fill(st.prev)
+        st.n_cams = len(self.cams)
+        for c, k in zip(st.cams, self.cams):
+            c.cam = k.cam
+            for name in ("Rcw", "tcw", "Rcb", "tcb", "tbc"):
+                getattr(c, name)[:] = np.asarray(getattr(k, name), np.float64).ravel().tolist()
+        st.bf = float(self.bf)
+        st.n_edges = self.n
+        st.kind, st.xw, st.obs = _p(self.kind), _p(self.xw), _p(self.obs)
+        st.inv_sigma2, st.track_depth = _p(self.inv_sigma2), _p(self.track_depth)
+        pre = self.preint.struct()
+        keep.append(pre)
+        st.preint = C.addressof(pre)
+        st.C_rw = _p(self.C_rw)
+        if self.prior is not None:
+            pr = self.prior.struct()
+            keep.append(pr)
+            st.prior = C.addressof(pr)
+        return st
+
+
+@dataclass
+class PoseInertialResult:
+    state: ImuState
+    outlier: np.ndarray
+    n_inliers: int            # the reference's return value
+    rounds_run: int
+    iterations: int
+    solve_failed: bool
+    recovered: bool
+    H: np.ndarray             # 15 x 15, as passed to ConstraintPoseImu's constructor
+    edge_chi2: np.ndarray     # as read by each edge's last classification
+
+
+def run_pose_inertial(ctx, probs):
+    nb = len(probs)
+    keep = []
+    ps = (_abi.OsgPoseInertialProblem * max(1, nb))(*[q.struct(keep) for q in probs])
+    rs = (_abi.OsgPoseInertialResult * max(1, nb))()
+    outl = [np.zeros(q.n, np.uint8) for q in probs]
+    chi2 = [np.zeros(q.n, np.float64) for q in probs]
+    for r, o, c in zip(rs, outl, chi2):
+        r.outlier, r.edge_chi2 = _p(o), _p(c)
+    ctx.check(ctx.lib.osg_pose_inertial_optimization_batch(ctx.handle, ps, nb, rs), "PoseInertialOptimization")
+    return [PoseInertialResult(ImuState.of(r.state), o, r.n_inliers, r.rounds_run, r.iterations, bool(r.solve_failed),
+                               bool(r.recovered), np.array(r.H[:]).reshape(15, 15), c)
+            for r, o, c in zip(rs[:nb], outl, chi2)]
+
+
+def constraint_pose_imu(H):
+    """ConstraintPoseImu's constructor (ref:include/G2oTypes.h:825-838) on the H a call returned:
+    ``H = (H + H) / 2`` (the upstream line, which symmetrises nothing), then the eigenvalues of the
+    self-adjoint solver below 1e-12 set to 0.  Eigen's SelfAdjointEigenSolver reads the lower triangle only,
+    and so does ``numpy.linalg.eigh``."""
+    H = np.asarray(H, np.float64).reshape(15, 15)
+    H = (H + H) / 2
+    w, V = np.linalg.eigh(H, UPLO="L")
+    w = np.where(w < 1e-12, 0.0, w)
+    return (V * w) @ V.T
+
+
+# EuRoC-like body-from-camera extrinsic (a 90 degree class rotation and a few centimetres)
+_TBC_R = np.array([[0.0148655429818, -0.999880929698, 0.00414029679422],
+                   [0.999557249008, 0.0149672133247, 0.025715529948],
+                   [-0.0257744366974, 0.00375618835797, 0.999660727178]])
+_TBC_T = np.array([-0.0216401454975, -0.064676986768, 0.00981073058949])
+
+
+def _so3_exp(w):
+    th = np.linalg.norm(w)
+    K = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
+    if th < 1e-9:
+        return np.eye(3) + K
+    return np.eye(3) + np.sin(th) / th * K + (1 - np.cos(th)) / th ** 2 * K @ K
+
+
+def _orthonormal(R):
+    U, _, Vt = np.linalg.svd(R)
+    return U @ Vt
+
+
+def synth_pose_inertial_problem(rng, n_edges=300, mode=_abi.OSG_PIO_LAST_KEYFRAME, cam="pinhole_mono", outlier_frac=0.1,
+                                n_levels=8, rec_init=False, n_behind=0, dt=None, pose_err=(0.3, 0.01),
+                                null_prior=False, prior=None, prev=None):
+    """A consistent two-state visual-inertial problem: a previous state, a constant body-frame rotation rate and
+    acceleration over dt, the current state integrated from them, preintegrated deltas that agree with the pair
+    up to noise, a covariance from EuRoC-like noise densities at 200 Hz, and visual edges of the current frame's
+    true pose with outliers.  ``cam``: "pinhole_mono", "pinhole_stereo" (60 % stereo edges) or "kb8_rig" (half of
+    the edges in the right camera).  ``n_behind`` edges get a point behind the camera.  ``null_prior``
+    (LastFrame): the previous accelerometer bias is held by a 5e-7 random-walk information and a 1e-7 prior
+    alone, so the block that Marginalize inverts has three eigenvalues of 6e-7, below its 1e-6 cut.  ``prior`` / ``prev`` chain a call after another."""
+    last_frame = mode == _abi.OSG_PIO_LAST_FRAME
+    if dt is None:
+        dt = 0.05 if last_frame else 0.25
+    g = np.array([0, 0, -float(np.float32(9.81))])
+    # previous state
+    if prev is None:
+        prev = ImuState(_f32(_orthonormal(small_rotation(rng, 30.0))), _f32(rng.normal(0, 1.0, 3)),
+                        _f32(rng.normal(0, 0.5, 3)), _f32(rng.normal(0, 2e-3, 3)), _f32(rng.normal(0, 2e-2, 3)))
+    # the true motion and its preintegration (bias of the integration = the previous state's, as Tracking leaves it)
+    w, a = rng.normal(0, 0.3, 3), rng.normal(0, 1.0, 3)
+    dR = _so3_exp(w * dt)
+    dV = a * dt
+    dP = 0.5 * a * dt * dt
+    R1 = prev.Rwb
+    R2 = R1 @ dR
+    v2 = prev.v + g * dt + R1 @ dV
+    p2 = prev.twb + prev.v * dt + 0.5 * g * dt * dt + R1 @ dP
+    n_imu = max(1, int(round(dt * 200)))
+    sg, sa = 1.7e-4 * np.sqrt(200.0), 2.0e-3 * np.sqrt(200.0)
+    sgw, saw = 1.9e-5 / np.sqrt(200.0), 3.0e-3 / np.sqrt(200.0)
+    h = dt / n_imu
+    var = np.concatenate([np.full(3, n_imu * (sg * h) ** 2), np.full(3, n_imu * (sa * h) ** 2),
+                          np.full(3, n_imu * (0.5 * sa * h * h) ** 2 * n_imu ** 2 / 3 + 1e-14),
+                          np.full(3, n_imu * sgw ** 2), np.full(3, n_imu * saw ** 2)])
+    M = np.eye(15)
+    M[:9, :9] += 0.05 * rng.normal(size=(9, 9))
+    Cm = (M * var) @ M.T
+    Cm[9:, :9] = 0
+    Cm[:9, 9:] = 0
+    Cm[9:12, 12:] = 0
+    Cm[12:, 9:12] = 0
+    if null_prior:
+        Cm = Cm * 1e6  # a poor IMU: every information at most ~1e4, which keeps the system solvable in double
+    C_rw = Cm.copy()
+    if null_prior:
+        C_rw[12:, 12:] = np.eye(3) * 2e6
+    noise = rng.normal(size=9) * np.sqrt(var[:9])
+    pre = Preintegrated(dR @ _so3_exp(noise[:3]), dV + noise[3:6], dP + noise[6:9],
+                        -dt * np.eye(3) + 0.01 * dt * rng.normal(size=(3, 3)), 0.5 * dt * dt * rng.normal(size=(3, 3)),
+                        (-dt * dR * 0 - dt * np.eye(3) + 0.02 * dt * rng.normal(size=(3, 3))) * (0 if null_prior else 1),
+                        0.1 * dt ** 3 * rng.normal(size=(3, 3)),
+                        (-0.5 * dt * dt * np.eye(3) + 0.01 * dt * dt * rng.normal(size=(3, 3))) * (0 if null_prior else 1),
+                        np.concatenate([prev.ba, prev.bg]), dt, Cm)
+    truth = ImuState(R2, p2, v2, prev.bg, prev.ba)
+    # the predicted current state (what PredictStateIMU leaves in the Frame): off the truth by pose_err
+    Rp = _orthonormal(R2 @ small_rotation(rng, pose_err[0]))
+    cur = ImuState(_f32(Rp), _f32(p2 + rng.normal(0, pose_err[1], 3)), _f32(v2 + rng.normal(0, 0.02, 3)),
+                   _f32(prev.bg), _f32(prev.ba))
+    if last_frame and prior is None:
+        D = np.sqrt(np.array([1e6] * 3 + [1e5] * 3 + [1e4] * 3 + [1e8] * 3 + [1e5] * 3))
+        B = (np.eye(15) + 0.1 * rng.normal(size=(15, 15))) * D[:, None]
+        Hp = B @ B.T
+        if null_prior:
+            Hp *= 1e-6
+            Hp[12:, :] = 0
+            Hp[:, 12:] = 0
+            Hp[12:, 12:] = 1e-7 * np.eye(3)
+        prior = ImuPrior(prev.Rwb @ small_rotation(rng, 0.02), prev.twb + rng.normal(0, 1e-3, 3),
+                         prev.v + rng.normal(0, 1e-3, 3), prev.bg + rng.normal(0, 1e-5, 3),
+                         prev.ba + rng.normal(0, 1e-4, 3), constraint_pose_imu(Hp))
+    # cameras
+    Rcb, tcb = _TBC_R.T, -_TBC_R.T @ _TBC_T
+    rig = cam == "kb8_rig"
+    model = kb8_camera() if rig else pinhole_camera()
+
+    def cam_pose(S, Rcb_, tcb_):
+        Rbw = S.Rwb.T
+        return Rcb_ @ Rbw, Rcb_ @ (-Rbw @ S.twb) + tcb_
+
+    Rcb0, tcb0, tbc0 = _f32(Rcb), _f32(tcb), _f32(_TBC_T)
+    Rcw0, tcw0 = (_f32(a) for a in cam_pose(cur, Rcb0, tcb0))
+    cams = [ImuCamera(model, Rcw0, tcw0, Rcb0, tcb0, tbc0)]
+    if rig:
+        q = np.array(TUMVI_TRL[:4]) / np.linalg.norm(TUMVI_TRL[:4])
+        Rrl, trl = _f32(quat_to_rot(q)), _f32(TUMVI_TRL[4:])
+        Rcb1 = Rrl @ Rcb0
+        tcb1 = Rrl @ tcb0 + trl
+        cams.append(ImuCamera(kb8_camera(), Rrl @ Rcw0, Rrl @ tcw0 + trl, Rcb1, tcb1, -Rcb1.T @ tcb1))
+    # points seen from the true pose
+    n = n_edges
+    true_cams = [cam_pose(truth, k.Rcb, k.tcb) for k in cams]
+    ci = (rng.random(n) < 0.5).astype(int) if rig else np.zeros(n, int)
+    z = rng.uniform(2.0, 20.0, n)
+    if rig:
+        th, ps = rng.uniform(0.05, 1.1, n), rng.uniform(-np.pi, np.pi, n)
+        Xc = np.stack([z * np.sin(th) * np.cos(ps), z * np.sin(th) * np.sin(ps), z * np.cos(th)], 1)
+    else:
+        u, v = rng.uniform(20, EUROC_W - 20, n), rng.uniform(20, EUROC_H - 20, n)
+        Xc = np.stack([(u - EUROC_CX) / EUROC_FX * z, (v - EUROC_CY) / EUROC_FY * z, z], 1)
+    Xw = np.zeros((n, 3))
+    for c, (Rc, tc) in enumerate(true_cams):
+        m = ci == c
+        Xw[m] = (Xc[m] - tc) @ Rc
+    Xw = _f32(Xw)
+    octv = rng.choice(n_levels, n, p=np.array([1.2 ** -i for i in range(n_levels)]) / sum(1.2 ** -i for i in range(n_levels)))
+    sig = 1.2 ** octv
+    obs = np.zeros((n, 3))
+    depth = np.zeros(n)
+    for c, (Rc, tc) in enumerate(true_cams):
+        m = ci == c
+        Xm = Xw[m] @ Rc.T + tc
+        obs[m, :2] = _project(cams[c].cam, Xm)
+        depth[m] = Xm[:, 2]
+    obs[:, 0] += rng.normal(0, 1, n) * sig
+    obs[:, 1] += rng.normal(0, 1, n) * sig
+    out = rng.random(n) < outlier_frac
+    obs[out, 0] += rng.uniform(8, 40, out.sum()) * rng.choice([-1, 1], out.sum())
+    obs[out, 1] += rng.uniform(8, 40, out.sum()) * rng.choice([-1, 1], out.sum())
+    stereo = (rng.random(n) < 0.6) if cam == "pinhole_stereo" else np.zeros(n, bool)
+    bf = float(np.float32(EUROC_BF)) if not rig else 0.0
+    obs[:, 2] = np.where(stereo, obs[:, 0] - bf / np.maximum(depth, 0.1) + rng.normal(0, 0.5, n), 0.0)
+    kind = np.where(stereo, _abi.EDGE_STEREO, np.where(ci == 1, _abi.EDGE_BODY, _abi.EDGE_MONO)).astype(np.int8)
+    for i in range(min(n_behind, n)):  # a wrong match to a point behind the camera, observed where it would mirror
+        Rc, tc = true_cams[ci[i]]
+        Xb = np.array([rng.normal(0, 0.5), rng.normal(0, 0.5), -rng.uniform(2, 5)])
+        Xw[i] = _f32((Xb - tc) @ Rc)
+        kind[i] = _abi.EDGE_BODY if ci[i] == 1 else _abi.EDGE_MONO
+        obs[i, 2] = 0.0
+    return PoseInertialProblem(mode, cur, prev, cams, bf, kind, Xw, _f32(obs), inv_level_sigma2(n_levels)[octv],
+                               np.maximum(depth, 0.0).astype(np.float32), pre, C_rw, prior, rec_init, truth)

@@ -1,0 +1,173 @@
+"""CPU: the restatement of PoseInertialOptimization (tests/pyref_poseinertial.py) on hand-derived cases, the
+guards of every fixture (tests/poseinertial_fixtures.py against profiles/poseinertial_margins.json), and the host
+side of the entry points under AddressSanitizer and UBSan (tests/host/poseinertial_host.cpp)."""
+import copy
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from orb_slam3_comments_ghr_amd import optimizer as O
+from tests import poseinertial_fixtures as FX
+from tests import pyref_poseinertial as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def consistent(mode, n=0, seed=5):
+    """A problem whose preintegration agrees exactly (up to the float fields) with the two states."""
+    P = O.synth_pose_inertial_problem(np.random.default_rng(seed), n, mode, "pinhole_mono", outlier_frac=0.0)
+    t = P.truth
+    P.cur = O.ImuState(t.Rwb, t.twb, t.v, P.prev.bg, P.prev.ba)
+    R1 = P.prev.Rwb
+    g = np.array([0, 0, -float(np.float32(9.81))])
+    dt = float(P.preint.dT)
+    P.preint.dR = (R1.T @ t.Rwb).astype(np.float32)
+    P.preint.dV = (R1.T @ (t.v - P.prev.v - g * dt)).astype(np.float32)
+    P.preint.dP = (R1.T @ (t.twb - P.prev.twb - P.prev.v * dt - g * dt * dt / 2)).astype(np.float32)
+    if P.prior is not None:
+        P.prior = O.ImuPrior(P.prev.Rwb, P.prev.twb, P.prev.v, P.prev.bg, P.prev.ba, P.prior.H)
+    return P
+
+
+@pytest.mark.parametrize("mode", [FX.LKF, FX.LF])
+def test_no_visual_edge_and_a_consistent_preintegration_stay_at_the_truth(mode):
+    P = consistent(mode)
+    r = R.pose_inertial_optimization(P)
+    # the float32 deltas carry 6e-8 relative error; the state answers with at most a few of those
+    assert R.rot_angle(r.Rwb, P.truth.Rwb) < 1e-6
+    assert np.max(np.abs(r.twb - P.truth.twb)) < 1e-6
+    assert np.max(np.abs(r.v - P.truth.v)) < 1e-5
+    assert np.max(np.abs(r.bg - P.prev.bg)) < 1e-6 and np.max(np.abs(r.ba - P.prev.ba)) < 1e-4
+    assert r.n_inliers == 0 and r.rounds_run == 1 and r.iterations == 10 and not r.solve_failed
+
+
+@pytest.mark.parametrize("mode,n,rounds", [(FX.LKF, 6, 1), (FX.LKF, 7, 4), (FX.LF, 5, 1), (FX.LF, 6, 4)])
+def test_the_edge_count_break_counts_the_inertial_edges(mode, n, rounds):
+    r = R.pose_inertial_optimization(O.synth_pose_inertial_problem(np.random.default_rng(n), n, mode, "pinhole_mono"))
+    assert r.rounds_run == rounds and r.iterations == 10 * rounds
+
+
+def test_the_recovery_pass_runs_at_29_inliers_and_not_at_30():
+    r29, r30 = FX.reference("lkf_in29"), FX.reference("lkf_in30")
+    assert r29.nInliers == 29 and r29.recovered
+    assert r30.nInliers == 30 and not r30.recovered
+    q29, q30 = FX.reference("lf_in29"), FX.reference("lf_in30")
+    assert q29.nInliers == 29 and q29.recovered and q30.nInliers == 30 and not q30.recovered
+
+
+def test_rec_init_suppresses_the_recovery_pass():
+    r, s = FX.reference("lkf_in29"), FX.reference("lkf_in29_recinit")
+    assert r.recovered and not s.recovered and s.nInliers == 29
+    assert s.n_inliers == 34 - int(s.outlier.sum())
+    # the recovery pass clears flags and recounts
+    assert r.outlier.sum() <= s.outlier.sum()
+    np.testing.assert_array_equal(r.Rwb, s.Rwb)
+
+
+def test_marginalize_is_the_schur_complement_on_a_well_conditioned_matrix():
+    rng = np.random.default_rng(1)
+    B = rng.normal(size=(30, 30))
+    H = B @ B.T + 30 * np.eye(30)
+    got, sv = R.Marginalize(H, 0, 14)
+    want = H[15:, 15:] - H[15:, :15] @ np.linalg.inv(H[:15, :15]) @ H[:15, 15:]
+    np.testing.assert_allclose(got[15:, 15:], want, rtol=0, atol=1e-11 * np.abs(want).max())
+    assert not got[:15].any() and not got[:, :15].any() and sv.min() > 1e-6
+
+
+def test_marginalize_drops_a_planted_null_direction():
+    rng = np.random.default_rng(2)
+    B = rng.normal(size=(30, 30))
+    H = B @ B.T + 30 * np.eye(30)
+    n = np.zeros(30)
+    n[:15] = rng.normal(size=15)
+    n /= np.linalg.norm(n)
+    Pn = np.eye(30) - np.outer(n, n)
+    H0 = Pn @ H @ Pn + 1e-8 * np.outer(n, n)   # eigenvalue 1e-8 along n, inside the marginalised block
+    got, sv = R.Marginalize(H0, 0, 14)
+    assert sv.min() < 1e-6
+    Q = np.linalg.svd(np.eye(15) - np.outer(n[:15], n[:15]))[0][:, :14]   # the block without n
+    A = Q.T @ H0[:15, :15] @ Q
+    want = H0[15:, 15:] - H0[15:, :15] @ Q @ np.linalg.inv(A) @ Q.T @ H0[:15, 15:]
+    np.testing.assert_allclose(got[15:, 15:], want, rtol=0, atol=1e-10 * np.abs(want).max())
+
+
+def test_the_constructor_keeps_the_upstream_symmetrisation_quirk():
+    rng = np.random.default_rng(3)
+    B = rng.normal(size=(15, 15))
+    H = B @ B.T + np.eye(15)
+    Hu = H.copy()
+    Hu[0, 5] += 0.5   # an asymmetric input: (H + H) / 2 leaves it, the eigen-solver reads the lower triangle
+    for f in (O.constraint_pose_imu, lambda M: R.ConstraintPoseImuH(M)[0]):
+        np.testing.assert_allclose(f(Hu), H, rtol=0, atol=1e-12 * np.abs(H).max())
+        Hl = H.copy()
+        Hl[5, 0] += 0.5
+        assert np.abs(f(Hl) - H).max() > 0.1
+    small = np.diag([1.0] * 14 + [1e-13])
+    assert O.constraint_pose_imu(small)[14, 14] == 0.0
+
+
+def test_a_round_one_outlier_is_readmitted_and_a_point_behind_the_camera_is_out():
+    for k in FX.READMIT:
+        assert FX.reference(k).readmitted > 0
+    for k in FX.BEHIND:
+        r = FX.reference(k)
+        assert min(r.depths) < 0 and r.outlier[:2].all()
+    r = FX.reference("lf_null")
+    assert r.marg_sv.min() < 1e-6 < r.marg_sv.max()
+
+
+def test_margins_file_covers_every_fixture_and_admits_it():
+    m = FX.margins()
+    assert set(m["fixtures"]) == set(FX.FIXTURES) and set(m["groups"]) == set(FX.GROUPS)
+    for k, s in m["fixtures"].items():
+        assert s["same"] and s["valid"], k
+        mx = m["groups"][FX.FIXTURES[k].group]["max"]
+        for q in FX.THRESHOLD_KINDS:
+            assert s["margin"][q] > 10.0 * mx[q], (k, q)
+    for g, v in m["groups"].items():
+        for q in R.QUANTITIES:
+            assert v["tol"][q] == 10.0 * v["max"][q]
+
+
+@pytest.mark.parametrize("name", ["lkf_n7", "lf_n6", "lkf_in29", "lf_null"])
+def test_recorded_study_is_reproduced(name):
+    s, m = FX.study(name), FX.margins()["fixtures"][name]
+    assert s["same"]
+    for q, v in s["margin"].items():
+        assert v == pytest.approx(m["margin"][q], rel=1e-6)
+
+
+# ----------------------------------------------------------------------------------- host code
+def host_program(tmp_path, flags):
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is part of the image"
+    exe = str(tmp_path / ("poseinertial_host" + str(len(flags))))
+    r = subprocess.run([gxx, "-std=c++17", "-Wall", "-Werror", *flags,
+                        "-I" + os.path.join(ROOT, "orb_slam3_comments_ghr_amd", "csrc"),
+                        os.path.join(ROOT, "tests", "host", "poseinertial_host.cpp"), "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return exe
+
+
+def test_host_side_under_sanitizers(tmp_path):
+    exe = host_program(tmp_path, ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+    r = subprocess.run([exe, "check"], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-2000:] + r.stderr[-3000:]
+
+
+def test_host_informations_match_the_restatement(tmp_path):
+    exe = host_program(tmp_path, ["-O1"])
+    P = FX.build("lf_rig")
+    C = np.ascontiguousarray(P.preint.C, np.float32)
+    path = str(tmp_path / "C.bin")
+    np.concatenate([C.ravel(), P.C_rw.ravel()]).astype(np.float32).tofile(path)
+    out = subprocess.run([exe, "info", path], capture_output=True, text=True, check=True).stdout.split()
+    got = np.array([float(x) for x in out])
+    info9, _ = R.inertial_information(C)
+    Crw = P.C_rw.astype(np.float64)
+    want = np.concatenate([info9.ravel(), np.linalg.inv(Crw[9:12, 9:12]).ravel(), np.linalg.inv(Crw[12:, 12:]).ravel()])
+    # C's leading block has a condition number near 1e7: two double-precision inverses agree to about 1e-9
+    np.testing.assert_allclose(got, want, rtol=0, atol=1e-8 * np.abs(want).max())
