@@ -46,7 +46,7 @@ $(OBJDIR)/match.o: $(CSRC)/match.hip $(HDRS) $(CSRC)/match_common.h $(CSRC)/frus
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
 $(OBJDIR)/pose.o: $(CSRC)/pose.hip $(HDRS) $(CSRC)/ba_common.h $(CSRC)/exact_math.h $(CSRC)/glibc_math.h $(CSRC)/match_common.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
-$(OBJDIR)/poseinertial.o: $(CSRC)/poseinertial.hip $(HDRS) $(CSRC)/ba_common.h $(CSRC)/poseinertial_common.h $(CSRC)/exact_math.h $(RANSAC_HDRS) | $(OBJDIR)
+$(OBJDIR)/poseinertial.o: $(CSRC)/poseinertial.hip $(HDRS) $(CSRC)/ba_common.h $(CSRC)/poseinertial_common.h $(CSRC)/so3_common.h $(CSRC)/exact_math.h $(RANSAC_HDRS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
 $(OBJDIR)/sim3opt.o: $(CSRC)/sim3opt.hip $(HDRS) $(CSRC)/ba_common.h $(CSRC)/sim3_common.h $(CSRC)/exact_math.h $(CSRC)/glibc_math.h $(CSRC)/batch_io.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
@@ -56,7 +56,7 @@ $(OBJDIR)/mlpnp.o: $(CSRC)/mlpnp.hip $(HDRS) $(CSRC)/mlpnp_select.h $(RANSAC_HDR
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
 $(OBJDIR)/twoview.o: $(CSRC)/twoview.hip $(HDRS) $(CSRC)/twoview_select.h $(RANSAC_HDRS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
-$(OBJDIR)/essgraph.o: $(CSRC)/essgraph.hip $(HDRS) $(CSRC)/sim3_common.h $(CSRC)/exact_math.h | $(OBJDIR)
+$(OBJDIR)/essgraph.o: $(CSRC)/essgraph.hip $(HDRS) $(CSRC)/sim3_common.h $(CSRC)/exact_math.h $(CSRC)/essgraph4_common.h $(CSRC)/so3_common.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
 $(OBJDIR)/ba.o: $(CSRC)/ba.hip $(HDRS) $(CSRC)/ba_common.h $(CSRC)/exact_math.h $(CSRC)/glibc_math.h $(CSRC)/match_common.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@

@@ -1,7 +1,8 @@
 // Optimizer_osg.cc — drop-in bodies for Optimizer::PoseOptimization, Optimizer::PoseInertialOptimizationLastKeyFrame /
 // LastFrame, the g2o part of
 // Optimizer::LocalBundleAdjustment (both overloads), Optimizer::BundleAdjustment (global BA) and
-// Optimizer::OptimizeSim3 and Optimizer::OptimizeEssentialGraph (the loop-closure overload) on the MI355X path (ORB-SLAM3 tree built with -DORB_SLAM3_OSG;
+// Optimizer::OptimizeSim3, Optimizer::OptimizeEssentialGraph (the loop-closure overload) and
+// Optimizer::OptimizeEssentialGraph4DoF on the MI355X path (ORB-SLAM3 tree built with -DORB_SLAM3_OSG;
 // see INTEGRATION.md).  Signatures: ref:include/Optimizer.h:54-90.
 #include "Optimizer.h"
 #include "osg_hooks_orbslam3.h"
@@ -82,6 +83,16 @@ void Optimizer::OptimizeEssentialGraph(Map *pMap, KeyFrame *pLoopKF, KeyFrame *p
    // taken inside, after the optimisation and before the write-back
     osg_orbslam3::optimize_essential_graph<OsgHooks>(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3,
                                                      LoopConnections, bFixScale);
+}
+
+void Optimizer::OptimizeEssentialGraph4DoF(Map *pMap, KeyFrame *pLoopKF, KeyFrame *pCurKF,
+                                           const LoopClosing::KeyFrameAndPose &NonCorrectedSim3,
+                                           const LoopClosing::KeyFrameAndPose &CorrectedSim3,
+                                           const map<KeyFrame *, set<KeyFrame *>> &LoopConnections)
+{  // ref:src/Optimizer.cc:4870-5198 (LoopClosing::CorrectLoop's pose graph in an inertial map); the lock of :5150
+   // is taken inside, after the optimisation and before the write-back
+    osg_orbslam3::optimize_essential_graph_4dof<OsgHooks>(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3,
+                                                          LoopConnections);
 }
 
 }  // namespace ORB_SLAM3

@@ -306,6 +306,28 @@ struct OsgHooks {
         Sophus::SE3f Tiw(r.cast<float>(), tr.cast<float>() / s);
         pKF->SetPose(Tiw);
     }
+    // OptimizeEssentialGraph4DoF, ref:src/G2oTypes.cc:29-75, ref:src/Optimizer.cc:5164-5168
+    static void kf_imu_cam_pose(KeyFrame *pKF, double row[36])
+    {
+        using RowM = Eigen::Matrix<double, 3, 3, Eigen::RowMajor>;
+        Eigen::Map<RowM>(row) = pKF->GetImuRotation().cast<double>();
+        Eigen::Map<Eigen::Vector3d>(row + 9) = pKF->GetImuPosition().cast<double>();
+        Eigen::Map<RowM>(row + 12) = pKF->GetRotation().cast<double>();
+        Eigen::Map<Eigen::Vector3d>(row + 21) = pKF->GetTranslation().cast<double>();
+        Eigen::Map<RowM>(row + 24) = pKF->mImuCalib.mTcb.rotationMatrix().cast<double>();
+        Eigen::Map<Eigen::Vector3d>(row + 33) = pKF->mImuCalib.mTcb.translation().cast<double>();
+    }
+    static void rot_to_quat(const double R[9], double q[4])
+    {
+        const Eigen::Matrix3d M = Eigen::Map<const Eigen::Matrix<double, 3, 3, Eigen::RowMajor>>(R);
+        const Eigen::Quaterniond r(M);
+        q[0] = r.x(); q[1] = r.y(); q[2] = r.z(); q[3] = r.w();
+    }
+    static void kf_set_pose_se3d(KeyFrame *pKF, const double q[4], const double t[3])
+    {
+        const Sophus::SE3d Tiw(Eigen::Quaterniond(q[3], q[0], q[1], q[2]), Eigen::Vector3d(t[0], t[1], t[2]));
+        pKF->SetPose(Tiw.cast<float>());
+    }
     static void mp_world_pos(MapPoint *pMP, float x[3])
     {
         const Eigen::Vector3f p = pMP->GetWorldPos();

@@ -2549,6 +2549,257 @@ int optimize_essential_graph(MapT *pMap, KeyFrameT *pLoopKF, KeyFrameT *pCurKF, 
     return rc;
 }
 
+// ----------------------------------------------------------------------- OptimizeEssentialGraph4DoF
+// Optimizer::OptimizeEssentialGraph4DoF (ref:src/Optimizer.cc:4870-5198), what LoopClosing::CorrectLoop calls in
+// place of OptimizeEssentialGraph once the map is inertial and its IMU initialised (ref:src/LoopClosing.cc:1644-1653).
+// Hooks (sim3_get, kf_pose_sim3, mp_world_pos, mp_set_world_pos as above):
+//   static void H::kf_imu_cam_pose(KeyFrame*, double row[36])   the fields of ImuCamPose(pKF) (ref:src/G2oTypes.cc:29-75),
+//                each cast from the KeyFrame's floats: Rwb = GetImuRotation(), twb = GetImuPosition(), Rcw = GetRotation(),
+//                tcw = GetTranslation(), Rcb / tcb of mImuCalib.mTcb; 3 x 3 matrices row-major, the ABI's vertex row
+//   static void H::rot_to_quat(const double R[9], double q[4])   Eigen::Quaterniond(Matrix3d) as (x y z w): the rotation
+//                of CorrectedSiw = g2o::Sim3(Ri, ti, 1.) (:5164)
+//   static void H::kf_set_pose_se3d(KeyFrame*, const double q[4], const double t[3])
+//                SetPose(Sophus::SE3d(Quaterniond(q), Vector3d(t)).cast<float>()) (:5167-5168)
+//
+// EssentialGraph4DoFGather is the graph build of :4903-5143 as plain host code, literally.  A vertex per non-bad
+// KeyFrame of GetAllKeyFrames(): for one in CorrectedSim3 the 3-argument ImuCamPose constructor's arithmetic on the
+// inverse of its corrected Sim3 (ref:src/G2oTypes.cc:132-157), else the KeyFrame's own ImuCamPose; pLoopKF fixed.
+// Then the edges in the reference's insertion order: the LoopConnections (weight >= minFeat unless the pair is
+// (pCurKF, pLoopKF); these fill sInsertedEdges), and per KeyFrame no spanning-tree edge (pParentKF is a null
+// constant), the mPrevKF edge, the loop edges to smaller ids and the covisibility >= minFeat edges (not mPrevKF,
+// not mNextKF, not a child, not a loop edge, not bad, smaller id, not in sInsertedEdges).  A measurement is
+// Siw * Swj of the non-corrected Sim3s in double with g2o::Sim3's own operators; its rotation matrix and its
+// translation are taken and its scale is dropped, as Edge4DoF's Tij does.  The information is the reference's
+// matLambda: the identity with (0, 0) and (1, 1) set to 1e3 and (0, 0) set a second time, so (2, 2) stays 1.
+//
+// Bad KeyFrames are treated as in EssentialGraphGather: an edge whose KeyFrame has no vertex is DROPPED and counted
+// in n_dropped, and the write-back skips a KeyFrame without a vertex, where :5160-5162 would dereference null.
+namespace osgs3 {
+// Eigen's QuaternionBase::toRotationMatrix, operation for operation (row-major; the quaternion is not normalised)
+inline void q_to_rot(const double *q, double *R)
+{
+    const double tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2];
+    const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
+    const double txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
+    const double tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
+    R[0] = 1 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
+    R[3] = txy + twz; R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
+    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1 - (txx + tyy);
+}
+}  // namespace osgs3
+
+template <class H, class MapT, class KeyFrameT, class MapPointT>
+struct EssentialGraph4DoFGather {
+    static constexpr int minFeat = 100;
+    std::vector<KeyFrameT *> vpKFs, vertex_kf;
+    std::vector<MapPointT *> vpMPs;
+    std::vector<int32_t> index_of_id;
+    std::vector<double> pose, sim3_before, e_meas, out;  // sim3_before: vScw of every vertex, for the MapPoints
+    std::vector<uint8_t> fixed;
+    std::vector<int32_t> e_v0, e_v1;
+    int n_dropped = 0;
+    osg_essgraph4_problem p{};
+
+    template <class Sim3T>
+    static osgs3::Sim3 from_g2o(const Sim3T &g)
+    {
+        osgs3::Sim3 S;
+        H::sim3_get(g, S.q, S.t, S.s);
+        return S;
+    }
+    // Edge4DoF(Tij) with Tij's rotation block Sij.rotation().toRotationMatrix() and translation Sij.translation()
+    void add_edge(unsigned long nIDi, unsigned long nIDj, const osgs3::Sim3 &Sij)
+    {
+        const int32_t a = nIDi < index_of_id.size() ? index_of_id[nIDi] : -1;
+        const int32_t b = nIDj < index_of_id.size() ? index_of_id[nIDj] : -1;
+        if (a < 0 || b < 0 || a == b) {
+            n_dropped++;
+            return;
+        }
+        e_v0.push_back(a);
+        e_v1.push_back(b);
+        double m[12];
+        osgs3::q_to_rot(Sij.q, m);
+        for (int i = 0; i < 3; i++) m[9 + i] = Sij.t[i];
+        e_meas.insert(e_meas.end(), m, m + 12);
+    }
+    template <class KFAndPoseT, class LoopConnT>
+    void assign(MapT *pMap, KeyFrameT *pLoopKF, KeyFrameT *pCurKF, const KFAndPoseT &NonCorrectedSim3,
+                const KFAndPoseT &CorrectedSim3, const LoopConnT &LoopConnections)
+    {
+        p = osg_essgraph4_problem{};
+        for (auto *v : {&pose, &sim3_before, &e_meas, &out}) v->clear();
+        for (auto *v : {&e_v0, &e_v1}) v->clear();
+        fixed.clear();
+        vertex_kf.clear();
+        n_dropped = 0;
+        vpKFs = pMap->GetAllKeyFrames();
+        vpMPs = pMap->GetAllMapPoints();
+        const unsigned int nMaxKFid = pMap->GetMaxKFid();
+        osgs3::Sim3 ident;
+        ident.q[0] = ident.q[1] = ident.q[2] = 0; ident.q[3] = 1;
+        ident.t[0] = ident.t[1] = ident.t[2] = 0; ident.s = 1;
+        std::vector<osgs3::Sim3> vScw(nMaxKFid + 1, ident);  // g2o::Sim3(): the identity
+        index_of_id.assign(nMaxKFid + 1, -1);
+        for (size_t i = 0, iend = vpKFs.size(); i < iend; i++) {  // :4903-4944
+            KeyFrameT *pKF = vpKFs[i];
+            if (pKF->isBad()) continue;
+            const unsigned long nIDi = pKF->mnId;
+            double row[OSG_EG4_POSE_IN];
+            H::kf_imu_cam_pose(pKF, row);
+            auto it = CorrectedSim3.find(pKF);
+            if (it != CorrectedSim3.end()) {
+                vScw[nIDi] = from_g2o(it->second);
+                const osgs3::Sim3 Swc = osgs3::sim3_inverse(vScw[nIDi]);
+                double Rwc[9];
+                osgs3::q_to_rot(Swc.q, Rwc);
+                const double *twc = Swc.t, *Rcb = row + 24, *tcb = row + 33;
+                double *Rwb = row, *twb = row + 9, *Rcw = row + 12, *tcw = row + 21;
+                for (int r = 0; r < 3; r++) {  // ImuCamPose(_Rwc, _twc, pKF)
+                    twb[r] = (Rwc[3 * r] * tcb[0] + Rwc[3 * r + 1] * tcb[1] + Rwc[3 * r + 2] * tcb[2]) + twc[r];
+                    for (int c = 0; c < 3; c++) {
+                        Rwb[3 * r + c] = Rwc[3 * r] * Rcb[c] + Rwc[3 * r + 1] * Rcb[3 + c] + Rwc[3 * r + 2] * Rcb[6 + c];
+                        Rcw[3 * r + c] = Rwc[3 * c + r];
+                    }
+                }
+                for (int r = 0; r < 3; r++) tcw[r] = -(Rcw[3 * r] * twc[0] + Rcw[3 * r + 1] * twc[1] + Rcw[3 * r + 2] * twc[2]);
+            } else {
+                H::kf_pose_sim3(pKF, vScw[nIDi].q, vScw[nIDi].t);
+                vScw[nIDi].s = 1.0;
+            }
+            index_of_id[nIDi] = (int32_t)vertex_kf.size();
+            vertex_kf.push_back(pKF);
+            fixed.push_back(pKF == pLoopKF ? 1 : 0);
+            pose.insert(pose.end(), row, row + OSG_EG4_POSE_IN);
+            const osgs3::Sim3 &S = vScw[nIDi];
+            const double r8[8] = {S.q[0], S.q[1], S.q[2], S.q[3], S.t[0], S.t[1], S.t[2], S.s};
+            sim3_before.insert(sim3_before.end(), r8, r8 + 8);
+        }
+        std::set<std::pair<unsigned long, unsigned long>> sInsertedEdges;
+        for (auto mit = LoopConnections.begin(), mend = LoopConnections.end(); mit != mend; mit++) {  // :4957-4993
+            KeyFrameT *pKF = mit->first;
+            const unsigned long nIDi = pKF->mnId;
+            const auto &spConnections = mit->second;
+            const osgs3::Sim3 Siw = vScw[nIDi];
+            for (auto sit = spConnections.begin(), send = spConnections.end(); sit != send; sit++) {
+                const unsigned long nIDj = (*sit)->mnId;
+                if ((nIDi != pCurKF->mnId || nIDj != pLoopKF->mnId) && pKF->GetWeight(*sit) < minFeat) continue;
+                add_edge(nIDi, nIDj, osgs3::sim3_mul(Siw, osgs3::sim3_inverse(vScw[nIDj])));
+                sInsertedEdges.insert(std::make_pair(std::min(nIDi, nIDj), std::max(nIDi, nIDj)));
+            }
+        }
+        auto non_corrected = [&](KeyFrameT *k) {  // the NonCorrectedSim3 entry, else vScw
+            auto it = NonCorrectedSim3.find(k);
+            return it != NonCorrectedSim3.end() ? from_g2o(it->second) : vScw[k->mnId];
+        };
+        for (size_t i = 0, iend = vpKFs.size(); i < iend; i++) {  // :4997-5143
+            KeyFrameT *pKF = vpKFs[i];
+            const unsigned long nIDi = pKF->mnId;
+            const osgs3::Sim3 Siw = non_corrected(pKF);
+            KeyFrameT *prevKF = pKF->mPrevKF;
+            if (prevKF) add_edge(nIDi, prevKF->mnId, osgs3::sim3_mul(Siw, osgs3::sim3_inverse(non_corrected(prevKF))));
+            const std::set<KeyFrameT *> sLoopEdges = pKF->GetLoopEdges();
+            for (auto sit = sLoopEdges.begin(), send = sLoopEdges.end(); sit != send; sit++) {
+                KeyFrameT *pLKF = *sit;
+                if (pLKF->mnId < pKF->mnId)
+                    add_edge(nIDi, pLKF->mnId, osgs3::sim3_mul(Siw, osgs3::sim3_inverse(non_corrected(pLKF))));
+            }
+            const std::vector<KeyFrameT *> vpConnectedKFs = pKF->GetCovisiblesByWeight(minFeat);
+            for (auto vit = vpConnectedKFs.begin(); vit != vpConnectedKFs.end(); vit++) {
+                KeyFrameT *pKFn = *vit;
+                if (pKFn && pKFn != prevKF && pKFn != pKF->mNextKF && !pKF->hasChild(pKFn) && !sLoopEdges.count(pKFn)) {
+                    if (!pKFn->isBad() && pKFn->mnId < pKF->mnId) {
+                        if (sInsertedEdges.count(std::make_pair(std::min<unsigned long>(pKF->mnId, pKFn->mnId),
+                                                                std::max<unsigned long>(pKF->mnId, pKFn->mnId))))
+                            continue;
+                        add_edge(nIDi, pKFn->mnId, osgs3::sim3_mul(Siw, osgs3::sim3_inverse(non_corrected(pKFn))));
+                    }
+                }
+            }
+        }
+        out.assign(OSG_EG4_POSE_OUT * vertex_kf.size(), 0.0);
+        p.n_vertices = (int32_t)vertex_kf.size();
+        p.pose = pose.data();
+        p.fixed = fixed.data();
+        p.n_edges = (int32_t)e_v0.size();
+        p.e_v0 = e_v0.data();
+        p.e_v1 = e_v1.data();
+        p.e_meas = e_meas.data();
+        double matLambda[6] = {1, 1, 1, 1, 1, 1};  // :4949-4952
+        matLambda[0] = 1e3;
+        matLambda[1] = 1e3;
+        matLambda[0] = 1e3;
+        for (int i = 0; i < 6; i++) p.info_diag[i] = matLambda[i];
+        p.max_iterations = 0;  // optimize(20), :5148
+        p.lambda_init = 0.0;   // no setUserLambdaInit: g2o's own
+    }
+};
+
+// The MapPoint side of the write-back (:5173-5193) as arrays: the positions of the non-bad MapPoints and the vertex
+// of each one's GetReferenceKeyFrame() (this overload never reads mnCorrectedReference), -1 when that KeyFrame has
+// no vertex.
+template <class H, class MapT, class KeyFrameT, class MapPointT>
+void essential_graph_4dof_points(const EssentialGraph4DoFGather<H, MapT, KeyFrameT, MapPointT> &g,
+                                 std::vector<MapPointT *> &mps, std::vector<float> &Xw, std::vector<int32_t> &ref)
+{
+    mps.clear();
+    Xw.clear();
+    ref.clear();
+    for (size_t i = 0, iend = g.vpMPs.size(); i < iend; i++) {
+        MapPointT *pMP = g.vpMPs[i];
+        if (pMP->isBad()) continue;
+        const unsigned long nIDr = pMP->GetReferenceKeyFrame()->mnId;
+        float x[3];
+        H::mp_world_pos(pMP, x);
+        mps.push_back(pMP);
+        Xw.insert(Xw.end(), x, x + 3);
+        ref.push_back(nIDr < g.index_of_id.size() ? g.index_of_id[nIDr] : -1);
+    }
+}
+
+// The whole call.  On an ABI error nothing of the map is touched.  Returns the ABI's code.
+template <class H, class MapT, class KeyFrameT, class KFAndPoseT, class LoopConnT>
+int optimize_essential_graph_4dof(MapT *pMap, KeyFrameT *pLoopKF, KeyFrameT *pCurKF, const KFAndPoseT &NonCorrectedSim3,
+                                  const KFAndPoseT &CorrectedSim3, const LoopConnT &LoopConnections)
+{
+    using MapPointT = typename std::remove_pointer<typename std::decay<decltype(pMap->GetAllMapPoints()[0])>::type>::type;
+    osg_ctx *ctx = thread_ctx();
+    EssentialGraph4DoFGather<H, MapT, KeyFrameT, MapPointT> g;
+    g.assign(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections);
+    osg_essgraph4_result r{};
+    r.pose = g.out.data();
+    int rc = call(ctx, "osg_optimize_essential_graph_4dof", [&] { return osg_optimize_essential_graph_4dof(ctx, &g.p, &r); });
+    if (rc < 0) return rc;
+    std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);  // :5150
+    // :5154-5169: SetPose from Rcw[0], tcw[0] through a unit-scale Sim3, whose rows correct the MapPoints below
+    std::vector<double> sim3_after(8 * g.vertex_kf.size());
+    std::vector<MapPointT *> mps;
+    std::vector<float> Xw, Xw_out;
+    std::vector<int32_t> ref;
+    essential_graph_4dof_points<H>(g, mps, Xw, ref);
+    Xw_out.resize(Xw.size());
+    for (size_t v = 0; v < g.vertex_kf.size(); v++) {
+        const double *o = g.out.data() + OSG_EG4_POSE_OUT * v;
+        double *a = sim3_after.data() + 8 * v;
+        H::rot_to_quat(o, a);
+        a[4] = o[9]; a[5] = o[10]; a[6] = o[11];
+        a[7] = 1.0;
+    }
+    rc = call(ctx, "osg_essgraph_correct_points", [&] {
+        return osg_essgraph_correct_points(ctx, (int32_t)mps.size(), Xw.data(), ref.data(), g.p.n_vertices,
+                                           g.sim3_before.data(), sim3_after.data(), Xw_out.data());
+    });
+    if (rc < 0) return rc;
+    for (size_t v = 0; v < g.vertex_kf.size(); v++)
+        H::kf_set_pose_se3d(g.vertex_kf[v], sim3_after.data() + 8 * v, sim3_after.data() + 8 * v + 4);
+    for (size_t i = 0; i < mps.size(); i++) {  // :5173-5196
+        H::mp_set_world_pos(mps[i], Xw_out.data() + 3 * i);
+        mps[i]->UpdateNormalAndDepth();
+    }
+    pMap->IncreaseChangeIndex();
+    return rc;
+}
+
 // ------------------------------------------------------------------------------- Sim3Solver
 // Sim3Solver (ref:include/Sim3Solver.h, ref:src/Sim3Solver.cc) with the reference's public surface.  Hooks
 // (beside cam_point, index_in_keyframe and camera above):

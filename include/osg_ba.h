@@ -363,7 +363,46 @@ int osg_optimize_essential_graph(struct osg_ctx *ctx, const osg_essgraph_problem
 int osg_essgraph_correct_points(struct osg_ctx *ctx, int32_t n_points, const float *Xw, const int32_t *ref_vertex,
                                 int32_t n_vertices, const double *sim3_before, const double *sim3_after,
                                 float *Xw_out);
-/* Diagnostics: per-phase device time of osg_optimize_essential_graph.  enable = 1: every later call
+/* ---- OptimizeEssentialGraph4DoF --------------------------------------------------------------
+ * The g2o part of Optimizer::OptimizeEssentialGraph4DoF (ref:src/Optimizer.cc:4870-5198), the pose graph
+ * LoopClosing::CorrectLoop optimises in an inertial map: VertexPose4DoF vertices (an ImuCamPose updated in
+ * yaw and translation by UpdateW) and Edge4DoF edges (6 rows, diagonal information, no robust kernel,
+ * numeric Jacobians), Levenberg-Marquardt with g2o's own lambda, optimize(20).
+ * A vertex is 36 doubles, the ImuCamPose as its constructor leaves it, 3 x 3 matrices row-major:
+ *   Rwb[9] twb[3] Rcw[9] tcw[3] Rcb[9] tcb[3].
+ * Rcw / tcw are read as passed until the vertex's first update re-derives them from Rwb / twb. */
+#define OSG_EG4_POSE_IN 36
+#define OSG_EG4_POSE_OUT 24
+typedef struct osg_essgraph4_problem {
+    int32_t n_vertices;       /* non-bad KeyFrames, caller's order; at most 65 535 */
+    const double *pose;       /* OSG_EG4_POSE_IN per vertex */
+    const uint8_t *fixed;     /* per vertex */
+    int32_t n_edges;
+    const int32_t *e_v0, *e_v1; /* vertex(0) = i, vertex(1) = j; i != j */
+    const double *e_meas;     /* 12 per edge: dRij[9] row-major, dtij[3] */
+    double info_diag[6];      /* the diagonal of the edges' information: rotation x, y, z, translation x, y, z */
+    int32_t max_iterations;   /* 0: the reference's 20 */
+    double lambda_init;       /* >= 0; 0: g2o's 1e-5 max |diag H|, what the reference runs with */
+} osg_essgraph4_problem;
+
+typedef struct osg_essgraph4_result {
+    double *pose;             /* OSG_EG4_POSE_OUT per vertex out: Rcw[9] tcw[3] Rwb[9] twb[3]; a fixed vertex
+                                 bit-equal to its input */
+    double chi2_initial, chi2_final;   /* sum of e' diag(info_diag) e */
+    int32_t lm_iterations, lm_trials;
+    double *edge_chi2;        /* optional (NULL: not written), per edge at the returned state */
+} osg_essgraph4_result;
+
+/* Returns 0 or a negative OSG_E_* code.  OSG_E_INVALID (nothing written, the context stays usable): an
+ * index outside [0, n_vertices), e_v0 == e_v1, a null array with a positive count, a negative count,
+ * lambda_init or max_iterations, more than 65 535 vertices, an info_diag entry that is negative or not
+ * finite.  OSG_E_NOMEM as osg_optimize_essential_graph.  n_edges == 0 or no free vertex: the output is the
+ * input, 0 iterations. */
+int osg_optimize_essential_graph_4dof(struct osg_ctx *ctx, const osg_essgraph4_problem *p, osg_essgraph4_result *r);
+/* The host check of the call above alone: 0 or OSG_E_INVALID.  Needs no context. */
+int osg_essgraph4_check(const osg_essgraph4_problem *p, const osg_essgraph4_result *r);
+
+/* Diagnostics: per-phase device time of osg_optimize_essential_graph and osg_optimize_essential_graph_4dof.  enable = 1: every later call
  * brackets its launches with HIP events (one pair per phase and launch group, read after the call);
  * 0 stops.  ms (may be NULL) receives the sums of the last timed call, in ms: linearise, assemble,
  * factor (damping copy, factorisation, both substitutions), update, chi2, and as the sixth value the

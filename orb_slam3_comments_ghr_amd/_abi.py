@@ -314,6 +314,20 @@ class OsgEssGraphResult(C.Structure):
     ]
 
 
+class OsgEssGraph4Problem(C.Structure):
+    _fields_ = [
+        ("n_vertices", i32), ("pose", P), ("fixed", P), ("n_edges", i32), ("e_v0", P), ("e_v1", P), ("e_meas", P),
+        ("info_diag", f64 * 6), ("max_iterations", i32), ("lambda_init", f64),
+    ]
+
+
+class OsgEssGraph4Result(C.Structure):
+    _fields_ = [
+        ("pose", P), ("chi2_initial", f64), ("chi2_final", f64), ("lm_iterations", i32), ("lm_trials", i32),
+        ("edge_chi2", P),
+    ]
+
+
 class OsgBaGraph(C.Structure):
     _fields_ = [
         ("n_poses", i32), ("pose", P), ("pose_fixed", P), ("n_points", i32), ("point", P),
@@ -387,6 +401,7 @@ EXPORTS = [
     "osg_sim3_ransac", "osg_sim3_ransac_batch", "osg_sim3_ransac_iterations",
     "osg_mlpnp_ransac", "osg_mlpnp_ransac_batch", "osg_mlpnp_ransac_parameters", "osg_mlpnp_check_samples",
     "osg_optimize_essential_graph", "osg_essgraph_correct_points", "osg_essgraph_kernel_times",
+    "osg_optimize_essential_graph_4dof", "osg_essgraph4_check",
     "osg_vocabulary_create", "osg_vocabulary_load_text", "osg_vocabulary_destroy", "osg_vocabulary_info",
     "osg_vocabulary_transform", "osg_vocabulary_transform_batch",
     "osg_kfdb_create", "osg_kfdb_destroy", "osg_kfdb_size", "osg_kfdb_add", "osg_kfdb_erase",
@@ -476,6 +491,8 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.osg_optimize_essential_graph.argtypes = [vp, C.POINTER(OsgEssGraphProblem), C.POINTER(OsgEssGraphResult)]
     lib.osg_essgraph_correct_points.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp]
     lib.osg_essgraph_kernel_times.argtypes = [vp, i32, vp]
+    lib.osg_optimize_essential_graph_4dof.argtypes = [vp, C.POINTER(OsgEssGraph4Problem), C.POINTER(OsgEssGraph4Result)]
+    lib.osg_essgraph4_check.argtypes = [C.POINTER(OsgEssGraph4Problem), C.POINTER(OsgEssGraph4Result)]
     lib.osg_local_bundle_adjustment.argtypes = [vp, C.POINTER(OsgBaGraph), C.POINTER(OsgBaResult),
                                                 vp]
     lib.osg_bundle_adjustment.argtypes = [vp, C.POINTER(OsgBaGraph), C.POINTER(OsgBaResult),

@@ -1,7 +1,9 @@
 // essgraph.hip — the g2o part of Optimizer::OptimizeEssentialGraph (ref:src/Optimizer.cc:4527-4858):
 // a pose graph of VertexSim3Expmap vertices and EdgeSim3 edges (error log(C * S_i * S_j^-1), identity
 // information, no robust kernel), optimised by g2o's Levenberg-Marquardt with a user lambda, and the
-// MapPoint correction of its write-back.  DESIGN.md §3.19.
+// MapPoint correction of its write-back.  DESIGN.md §3.19.  The same lists, assembly, factorisation and loop serve
+// the g2o part of Optimizer::OptimizeEssentialGraph4DoF (ref:src/Optimizer.cc:4870-5198; VertexPose4DoF, Edge4DoF)
+// with its own k_eg4_linearize, k_eg4_update and k_eg4_chi2.  DESIGN.md §3.26.
 //
 // Per LM iteration (device):
 //   k_eg_linearize  16 lanes per edge, four edges per wave: lane 0 the central error, lanes 1..14 the
@@ -31,8 +33,10 @@
 #include <cstring>
 #include <vector>
 
+#include "essgraph4_common.h"
 #include "osg_internal.h"
 #include "sim3_common.h"
+#include "so3_common.h"
 
 using osgs3::Sim3;
 
@@ -449,6 +453,207 @@ __global__ __launch_bounds__(256) void k_eg_chi2(const double *__restrict__ stat
     edge_chi[e] = c;
 }
 
+// ---- OptimizeEssentialGraph4DoF (ref:src/Optimizer.cc:4870-5198): VertexPose4DoF / Edge4DoF
+// in place of VertexSim3Expmap / EdgeSim3.  The lists, k_eg_assemble, k_eg_damp, k_eg_factor and the host loop
+// are the ones above.
+using namespace osgeg4;
+
+struct Info6 {
+    double w[6] = {1, 1, 1, 1, 1, 1};  // the diagonal of Edge4DoF's information
+};
+struct Cam4 {
+    double Rcw[9], tcw[3];
+};
+
+// ImuCamPose::UpdateW (ref:src/G2oTypes.cc:252-285) for VertexPose4DoF::oplusImpl's (0, 0, u0, u1, u2, u3), from
+// the state st and the constants cst of a vertex: the new DR, Rwb, twb and the camera re-derived from them.
+// The its counter and the normalisation that follows it act on DR alone and are k_eg4_update's.
+__device__ inline void eg4_update_w(const double *__restrict__ st, const double *__restrict__ cst, const double *u, double *DR,
+                                    double *Rwb, double *twb, Cam4 &C)
+{
+    const double w[3] = {0.0, 0.0, u[0]};
+    double dR[9], DR0[9], Rwb0[9], Rcb[9], Rbw[9], tbw[3];
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        DR0[i] = st[V_DR + i];
+        Rwb0[i] = st[V_RWB0 + i];
+        Rcb[i] = cst[i];
+    }
+    osgso3::exp_so3(w, dR);
+    osgso3::m3_mul(dR, DR0, DR);
+    osgso3::m3_mul(DR, Rwb0, Rwb);
+#pragma unroll
+    for (int i = 0; i < 3; i++) twb[i] = st[V_TWB + i] + u[1 + i];
+    osgso3::m3_t(Rwb, Rbw);
+    osgso3::m3_vec(Rbw, twb, tbw);
+#pragma unroll
+    for (int i = 0; i < 3; i++) tbw[i] = -tbw[i];
+    osgso3::m3_mul(Rcb, Rbw, C.Rcw);
+    osgso3::m3_vec(Rcb, tbw, C.tcw);
+#pragma unroll
+    for (int i = 0; i < 3; i++) C.tcw[i] += cst[9 + i];
+}
+__device__ __forceinline__ Cam4 load_cam4(const double *__restrict__ st)
+{
+    Cam4 C;
+#pragma unroll
+    for (int i = 0; i < 9; i++) C.Rcw[i] = st[V_RCW + i];
+#pragma unroll
+    for (int i = 0; i < 3; i++) C.tcw[i] = st[V_TCW + i];
+    return C;
+}
+// Edge4DoF::computeError (ref:include/G2oTypes.h:965-971); m: dRij row-major, dtij
+__device__ inline void eg4_error(const double *__restrict__ m, const Cam4 &Ci, const Cam4 &Cj, double *e)
+{
+    double Rjt[9], A[9], Mt[9], B[9], M[9], p[3], q[3];
+#pragma unroll
+    for (int i = 0; i < 9; i++) M[i] = m[i];
+    osgso3::m3_t(Cj.Rcw, Rjt);
+    osgso3::m3_mul(Ci.Rcw, Rjt, A);
+    osgso3::m3_t(M, Mt);
+    osgso3::m3_mul(A, Mt, B);
+    osgso3::log_so3(B, e);
+    osgso3::m3_vec(Rjt, Cj.tcw, p);
+#pragma unroll
+    for (int i = 0; i < 3; i++) p[i] = -p[i];
+    osgso3::m3_vec(Ci.Rcw, p, q);
+#pragma unroll
+    for (int i = 0; i < 3; i++) e[3 + i] = q[i] + Ci.tcw[i] - m[9 + i];
+}
+
+// 16 lanes per edge, four edges per wave, as k_eg_linearize: lane 0 the central error at the stored cameras,
+// lanes 1..8 the +-delta pair of one (side, dimension) through UpdateW, lanes 9..15 idle.  The slot keeps the
+// 7 x 7 layout of ES; only its rows and columns 0..3 are written (the host zeroes the slots once).
+__global__ __launch_bounds__(64) void k_eg4_linearize(const double *__restrict__ state, const double *__restrict__ cst,
+                                                      const double *__restrict__ meas, const int *__restrict__ v0,
+                                                      const int *__restrict__ v1, const int *__restrict__ fidx, int n_edges,
+                                                      Info6 info, double *__restrict__ slots)
+{
+    __shared__ double sJ[4][2][6][4];  // [edge of the wave][side][error row][update column]
+    __shared__ double sE[4][6];
+    const int g = threadIdx.x >> 4, k = threadIdx.x & 15;
+    const int e = blockIdx.x * 4 + g;
+    const bool valid = e < n_edges && k < 9;
+    const int side = k >= 5 ? 1 : 0, d = k == 0 ? 0 : (k - 1) - 4 * side;
+    double col[6] = {0, 0, 0, 0, 0, 0};
+    if (valid) {
+        const int a = v0[e], b = v1[e];
+        const double *m = meas + 12 * (size_t)e, *sa = state + VS * (size_t)a, *sb = state + VS * (size_t)b;
+        const Cam4 Ci = load_cam4(sa), Cj = load_cam4(sb);
+        if (k == 0) {
+            eg4_error(m, Ci, Cj, col);
+#pragma unroll
+            for (int r = 0; r < 6; r++) sE[g][r] = col[r];
+        } else {
+            const bool skip = (side ? fidx[b] : fidx[a]) < 0;
+            if (!skip) {
+                const double *sv = side ? sb : sa, *cv = cst + VC * (size_t)(side ? b : a);
+#pragma unroll 1
+                for (int sgn = 0; sgn < 2; sgn++) {
+                    double upd[4], DR[9], Rwb[9], twb[3], er[6];
+#pragma unroll
+                    for (int i = 0; i < 4; i++) upd[i] = i == d ? (sgn ? -DELTA : DELTA) : 0.0;
+                    Cam4 T;
+                    eg4_update_w(sv, cv, upd, DR, Rwb, twb, T);
+                    eg4_error(m, side ? Ci : T, side ? T : Cj, er);
+                    const double scalar = 1.0 / (2 * DELTA);
+#pragma unroll
+                    for (int r = 0; r < 6; r++) col[r] = sgn ? scalar * (col[r] - er[r]) : er[r];
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 6; r++) sJ[g][side][r][d] = col[r];
+        }
+    }
+    __syncthreads();
+    if (!valid) return;
+    double *slot = slots + (size_t)ES * e;
+    if (k == 0) {
+        double c = 0;
+#pragma unroll
+        for (int r = 0; r < 6; r++) c += col[r] * (info.w[r] * col[r]);
+        slot[S_CHI] = c;
+        return;
+    }
+    // row d of J_s^T W J_s, of J_i^T W J_j (side 0), and entry d of -J_s^T W e
+    double wc[6];
+#pragma unroll
+    for (int r = 0; r < 6; r++) wc[r] = col[r] * info.w[r];
+    for (int c = 0; c < 4; c++) {
+        double h = 0, x = 0;
+#pragma unroll
+        for (int r = 0; r < 6; r++) {
+            h += wc[r] * sJ[g][side][r][c];
+            x += wc[r] * sJ[g][1][r][c];
+        }
+        slot[(side ? S_HJJ : 0) + 7 * d + c] = h;
+        if (!side) slot[S_HIJ + 7 * d + c] = x;
+    }
+    double bs = 0;
+#pragma unroll
+    for (int r = 0; r < 6; r++) bs += col[r] * (info.w[r] * sE[g][r]);
+    slot[S_B + 7 * side + d] = -bs;
+}
+
+// VertexPose4DoF::oplusImpl per vertex into the trial buffer: UpdateW with its counter, the four zeroed
+// entries and the normalisation of DR in the reference's order (they act on the next update's rotation)
+__global__ __launch_bounds__(256) void k_eg4_update(const double *__restrict__ cur, const double *__restrict__ cst,
+                                                    const double *__restrict__ x, const int *__restrict__ fidx, int n,
+                                                    double *__restrict__ trial)
+{
+    const int v = blockIdx.x * 256 + threadIdx.x;
+    if (v >= n) return;
+    const double *st = cur + VS * (size_t)v;
+    double *out = trial + VS * (size_t)v;
+    const int f = fidx[v];
+    if (f < 0) {
+        for (int i = 0; i < VS; i++) out[i] = st[i];
+        return;
+    }
+    double u[4], DR[9], Rwb[9], twb[3];
+#pragma unroll
+    for (int i = 0; i < 4; i++) u[i] = x[8 * (size_t)f + i];
+    Cam4 C;
+    eg4_update_w(st, cst + VC * (size_t)v, u, DR, Rwb, twb, C);
+    int its = (int)st[V_ITS] + 1;
+    if (its >= 5) {
+        DR[2] = 0.0;
+        DR[5] = 0.0;
+        DR[6] = 0.0;
+        DR[7] = 0.0;
+        osgso3::normalize_rotation<double>(DR);
+        its = 0;
+    }
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        out[V_RWB0 + i] = st[V_RWB0 + i];
+        out[V_DR + i] = DR[i];
+        out[V_RCW + i] = C.Rcw[i];
+        out[V_RWB + i] = Rwb[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        out[V_TWB + i] = twb[i];
+        out[V_TCW + i] = C.tcw[i];
+    }
+    out[V_ITS] = (double)its;
+    for (int i = V_ITS + 1; i < VS; i++) out[i] = 0.0;
+}
+
+__global__ __launch_bounds__(256) void k_eg4_chi2(const double *__restrict__ state, const double *__restrict__ meas,
+                                                  const int *__restrict__ v0, const int *__restrict__ v1, int n_edges, Info6 info,
+                                                  double *__restrict__ edge_chi)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= n_edges) return;
+    double er[6];
+    eg4_error(meas + 12 * (size_t)e, load_cam4(state + VS * (size_t)v0[e]), load_cam4(state + VS * (size_t)v1[e]), er);
+    double c = 0;
+#pragma unroll
+    for (int r = 0; r < 6; r++) c += er[r] * (info.w[r] * er[r]);
+    edge_chi[e] = c;
+}
+
 // one workgroup: the sum (mode 0) or the maximum (mode 1) of src[0 .. n) in a fixed order
 __global__ __launch_bounds__(256) void k_eg_reduce(const double *__restrict__ src, int n, int mode, double *__restrict__ dst)
 {
@@ -538,27 +743,88 @@ int osg_essgraph_kernel_times(osg_ctx *ctx, int32_t enable, double *ms)
     return OSG_OK;
 }
 
-int osg_optimize_essential_graph(osg_ctx *ctx, const osg_essgraph_problem *p, osg_essgraph_result *r)
-{
-    if (!ctx) return OSG_E_INVALID;
-    OSG_REQUIRE(ctx, p && r, "null argument");
-    const int n = p->n_vertices, E = p->n_edges;
-    OSG_REQUIRE(ctx, n >= 0 && n <= 65535, "n_vertices must be in [0, 65535]");
-    OSG_REQUIRE(ctx, E >= 0 && E <= (1 << 24), "n_edges must be in [0, 2^24]");
-    OSG_REQUIRE(ctx, n == 0 || (p->sim3 && p->fixed && r->sim3), "vertex arrays");
-    OSG_REQUIRE(ctx, E == 0 || (p->e_v0 && p->e_v1 && p->e_meas), "edge arrays");
-    OSG_REQUIRE(ctx, p->max_iterations >= 0, "max_iterations");
-    OSG_REQUIRE(ctx, p->lambda_init >= 0.0, "lambda_init must not be negative");
-    for (int v = 0; v < n; v++) OSG_REQUIRE(ctx, p->sim3[8 * (size_t)v + 7] > 0.0, "the scale of vertex %d is not positive", v);
-    for (int e = 0; e < E; e++) {
-        const int a = p->e_v0[e], b = p->e_v1[e];
-        OSG_REQUIRE(ctx, a >= 0 && a < n && b >= 0 && b < n && a != b, "edge %d joins vertices %d and %d", e, a, b);
-        OSG_REQUIRE(ctx, p->e_meas[8 * (size_t)e + 7] > 0.0, "the scale of measurement %d is not positive", e);
+}  // extern "C"
+
+namespace {
+
+// The checked graph of either entry point as the shared driver reads it, and what it returns.
+struct EgIn {
+    int n_vertices, n_edges;
+    const uint8_t *fixed;
+    const int32_t *e_v0, *e_v1;
+    const double *state, *e_meas, *consts;  // K::SD, K::MD, K::CD doubles per vertex / edge / vertex
+    int max_iterations;
+    double lambda_init;
+    int fix_scale;
+    Info6 info;
+    bool want_edge_chi2;
+};
+struct EgOut {
+    std::vector<double> state, edge_chi2;  // every vertex's returned state; per edge when asked for
+    double chi2_initial = 0.0, chi2_final = 0.0;
+    int lm_iterations = 0, lm_trials = 0;
+};
+
+// what the kernels of a graph kind read
+struct EgDev {
+    const double *meas, *consts;
+    const int *v0, *v1, *fidx;
+    int n, E, fix_scale;
+    Info6 info;
+    hipStream_t stream;
+};
+
+// VertexSim3Expmap / EdgeSim3
+struct Sim3Graph {
+    static constexpr int SD = 8, MD = 8, CD = 0;
+    static constexpr bool SPARSE_SLOTS = false;
+    static void linearize(const EgDev &D, const double *cur, double *slots)
+    {
+        hipLaunchKernelGGL(k_eg_linearize, dim3((D.E + 3) / 4), dim3(64), 0, D.stream, cur, D.meas, D.v0, D.v1, D.fidx, D.E,
+                           D.fix_scale, slots);
     }
+    static void update(const EgDev &D, const double *cur, const double *x, double *trial)
+    {
+        hipLaunchKernelGGL(k_eg_update, dim3((D.n + 255) / 256), dim3(256), 0, D.stream, cur, x, D.fidx, D.n, D.fix_scale, trial);
+    }
+    static void chi2(const EgDev &D, const double *state, double *edge_chi)
+    {
+        hipLaunchKernelGGL(k_eg_chi2, dim3((D.E + 255) / 256), dim3(256), 0, D.stream, state, D.meas, D.v0, D.v1, D.E, edge_chi);
+    }
+};
+
+// VertexPose4DoF / Edge4DoF.  Its slots keep the 7 x 7 layout with the rows and columns 4..6 left zero, so
+// k_eg_assemble, k_eg_damp and k_eg_factor run as they are: those rows of the damped system are lambda on the
+// diagonal and 0 elsewhere, their x is 0, and they add nothing to any other entry, to lambda's start or to
+// the scale sum.
+struct Pose4Graph {
+    static constexpr int SD = VS, MD = 12, CD = VC;
+    static constexpr bool SPARSE_SLOTS = true;
+    static void linearize(const EgDev &D, const double *cur, double *slots)
+    {
+        hipLaunchKernelGGL(k_eg4_linearize, dim3((D.E + 3) / 4), dim3(64), 0, D.stream, cur, D.consts, D.meas, D.v0, D.v1,
+                           D.fidx, D.E, D.info, slots);
+    }
+    static void update(const EgDev &D, const double *cur, const double *x, double *trial)
+    {
+        hipLaunchKernelGGL(k_eg4_update, dim3((D.n + 255) / 256), dim3(256), 0, D.stream, cur, D.consts, x, D.fidx, D.n, trial);
+    }
+    static void chi2(const EgDev &D, const double *state, double *edge_chi)
+    {
+        hipLaunchKernelGGL(k_eg4_chi2, dim3((D.E + 255) / 256), dim3(256), 0, D.stream, state, D.meas, D.v0, D.v1, D.E, D.info,
+                           edge_chi);
+    }
+};
+
+// SparseOptimizer::optimize on a checked graph of kind K: the structure, the device memory and g2o's
+// Levenberg-Marquardt.  Nothing of the caller's is written here.
+template <class K>
+int eg_solve(osg_ctx *ctx, const EgIn *p, EgOut *r)
+{
+    const int n = p->n_vertices, E = p->n_edges;
+    constexpr size_t SB = 8 * (size_t)K::SD, MB = 8 * (size_t)K::MD, CB = 8 * (size_t)K::CD;
     EgState *st = eg_state(ctx);
     for (int i = 0; i < OSG_ESSGRAPH_NK; i++) st->ms[i] = 0.0;
-    r->chi2_initial = r->chi2_final = 0.0;
-    r->lm_iterations = r->lm_trials = 0;
     if (n == 0) return OSG_OK;
 
     // ---- host structure: free numbering, CSR lists in edge order, the envelope
@@ -613,15 +879,16 @@ int osg_optimize_essential_graph(osg_ctx *ctx, const osg_essgraph_problem *p, os
     const int n_pairs = (int)p_hi.size();
 
     // ---- device memory.  in: the constant arrays; work: states, vectors, scalars; then the slots and the store
-    const size_t o_state = 0, o_meas = o_state + al256(64 * (size_t)n), o_v0 = o_meas + al256(64 * (size_t)E);
+    const size_t o_state = 0, o_meas = o_state + al256(SB * n), o_v0 = o_meas + al256(MB * E);
     const size_t o_v1 = o_v0 + al256(4 * (size_t)E), o_fidx = o_v1 + al256(4 * (size_t)E);
     const size_t o_dptr = o_fidx + al256(4 * (size_t)n), o_dent = o_dptr + al256(4 * d_ptr.size());
     const size_t o_pptr = o_dent + al256(4 * d_ent.size()), o_pent = o_pptr + al256(4 * p_ptr.size());
     const size_t o_phi = o_pent + al256(4 * p_ent.size()), o_plo = o_phi + al256(4 * p_hi.size());
     const size_t o_first = o_plo + al256(4 * p_lo.size()), o_roff = o_first + al256(4 * first.size());
-    const size_t in_bytes = o_roff + al256(8 * row_off.size()) + 256;
+    const size_t o_const = o_roff + al256(8 * row_off.size());
+    const size_t in_bytes = o_const + al256(CB * n) + 256;
     const size_t N = (size_t)TB * T;
-    const size_t w_trial = al256(64 * (size_t)n), w_chi = w_trial + al256(64 * (size_t)n);
+    const size_t w_trial = al256(SB * n), w_chi = w_trial + al256(SB * n);
     const size_t w_b = w_chi + al256(8 * (size_t)E), w_y = w_b + al256(8 * N), w_xt = w_y + al256(8 * N);
     const size_t w_x = w_xt + al256(8 * N), w_dmax = w_x + al256(8 * N), w_ctl = w_dmax + al256(8 * (size_t)nf);
     const size_t work_bytes = w_ctl + 256;
@@ -644,9 +911,10 @@ int osg_optimize_essential_graph(osg_ctx *ctx, const osg_essgraph_problem *p, os
     }
     st->ms[5] = (double)(2 * store_bytes + (solve ? (size_t)T * TE * 8 : 0));
     std::vector<char> hin(in_bytes, 0);
-    std::memcpy(hin.data() + o_state, p->sim3, 64 * (size_t)n);
+    std::memcpy(hin.data() + o_state, p->state, SB * n);
+    if (CB) std::memcpy(hin.data() + o_const, p->consts, CB * n);
     if (E) {
-        std::memcpy(hin.data() + o_meas, p->e_meas, 64 * (size_t)E);
+        std::memcpy(hin.data() + o_meas, p->e_meas, MB * E);
         std::memcpy(hin.data() + o_v0, p->e_v0, 4 * (size_t)E);
         std::memcpy(hin.data() + o_v1, p->e_v1, 4 * (size_t)E);
     }
@@ -681,10 +949,11 @@ int osg_optimize_essential_graph(osg_ctx *ctx, const osg_essgraph_problem *p, os
     double *pin = (double *)osg_pinned(ctx, 4096);
     if (!pin) return osg_set_error(ctx, OSG_E_NOMEM, "pinned alloc failed");
     const int fs = p->fix_scale ? 1 : 0;
+    const EgDev D = {d_meas, (const double *)(din + o_const), d_v0, d_v1, d_fidx, n, E, fs, p->info, ctx->stream};
     // computeActiveErrors + activeChi2 at a state -> d_chi, d_ctl[2]
     auto chi_pass = [&](const double *state) -> int {
         Phase ph(ctx, st, PH_CHI);
-        hipLaunchKernelGGL(k_eg_chi2, dim3((E + 255) / 256), dim3(256), 0, ctx->stream, state, d_meas, d_v0, d_v1, E, d_chi);
+        K::chi2(D, state, d_chi);
         hipLaunchKernelGGL(k_eg_reduce, dim3(1), dim3(256), 0, ctx->stream, (const double *)d_chi, E, 0, d_ctl + 2);
         OSG_HIP_CHECK(ctx, hipGetLastError());
         return OSG_OK;
@@ -703,6 +972,9 @@ int osg_optimize_essential_graph(osg_ctx *ctx, const osg_essgraph_problem *p, os
     if (solve) {
         OSG_HIP_CHECK(ctx, hipMemsetAsync(dH, 0, store_bytes, ctx->stream));
         OSG_HIP_CHECK(ctx, hipMemsetAsync(d_x, 0, 8 * N, ctx->stream));
+        if (K::SPARSE_SLOTS) {
+            OSG_HIP_CHECK(ctx, hipMemsetAsync(dslots, 0, (size_t)ES * 8 * E, ctx->stream));
+        }
         const int n_iter = p->max_iterations > 0 ? p->max_iterations : 20;
         double lambda = 0, ni = 2, currentChi = chi_init;
         int nBad = 0;
@@ -710,8 +982,7 @@ int osg_optimize_essential_graph(osg_ctx *ctx, const osg_essgraph_problem *p, os
             iters++;
             {
                 Phase ph(ctx, st, PH_LIN);
-                hipLaunchKernelGGL(k_eg_linearize, dim3((E + 3) / 4), dim3(64), 0, ctx->stream, (const double *)cur, d_meas,
-                                   d_v0, d_v1, d_fidx, E, fs, dslots);
+                K::linearize(D, cur, dslots);
             }
             {
                 Phase ph(ctx, st, PH_ASM);
@@ -746,8 +1017,7 @@ int osg_optimize_essential_graph(osg_ctx *ctx, const osg_essgraph_problem *p, os
                 }
                 {
                     Phase ph(ctx, st, PH_UPDATE);
-                    hipLaunchKernelGGL(k_eg_update, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (const double *)cur,
-                                       (const double *)d_x, d_fidx, n, fs, trial);
+                    K::update(D, cur, d_x, trial);
                 }
                 OSG_HIP_CHECK(ctx, hipGetLastError());
                 OSG_RC(chi_pass(trial));
@@ -781,19 +1051,79 @@ int osg_optimize_essential_graph(osg_ctx *ctx, const osg_essgraph_problem *p, os
         OSG_RC(read_ctl());
         chi_final = pin[2];
     }
-    // ---- results: written only now, after every step that can fail
-    std::vector<double> out(8 * (size_t)n), echi(r->edge_chi2 ? (size_t)E : 0);
-    OSG_HIP_CHECK(ctx, hipMemcpyAsync(out.data(), cur, 64 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    if (r->edge_chi2 && E)
-        OSG_HIP_CHECK(ctx, hipMemcpyAsync(echi.data(), d_chi, 8 * (size_t)E, hipMemcpyDeviceToHost, ctx->stream));
+    r->state.resize((size_t)K::SD * n);
+    r->edge_chi2.resize(p->want_edge_chi2 ? (size_t)E : 0);
+    OSG_HIP_CHECK(ctx, hipMemcpyAsync(r->state.data(), cur, SB * n, hipMemcpyDeviceToHost, ctx->stream));
+    if (p->want_edge_chi2 && E)
+        OSG_HIP_CHECK(ctx, hipMemcpyAsync(r->edge_chi2.data(), d_chi, 8 * (size_t)E, hipMemcpyDeviceToHost, ctx->stream));
     OSG_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    for (int v = 0; v < n; v++)
-        std::memcpy(r->sim3 + 8 * (size_t)v, (p->fixed[v] ? p->sim3 : out.data()) + 8 * (size_t)v, 64);
-    if (r->edge_chi2 && E) std::memcpy(r->edge_chi2, echi.data(), 8 * (size_t)E);
     r->chi2_initial = chi_init;
     r->chi2_final = chi_final;
     r->lm_iterations = iters;
     r->lm_trials = trials;
+    return OSG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int osg_optimize_essential_graph(osg_ctx *ctx, const osg_essgraph_problem *p, osg_essgraph_result *r)
+{
+    if (!ctx) return OSG_E_INVALID;
+    OSG_REQUIRE(ctx, p && r, "null argument");
+    const int n = p->n_vertices, E = p->n_edges;
+    OSG_REQUIRE(ctx, n >= 0 && n <= 65535, "n_vertices must be in [0, 65535]");
+    OSG_REQUIRE(ctx, E >= 0 && E <= (1 << 24), "n_edges must be in [0, 2^24]");
+    OSG_REQUIRE(ctx, n == 0 || (p->sim3 && p->fixed && r->sim3), "vertex arrays");
+    OSG_REQUIRE(ctx, E == 0 || (p->e_v0 && p->e_v1 && p->e_meas), "edge arrays");
+    OSG_REQUIRE(ctx, p->max_iterations >= 0, "max_iterations");
+    OSG_REQUIRE(ctx, p->lambda_init >= 0.0, "lambda_init must not be negative");
+    for (int v = 0; v < n; v++) OSG_REQUIRE(ctx, p->sim3[8 * (size_t)v + 7] > 0.0, "the scale of vertex %d is not positive", v);
+    for (int e = 0; e < E; e++) {
+        const int a = p->e_v0[e], b = p->e_v1[e];
+        OSG_REQUIRE(ctx, a >= 0 && a < n && b >= 0 && b < n && a != b, "edge %d joins vertices %d and %d", e, a, b);
+        OSG_REQUIRE(ctx, p->e_meas[8 * (size_t)e + 7] > 0.0, "the scale of measurement %d is not positive", e);
+    }
+    EgIn in = {n, E, p->fixed, p->e_v0, p->e_v1, p->sim3, p->e_meas, nullptr, p->max_iterations, p->lambda_init,
+               p->fix_scale ? 1 : 0, Info6(), r->edge_chi2 != nullptr};
+    EgOut out;
+    OSG_RC(eg_solve<Sim3Graph>(ctx, &in, &out));
+    // ---- results: written only now, after every step that can fail
+    for (int v = 0; v < n; v++)
+        std::memcpy(r->sim3 + 8 * (size_t)v, (p->fixed[v] ? p->sim3 : out.state.data()) + 8 * (size_t)v, 64);
+    if (r->edge_chi2 && E) std::memcpy(r->edge_chi2, out.edge_chi2.data(), 8 * (size_t)E);
+    r->chi2_initial = out.chi2_initial;
+    r->chi2_final = out.chi2_final;
+    r->lm_iterations = out.lm_iterations;
+    r->lm_trials = out.lm_trials;
+    return OSG_OK;
+}
+
+int osg_essgraph4_check(const osg_essgraph4_problem *p, const osg_essgraph4_result *r)
+{
+    return osgeg4::check(p, r, nullptr);
+}
+
+int osg_optimize_essential_graph_4dof(osg_ctx *ctx, const osg_essgraph4_problem *p, osg_essgraph4_result *r)
+{
+    if (!ctx) return OSG_E_INVALID;
+    const char *why = nullptr;
+    if (osgeg4::check(p, r, &why) != 0) return osg_set_error(ctx, OSG_E_INVALID, "%s", why);
+    const int n = p->n_vertices, E = p->n_edges;
+    std::vector<double> state, consts;
+    osgeg4::pack(*p, state, consts);
+    EgIn in = {n, E, p->fixed, p->e_v0, p->e_v1, state.data(), p->e_meas, consts.data(), p->max_iterations, p->lambda_init,
+               0, Info6(), r->edge_chi2 != nullptr};
+    for (int i = 0; i < 6; i++) in.info.w[i] = p->info_diag[i];
+    EgOut out;
+    OSG_RC(eg_solve<Pose4Graph>(ctx, &in, &out));
+    for (int v = 0; v < n; v++) osgeg4::unpack(*p, v, out.state.data(), r->pose + OSG_EG4_POSE_OUT * (size_t)v);
+    if (r->edge_chi2 && E) std::memcpy(r->edge_chi2, out.edge_chi2.data(), 8 * (size_t)E);
+    r->chi2_initial = out.chi2_initial;
+    r->chi2_final = out.chi2_final;
+    r->lm_iterations = out.lm_iterations;
+    r->lm_trials = out.lm_trials;
     return OSG_OK;
 }
 

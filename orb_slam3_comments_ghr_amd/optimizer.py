@@ -349,6 +349,75 @@ class EssentialGraphResult:
         return self.sim3[:, 7]
 
 
+@dataclass
+class EssentialGraph4DoFProblem:
+    """One ``Optimizer::OptimizeEssentialGraph4DoF`` call as the adapter gathers it (include/osg_ba.h): per
+    non-bad KeyFrame the ImuCamPose of its VertexPose4DoF as constructed, the edges in the reference's insertion
+    order with their Tij as (dRij, dtij)."""
+    pose: np.ndarray          # n x 36 double: Rwb[9] twb[3] Rcw[9] tcw[3] Rcb[9] tcb[3], matrices row-major
+    fixed: np.ndarray         # n uint8
+    e_v0: np.ndarray          # E int32, vertex(0) = i
+    e_v1: np.ndarray          # E int32, vertex(1) = j
+    e_meas: np.ndarray        # E x 12 double: dRij row-major, dtij
+    info_diag: tuple = (1e3, 1e3, 1.0, 1.0, 1.0, 1.0)   # matLambda as the reference leaves it: (2, 2) stays 1
+    max_iterations: int = 0   # 0: the reference's 20
+    lambda_init: float = 0.0  # 0: g2o's 1e-5 max |diag H|, the reference's
+    truth: np.ndarray | None = None    # generator only (consistent=True): n x 36, the poses the measurements were built from
+    built: np.ndarray | None = None    # generator only: per vertex b"C" (the 3-argument constructor) or b"K" (the KeyFrame's)
+
+    def __post_init__(self):
+        self.pose = np.ascontiguousarray(self.pose, np.float64).reshape(-1, 36)
+        self.fixed = np.ascontiguousarray(self.fixed, np.uint8)
+        self.e_v0 = np.ascontiguousarray(self.e_v0, np.int32)
+        self.e_v1 = np.ascontiguousarray(self.e_v1, np.int32)
+        self.e_meas = np.ascontiguousarray(self.e_meas, np.float64).reshape(-1, 12)
+
+    @property
+    def n(self):
+        return len(self.pose)
+
+    @property
+    def n_edges(self):
+        return len(self.e_v0)
+
+    def struct(self):
+        st = _abi.OsgEssGraph4Problem()
+        st.n_vertices, st.pose, st.fixed = self.n, _p(self.pose), _p(self.fixed)
+        st.n_edges, st.e_v0, st.e_v1, st.e_meas = self.n_edges, _p(self.e_v0), _p(self.e_v1), _p(self.e_meas)
+        for i in range(6):
+            st.info_diag[i] = float(self.info_diag[i])
+        st.max_iterations = int(self.max_iterations)
+        st.lambda_init = float(self.lambda_init)
+        return st
+
+
+@dataclass
+class EssentialGraph4DoFResult:
+    pose: np.ndarray          # n x 24: Rcw[9] tcw[3] Rwb[9] twb[3]; a fixed vertex bit-equal to its input
+    chi2_initial: float
+    chi2_final: float
+    lm_iterations: int
+    lm_trials: int
+    edge_chi2: np.ndarray     # per edge at the returned state
+
+    @property
+    def R(self):
+        """Rcw, what the write-back reads"""
+        return self.pose[:, 0:9].reshape(-1, 3, 3)
+
+    @property
+    def t(self):
+        return self.pose[:, 9:12]
+
+    @property
+    def Rwb(self):
+        return self.pose[:, 12:21].reshape(-1, 3, 3)
+
+    @property
+    def twb(self):
+        return self.pose[:, 21:24]
+
+
 def run_pose(fn, problems, handle=None):
     """Call a PoseOptimization entry point on problems: the batch API (handle given) or a
     per-problem function fn(problem_structs, result_structs)."""
@@ -451,6 +520,19 @@ class Optimizer:
                        "OptimizeEssentialGraph")
         return EssentialGraphResult(out, R.chi2_initial, R.chi2_final, R.lm_iterations, R.lm_trials, chi)
 
+    def optimize_essential_graph_4dof(self, P: EssentialGraph4DoFProblem) -> EssentialGraph4DoFResult:
+        """The g2o part of ``Optimizer::OptimizeEssentialGraph4DoF`` (ref:src/Optimizer.cc:4870-5198): the pose
+        graph of an inertial map, its vertices updated in yaw and translation alone, optimize(20) with g2o's own
+        lambda.  The caller writes ``Rcw``, ``tcw`` back and corrects the MapPoints with ``correct_map_points``
+        (unit scales)."""
+        st = P.struct()
+        R = _abi.OsgEssGraph4Result()
+        out, chi = np.zeros((P.n, 24), np.float64), np.zeros(P.n_edges, np.float64)
+        R.pose, R.edge_chi2 = _p(out), _p(chi)
+        self.ctx.check(self.ctx.lib.osg_optimize_essential_graph_4dof(self.ctx.handle, C.byref(st), C.byref(R)),
+                       "OptimizeEssentialGraph4DoF")
+        return EssentialGraph4DoFResult(out, R.chi2_initial, R.chi2_final, R.lm_iterations, R.lm_trials, chi)
+
     def correct_map_points(self, Xw, ref_vertex, sim3_before, sim3_after):
         """``correctedSwr.map(Srw.map(X))`` of every MapPoint through its reference KeyFrame's vertex
         (ref:src/Optimizer.cc:4824-4851); a point with ``ref_vertex < 0`` is copied through."""
@@ -465,7 +547,8 @@ class Optimizer:
         return out
 
     def essential_graph_kernel_times(self, enable=True):
-        """(ms by phase: linearise, assemble, factor, update, chi2; matrix store bytes) of the last timed call"""
+        """(ms by phase: linearise, assemble, factor, update, chi2; matrix store bytes) of the last timed call of
+        ``optimize_essential_graph`` or ``optimize_essential_graph_4dof``"""
         ms = np.zeros(6, np.float64)
         self.ctx.check(self.ctx.lib.osg_essgraph_kernel_times(self.ctx.handle, int(bool(enable)), _p(ms)), "kernel times")
         return dict(zip(["linearise", "assemble", "factor", "update", "chi2"], ms[:5].tolist())), int(ms[5])
@@ -792,6 +875,141 @@ def synth_essential_graph(rng, n_kf, n_loop=3, extra_loops=0, fix_scale=False, c
     return EssentialGraphProblem(np.array([s3_row(e) for e in est]), fixed, np.array(v0, np.int32), np.array(v1, np.int32),
                                  np.array(meas).reshape(-1, 8), fix_scale=bool(fix_scale),
                                  truth=np.array([s3_row(g) for g in G]) if consistent else None)
+
+
+def imu_cam_pose_row(Rwb, twb, Rcw, tcw, Rcb, tcb):
+    """the 36 doubles of one vertex of an EssentialGraph4DoFProblem"""
+    return np.concatenate([np.asarray(Rwb, np.float64).ravel(), np.asarray(twb, np.float64),
+                           np.asarray(Rcw, np.float64).ravel(), np.asarray(tcw, np.float64),
+                           np.asarray(Rcb, np.float64).ravel(), np.asarray(tcb, np.float64)])
+
+
+def imu_cam_pose_corrected(Rwc, twc, Rcb, tcb):
+    """ImuCamPose(Rwc, twc, pKF) (ref:src/G2oTypes.cc:132-157), the vertex of a KeyFrame in CorrectedSim3: double
+    arithmetic on the inverse of the corrected Sim3, Tcb cast from the KeyFrame's float calibration."""
+    Rwc, twc = np.asarray(Rwc, np.float64), np.asarray(twc, np.float64)
+    Rcb, tcb = np.asarray(Rcb, np.float32).astype(np.float64), np.asarray(tcb, np.float32).astype(np.float64)
+    Rcw = Rwc.T.copy()
+    return imu_cam_pose_row(Rwc @ Rcb, Rwc @ tcb + twc, Rcw, -Rcw @ twc, Rcb, tcb)
+
+
+def imu_cam_pose_keyframe(Rcw, tcw, Rcb, tcb):
+    """ImuCamPose(pKF) (ref:src/G2oTypes.cc:29-75): every field cast from the floats KeyFrame::SetPose derived
+    (Rwc = Rcw', Ow = -Rwc tcw, Owb = Rwc tcb + Ow, Rwb = Rwc Rcb, ref:src/KeyFrame.cc:90-107), here with numpy's
+    float32 products."""
+    f = np.float32
+    Rcw, tcw, Rcb, tcb = np.asarray(Rcw, f), np.asarray(tcw, f), np.asarray(Rcb, f), np.asarray(tcb, f)
+    Rwc = Rcw.T
+    Ow = -(Rwc @ tcw)
+    return imu_cam_pose_row(Rwc @ Rcb, Rwc @ tcb + Ow, Rcw, tcw, Rcb, tcb)
+
+
+def synth_essential_graph_4dof(rng, n_kf, n_loop=3, extra_loops=0, consistent=False, drift=(3.0, 0.2),
+                               meas_noise=(0.02, 0.002), radius=0.8):
+    """The pose graph LoopClosing::CorrectLoop hands to OptimizeEssentialGraph4DoF in an inertial map: n_kf
+    KeyFrames on a closed trajectory (a circle of ``radius`` m in the plane across gravity, world z up, cameras
+    looking at its centre), a body-camera extrinsic that is not the identity, KeyFrame 0 fixed, the last
+    ``n_loop`` KeyFrames built as corrected (the 3-argument constructor), the others from the KeyFrame's floats.
+    Edges in the reference's insertion order: the LoopConnections (corrected KeyFrame k -> the KeyFrames
+    k - (n_kf - n_loop) and k - (n_kf - n_loop) + 1 at the start), then per KeyFrame i its mPrevKF edge
+    (i -> i - 1), its earlier loop edges (``extra_loops`` of them, as ``synth_essential_graph`` places them) and its
+    covisibility edges (i -> i - 2, i -> i - 3).  An edge (i, j) measures Tcw_i Tcw_j^-1.
+
+    The drift of an inertial map is in yaw and translation alone (gravity pins roll and pitch): it grows
+    linearly along the trajectory to ``drift`` = (degrees of yaw, metres) and moves the body pose as the vertex's
+    update does, Rwb <- Rz(yaw) Rwb, twb <- twb + d.
+      consistent=False: as the reference builds it.  The non-corrected poses N_i are the drifted ones, the
+        corrected KeyFrames are N_i with the drift of the trajectory's end taken out, every non-loop measurement
+        is N_i N_j^-1 and every loop measurement that of the initial estimates, each moved by a small rotation
+        about a random axis and a translation (``meas_noise`` degrees, metres: the roll / pitch the edges carry).
+      consistent=True: double throughout; the measurements are those of a ground truth (returned as ``truth``),
+        the corrected KeyFrames and KeyFrame 0 start at it and the others at the truth moved in yaw and
+        translation, so the optimum is the truth with chi2 = 0."""
+    n, m = int(n_kf), int(n_loop)
+    assert n >= 2 and 0 <= m < n
+    ang = 2 * np.pi * np.arange(n) / n
+    # Tcb as the calibration's floats give it: orthonormal to float precision
+    Rcb = rodrigues(np.array([1.2, -1.19, 1.21]) + 0.01 * rng.normal(size=3)).astype(np.float32).astype(np.float64)
+    tcb = (np.array([0.065, -0.021, 0.009]) + 0.002 * rng.normal(size=3)).astype(np.float32).astype(np.float64)
+    Gb = []                      # ground truth body poses (Rwb, twb)
+    for i in range(n):
+        c = np.array([radius * np.cos(ang[i]), radius * np.sin(ang[i]), 0.05 * np.sin(3 * ang[i])])
+        Rcw, tcw = look_at(c, [0.0, 0.0, 0.3 * rng.normal()], up=(0, 0, 1))
+        Rwc, twc = Rcw.T, -Rcw.T @ tcw
+        Gb.append((Rwc @ Rcb, Rwc @ tcb + twc))
+    tdir = rng.normal(size=3)
+    tdir /= np.linalg.norm(tdir)
+
+    def moved(b, f):
+        return rodrigues([0.0, 0.0, np.deg2rad(drift[0]) * f]) @ b[0], b[1] + drift[1] * f * tdir
+
+    def cam(b):                  # (Rcw, tcw) of a body pose
+        Rcw = Rcb @ b[0].T
+        return Rcw, Rcb @ (-(b[0].T @ b[1])) + tcb
+
+    frac = np.arange(n) / max(n - 1, 1)
+    corrected = np.zeros(n, bool)
+    corrected[n - m:] = True
+    N = [moved(Gb[i], frac[i]) for i in range(n)]
+    if consistent:
+        est_b = [Gb[i] if corrected[i] or i == 0 else N[i] for i in range(n)]
+        base = [cam(b) for b in Gb]
+    else:
+        est_b = [moved(N[i], -1.0) if corrected[i] else N[i] for i in range(n)]
+        base = [cam(b) for b in N]
+    est_c = [cam(b) for b in est_b]
+    rows = []
+    for i in range(n):
+        Rcw, tcw = est_c[i]
+        if corrected[i]:
+            rows.append(imu_cam_pose_corrected(Rcw.T, -Rcw.T @ tcw, Rcb, tcb))
+        elif consistent:
+            rows.append(imu_cam_pose_row(est_b[i][0], est_b[i][1], Rcw, tcw, Rcb, tcb))
+        else:
+            rows.append(imu_cam_pose_keyframe(Rcw, tcw, Rcb, tcb))
+    rows = np.array(rows)
+    # the poses the reference's vScw holds: the corrected Sim3's camera or the KeyFrame's float pose
+    start = [(rows[i, 12:21].reshape(3, 3), rows[i, 21:24]) for i in range(n)]
+    loops = {}
+    for q in range(int(extra_loops)):
+        a = n // 2 + 3 * q + 1
+        b = n // 5 + 2 * q
+        if b < a - 3 and a < n - m:
+            loops.setdefault(a, []).append(b)
+    v0, v1, meas = [], [], []
+
+    def edge(i, j, src):
+        dR = src[i][0] @ src[j][0].T
+        dt = src[i][1] - dR @ src[j][1]
+        if not consistent:
+            w = rng.normal(size=3)
+            w *= np.deg2rad(meas_noise[0]) * rng.normal() / np.linalg.norm(w)
+            dR, dt = rodrigues(w) @ dR, dt + rng.normal(0, meas_noise[1], 3)
+        v0.append(i)
+        v1.append(j)
+        meas.append(np.concatenate([dR.ravel(), dt]))
+
+    loop_src = base if consistent else start
+    for k in range(n - m, n):
+        for j in (k - (n - m), k - (n - m) + 1):
+            if 0 <= j < n - m and j != k:
+                edge(k, j, loop_src)
+    for i in range(n):
+        if i >= 1:
+            edge(i, i - 1, base)
+        for b in loops.get(i, []):
+            edge(i, b, base)
+        for j in (i - 2, i - 3):
+            if j >= 0:
+                edge(i, j, base)
+    fixed = np.zeros(n, np.uint8)
+    fixed[0] = 1
+    truth = None
+    if consistent:
+        truth = np.array([imu_cam_pose_row(Gb[i][0], Gb[i][1], base[i][0], base[i][1], Rcb, tcb) for i in range(n)])
+    return EssentialGraph4DoFProblem(rows, fixed, np.array(v0, np.int32), np.array(v1, np.int32),
+                                     np.array(meas).reshape(-1, 12), truth=truth,
+                                     built=np.where(corrected, b"C", b"K" if not consistent else b"D"))
 
 
 def synth_lba_graph(rng, n_kf=50, n_points=10000, k_range=(2, 8), n_fixed=2, stereo_frac=0.0,
