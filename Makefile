@@ -21,13 +21,13 @@ endif
 ifdef MLPNP_PROF
 HIPFLAGS += -DOSG_MLPNP_PROF
 endif
-HDRS = include/osg.h include/osg_ba.h $(CSRC)/osg_internal.h
+HDRS = include/osg.h include/osg_ba.h include/osg_imu.h $(CSRC)/osg_internal.h
 # the RANSAC solvers' shared device helpers and host batch scaffolding
 RANSAC_HDRS = $(CSRC)/ransac_common.h $(CSRC)/batch_io.h $(CSRC)/glibc_math.h
 # the pointer-binding packer and the launch sequence of the entry points built on it
 PACKED_HDRS = $(CSRC)/match_common.h $(CSRC)/packed_launch.h
 
-OBJS = $(OBJDIR)/runtime.o $(OBJDIR)/hamming.o $(OBJDIR)/hamming_mfma.o $(OBJDIR)/match.o $(OBJDIR)/pose.o $(OBJDIR)/poseinertial.o $(OBJDIR)/sim3opt.o $(OBJDIR)/sim3ransac.o $(OBJDIR)/mlpnp.o $(OBJDIR)/twoview.o $(OBJDIR)/essgraph.o $(OBJDIR)/ba.o $(OBJDIR)/dbow.o $(OBJDIR)/kfdb.o $(OBJDIR)/fuse.o $(OBJDIR)/triang.o $(OBJDIR)/newpoints.o $(OBJDIR)/frustum.o $(OBJDIR)/desc.o $(OBJDIR)/sim3.o $(OBJDIR)/init.o $(OBJDIR)/stereo.o $(OBJDIR)/orb.o $(OBJDIR)/fast.o $(OBJDIR)/pyramid.o
+OBJS = $(OBJDIR)/runtime.o $(OBJDIR)/hamming.o $(OBJDIR)/hamming_mfma.o $(OBJDIR)/match.o $(OBJDIR)/pose.o $(OBJDIR)/poseinertial.o $(OBJDIR)/preintegrate.o $(OBJDIR)/sim3opt.o $(OBJDIR)/sim3ransac.o $(OBJDIR)/mlpnp.o $(OBJDIR)/twoview.o $(OBJDIR)/essgraph.o $(OBJDIR)/ba.o $(OBJDIR)/dbow.o $(OBJDIR)/kfdb.o $(OBJDIR)/fuse.o $(OBJDIR)/triang.o $(OBJDIR)/newpoints.o $(OBJDIR)/frustum.o $(OBJDIR)/desc.o $(OBJDIR)/sim3.o $(OBJDIR)/init.o $(OBJDIR)/stereo.o $(OBJDIR)/orb.o $(OBJDIR)/fast.o $(OBJDIR)/pyramid.o
 
 WALL_BENCH = tools/adapter_wall_bench
 
@@ -47,6 +47,8 @@ $(OBJDIR)/match.o: $(CSRC)/match.hip $(HDRS) $(CSRC)/match_common.h $(CSRC)/frus
 $(OBJDIR)/pose.o: $(CSRC)/pose.hip $(HDRS) $(CSRC)/ba_common.h $(CSRC)/exact_math.h $(CSRC)/glibc_math.h $(CSRC)/match_common.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
 $(OBJDIR)/poseinertial.o: $(CSRC)/poseinertial.hip $(HDRS) $(CSRC)/ba_common.h $(CSRC)/poseinertial_common.h $(CSRC)/so3_common.h $(CSRC)/exact_math.h $(RANSAC_HDRS) | $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
+$(OBJDIR)/preintegrate.o: $(CSRC)/preintegrate.hip $(HDRS) $(CSRC)/imu_common.h $(CSRC)/so3_common.h $(CSRC)/batch_io.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
 $(OBJDIR)/sim3opt.o: $(CSRC)/sim3opt.hip $(HDRS) $(CSRC)/ba_common.h $(CSRC)/sim3_common.h $(CSRC)/exact_math.h $(CSRC)/glibc_math.h $(CSRC)/batch_io.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
@@ -112,5 +114,5 @@ clean:
 
 # the C++ adapter wall-rate bench (bench.py's wall_cpp_adapter_frames_per_s): host code over the
 # library and the HIP runtime (device-resident pyramid levels for the stereo workload)
-$(WALL_BENCH): tools/adapter_wall_bench.cpp adapters/orbslam3/osg_orbslam3.h tests/adapter/driver_common.h tests/adapter/mock_orbslam3.h include/osg.h include/osg_ba.h include/osg_dbow.h $(LIB)
+$(WALL_BENCH): tools/adapter_wall_bench.cpp adapters/orbslam3/osg_orbslam3.h tests/adapter/driver_common.h tests/adapter/mock_orbslam3.h include/osg.h include/osg_ba.h include/osg_dbow.h include/osg_imu.h $(LIB)
 	g++ -std=c++17 -O2 -Wall -Werror -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude $< -o $@ -L$(PKG) -lorbslam3_amd -L/opt/rocm/lib -lamdhip64 '-Wl,-rpath,$$ORIGIN/../$(PKG)' -Wl,-rpath,/opt/rocm/lib -pthread

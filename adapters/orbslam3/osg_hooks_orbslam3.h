@@ -516,6 +516,79 @@ struct OsgHooks {
         return new ConstraintPoseImu(R, Eigen::Vector3d(s.twb[0], s.twb[1], s.twb[2]), Eigen::Vector3d(s.v[0], s.v[1], s.v[2]),
                                      Eigen::Vector3d(s.bg[0], s.bg[1], s.bg[2]), Eigen::Vector3d(s.ba[0], s.ba[1], s.ba[2]), Hm);
     }
+    // ---- IMU preintegration ("IMU preintegration"); IMU::Preintegrated names OsgHooks a friend
+    static void imu_point(const IMU::Point &m, float a[3], float w[3], double &t)
+    {
+        for (int k = 0; k < 3; k++) a[k] = m.a(k), w[k] = m.w(k);
+        t = m.t;
+    }
+    static void bias6(const IMU::Bias &b, float o[6])
+    {
+        o[0] = b.bax, o[1] = b.bay, o[2] = b.baz, o[3] = b.bwx, o[4] = b.bwy, o[5] = b.bwz;
+    }
+    static void frame_bias(Frame &F, float b[6]) { bias6(F.mImuBias, b); }
+    static IMU::Preintegrated *new_preintegrated(Frame &last, Frame &cur)
+    {
+        return new IMU::Preintegrated(last.mImuBias, cur.mImuCalib);
+    }
+    static void preint_get(IMU::Preintegrated *pInt, osg_imu_preintegrated &st, float nga[6], float walk[6], float bu[6])
+    {
+        preintegrated(pInt, st.pre);  // GetOriginalBias() takes mMutex itself, and so does GetUpdatedBias()
+        for (int k = 0; k < 3; k++) st.avgA[k] = pInt->avgA(k), st.avgW[k] = pInt->avgW(k);
+        for (int k = 0; k < 6; k++) nga[k] = pInt->Nga.diagonal()(k), walk[k] = pInt->NgaWalk.diagonal()(k);
+        bias6(pInt->GetUpdatedBias(), bu);
+    }
+    static void preint_measurements(IMU::Preintegrated *pInt, std::vector<float> &out)
+    {
+        std::unique_lock<std::mutex> lock(pInt->mMutex);
+        for (const auto &m : pInt->mvMeasurements) {
+            for (int k = 0; k < 3; k++) out.push_back(m.a(k));
+            for (int k = 0; k < 3; k++) out.push_back(m.w(k));
+            out.push_back(m.t);
+        }
+    }
+    // the integrated fields of a result, under the caller's lock
+    static void preint_fields(IMU::Preintegrated *pInt, const osg_imu_preintegrated &st)
+    {
+        using M3 = Eigen::Map<const Eigen::Matrix<float, 3, 3, Eigen::RowMajor>>;
+        const osg_pio_preintegrated &q = st.pre;
+        pInt->dR = M3(q.dR), pInt->JRg = M3(q.JRg), pInt->JVg = M3(q.JVg), pInt->JVa = M3(q.JVa);
+        pInt->JPg = M3(q.JPg), pInt->JPa = M3(q.JPa);
+        for (int k = 0; k < 3; k++) {
+            pInt->dV(k) = q.dV[k], pInt->dP(k) = q.dP[k];
+            pInt->avgA(k) = st.avgA[k], pInt->avgW(k) = st.avgW[k];
+        }
+        pInt->dT = q.dT;
+        pInt->C = Eigen::Map<const Eigen::Matrix<float, 15, 15, Eigen::RowMajor>>(q.C);
+    }
+    static void preint_append(IMU::Preintegrated *pInt, const float *meas, int n)
+    {
+        for (int i = 0; i < n; i++) {
+            const float *m = meas + 7 * i;
+            pInt->mvMeasurements.emplace_back(Eigen::Vector3f(m[0], m[1], m[2]), Eigen::Vector3f(m[3], m[4], m[5]), m[6]);
+        }
+    }
+    static void preint_continue(IMU::Preintegrated *pInt, const osg_imu_preintegrated &st, const float *meas, int n)
+    {
+        std::unique_lock<std::mutex> lock(pInt->mMutex);
+        preint_fields(pInt, st);
+        preint_append(pInt, meas, n);
+    }
+    static void preint_restart(IMU::Preintegrated *pInt, const osg_imu_preintegrated &st, const float *meas, int n)
+    {
+        std::unique_lock<std::mutex> lock(pInt->mMutex);
+        const std::vector<float> list(meas, meas + 7 * (size_t)n);
+        const float *b = st.pre.b;
+        pInt->Initialize(IMU::Bias(b[0], b[1], b[2], b[3], b[4], b[5]));
+        preint_fields(pInt, st);
+        preint_append(pInt, list.data(), n);
+    }
+    static void gyro_bias(KeyFrame &K, float g[3])
+    {
+        const Eigen::Vector3f v = K.GetGyroBias();
+        for (int k = 0; k < 3; k++) g[k] = v(k);
+    }
+    static void set_new_bias(KeyFrame &K, const float b[6]) { K.SetNewBias(IMU::Bias(b[0], b[1], b[2], b[3], b[4], b[5])); }
     // KeyFrameDatabase: the vocabulary on the device, set by System right after it loads ORBvoc
     // (osg_vocabulary_load_text) and before it constructs the database
     static const osg_vocabulary *&device_vocabulary()

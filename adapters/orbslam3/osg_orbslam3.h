@@ -34,6 +34,7 @@
 #include <cstdio>
 #include <cstring>
 #include <deque>
+#include <iostream>
 #include <list>
 #include <map>
 #include <memory>
@@ -50,6 +51,7 @@
 #include "osg.h"
 #include "osg_ba.h"
 #include "osg_dbow.h"
+#include "osg_imu.h"
 // the replay of Sim3Solver's sequential rule, shared with the library's selection launch
 #include "../../orb_slam3_comments_ghr_amd/csrc/sim3ransac_select.h"
 // the replay of MLPnPsolver's sequential rule and SetRansacParameters, likewise
@@ -4100,6 +4102,181 @@ int search_local_points(FrameT &F, const std::vector<MapPointT *> &vpLocalMapPoi
     g.write_back(vpLocalMapPoints, F.mmProjectPoints, Point2fT());
     if (g.res.n_to_match > 0) g.slots.apply(F.mvpMapPoints, vpLocalMapPoints, (int)vpLocalMapPoints.size());
     return nm;
+}
+
+// ------------------------------------------------- a20 IMU preintegration
+// IMU::Preintegrated::IntegrateNewMeasurement runs on the device through osg_imu_preintegrate_batch; the objects
+// stay the reference's (mvMeasurements a host vector on IMU::Preintegrated).  Hooks:
+//   H::imu_point(const Point&, float a[3], float w[3], double& t)       IMU::Point
+//   H::frame_bias(Frame&, float b[6])                                    mImuBias as (ba, bg)
+//   H::new_preintegrated(Frame& last, Frame& cur)                        new IMU::Preintegrated(last.mImuBias, cur.mImuCalib)
+//   H::preint_get(Preintegrated*, osg_imu_preintegrated&, float nga[6], float walk[6], float bu[6])
+//                the stored fields with avgA and avgW, the diagonals of Nga and NgaWalk, the updated bias
+//   H::preint_measurements(Preintegrated*, std::vector<float>&)          appends mvMeasurements, 7 floats per step
+//   H::preint_continue(Preintegrated*, const osg_imu_preintegrated&, const float* meas, int n)
+//                stores the fields and appends n steps to mvMeasurements (bu and db stay)
+//   H::preint_restart(Preintegrated*, const osg_imu_preintegrated&, const float* meas, int n)
+//                Initialize(b of the result), then the fields, mvMeasurements = the n steps
+//   H::gyro_bias(KeyFrame&, float bg[3]), H::set_new_bias(KeyFrame&, const float b[6])   GetGyroBias(), SetNewBias(b)
+template <class H, class PreintT>
+inline osg_imu_problem imu_problem_of(PreintT *p, osg_imu_preintegrated &state, float bu[6])
+{
+    osg_imu_problem q{};
+    H::preint_get(p, state, q.nga, q.nga_walk, bu);
+    return q;
+}
+
+// The first two steps of Tracking::PreintegrateIMU (ref:src/Tracking.cc:1771-1901), host only: the early returns,
+// the queue selection into mvImuFromLastFrame and the integrables of the frame, 7 floats per step in meas.
+// Returns the number of steps, or -1 where the reference returns before integrating (setIntegrated() called or
+// not as it does).
+template <class H, class TrackingT>
+int imu_frame_list(TrackingT &T, std::vector<float> &meas)
+{
+    auto &F = T.mCurrentFrame;
+    meas.clear();
+    if (!F.mpPrevFrame) {                                   // :1775-1780
+        F.setIntegrated();
+        return -1;
+    }
+    T.mvImuFromLastFrame.clear();
+    T.mvImuFromLastFrame.reserve(T.mlQueueImuData.size());
+    if (T.mlQueueImuData.size() == 0) {                     // :1785-1790
+        F.setIntegrated();
+        return -1;
+    }
+    {                                                       // :1792-1829
+        std::unique_lock<decltype(T.mMutexImuQueue)> lock(T.mMutexImuQueue);
+        std::vector<double> tq;
+        tq.reserve(T.mlQueueImuData.size());
+        for (const auto &m : T.mlQueueImuData) {
+            float a[3], w[3];
+            double t;
+            H::imu_point(m, a, w, t);
+            tq.push_back(t);
+        }
+        std::vector<int32_t> taken(tq.size());
+        int32_t popped = 0;
+        const int n_taken = osg_imu_select(tq.data(), (int32_t)tq.size(), F.mpPrevFrame->mTimeStamp, F.mTimeStamp,
+                                           T.mImuPer, taken.data(), &popped);
+        int at = 0, k = 0;
+        for (auto it = T.mlQueueImuData.begin(); it != T.mlQueueImuData.end() && k < n_taken; ++it, ++at)
+            if (at == taken[k]) {
+                T.mvImuFromLastFrame.push_back(*it);
+                k++;
+            }
+        for (int i = 0; i < popped; i++) T.mlQueueImuData.pop_front();
+    }
+    const int m = (int)T.mvImuFromLastFrame.size(), n = m - 1;
+    if (n == 0) {                                           // :1834-1838, without setIntegrated(), as written
+        std::cout << "Empty IMU measurements vector!!!\n";
+        return -1;
+    }
+    if (m == 0) return 0;                                   // every point was too old: the loop of :1851 runs zero times
+    std::vector<float> a(3 * (size_t)m), w(3 * (size_t)m);
+    std::vector<double> t(m);
+    for (int i = 0; i < m; i++) H::imu_point(T.mvImuFromLastFrame[i], &a[3 * i], &w[3 * i], t[i]);
+    meas.resize(7 * (size_t)n);
+    osg_imu_integrables(a.data(), w.data(), t.data(), m, F.mpPrevFrame->mTimeStamp, F.mTimeStamp, meas.data());
+    return n;
+}
+
+// Tracking::PreintegrateIMU (ref:src/Tracking.cc:1771-1918): imu_frame_list, one batch call of two problems over
+// the same list (the state continued from the last KeyFrame, a fresh one from the last frame's bias), the
+// hand-over.  Returns the steps integrated, or -1 where nothing was.
+template <class H, class TrackingT>
+int preintegrate_imu(TrackingT &T)
+{
+    auto &F = T.mCurrentFrame;
+    std::vector<float> meas;
+    const int n = imu_frame_list<H>(T, meas);
+    if (n < 0) return -1;
+    auto *pFrame = H::new_preintegrated(T.mLastFrame, F);   // :1841
+    if (n > 0 && !T.mpImuPreintegratedFromLastKF)           // :1904-1905, once instead of once per step
+        std::cout << "mpImuPreintegratedFromLastKF does not exist" << std::endl;
+    osg_imu_preintegrated from_kf{}, fresh{}, out[2];
+    float bu[6];
+    osg_imu_problem p[2] = {imu_problem_of<H>(T.mpImuPreintegratedFromLastKF, from_kf, bu),
+                            imu_problem_of<H>(pFrame, fresh, bu)};
+    p[0].meas = p[1].meas = meas.data();
+    p[0].n = p[1].n = n;
+    p[0].init = &from_kf;
+    H::frame_bias(T.mLastFrame, p[1].bias);
+    osg_ctx *ctx = thread_ctx();
+    if (call(ctx, "osg_imu_preintegrate_batch", [&] { return osg_imu_preintegrate_batch(ctx, p, 2, out); }) < 0) {
+        delete pFrame;
+        return -1;
+    }
+    H::preint_continue(T.mpImuPreintegratedFromLastKF, out[0], meas.data(), n);   // :1906
+    H::preint_restart(pFrame, out[1], meas.data(), n);                            // :1907
+    F.mpImuPreintegratedFrame = pFrame;                     // :1911-1915
+    F.mpImuPreintegrated = T.mpImuPreintegratedFromLastKF;
+    F.mpLastKeyFrame = T.mpLastKeyFrame;
+    F.setIntegrated();
+    return n;
+}
+
+// The write-back loops of Optimizer::InertialOptimization (ref:src/Optimizer.cc:3879-3897, 4057-4075) after the
+// caller's SetVelocity.  keyframes_to_reintegrate gives every KeyFrame SetNewBias(b) and returns the
+// preintegrations of those whose gyro bias moved by more than 0.01; reintegrate_keyframes reintegrates them all in
+// one batch call and returns how many there were.  b is (ba, bg).
+template <class H, class KeyFrameT>
+auto keyframes_to_reintegrate(const std::vector<KeyFrameT *> &vpKFs, const float b[6])
+{
+    std::vector<decltype(vpKFs[0]->mpImuPreintegrated)> todo;
+    for (KeyFrameT *pKFi : vpKFs) {
+        float g[3];
+        H::gyro_bias(*pKFi, g);
+        const float dx = g[0] - b[3], dy = g[1] - b[4], dz = g[2] - b[5];
+        const bool moved = std::sqrt(dx * dx + dy * dy + dz * dz) > 0.01;   // a float norm against the double 0.01
+        H::set_new_bias(*pKFi, b);
+        if (moved && pKFi->mpImuPreintegrated) todo.push_back(pKFi->mpImuPreintegrated);
+    }
+    return todo;
+}
+
+template <class H, class KeyFrameT>
+int reintegrate_keyframes(const std::vector<KeyFrameT *> &vpKFs, const float b[6])
+{
+    const auto todo = keyframes_to_reintegrate<H>(vpKFs, b);
+    if (todo.empty()) return 0;
+    const size_t nb = todo.size();
+    std::vector<std::vector<float>> lists(nb);
+    std::vector<osg_imu_problem> p(nb);
+    std::vector<osg_imu_preintegrated> out(nb);
+    for (size_t i = 0; i < nb; i++) {                       // Reintegrate(): Initialize(bu) plus the whole list
+        osg_imu_preintegrated unused{};
+        p[i] = osg_imu_problem{};
+        H::preint_get(todo[i], unused, p[i].nga, p[i].nga_walk, p[i].bias);
+        H::preint_measurements(todo[i], lists[i]);
+        p[i].meas = lists[i].data();
+        p[i].n = (int32_t)(lists[i].size() / 7);
+    }
+    osg_ctx *ctx = thread_ctx();
+    if (call(ctx, "osg_imu_preintegrate_batch",
+             [&] { return osg_imu_preintegrate_batch(ctx, p.data(), (int32_t)nb, out.data()); }) < 0)
+        return 0;
+    for (size_t i = 0; i < nb; i++) H::preint_restart(todo[i], out[i], lists[i].data(), p[i].n);
+    return (int)nb;
+}
+
+// IMU::Preintegrated::MergePrevious (ref:src/ImuTypes.cc:329-352) for LocalMapping::KeyFrameCulling
+// (ref:src/LocalMapping.cc:1358, 1368): Initialize(bu) plus pPrev's list followed by the own one.
+template <class H, class PreintT>
+void merge_previous(PreintT *self, PreintT *pPrev)
+{
+    if (pPrev == self) return;
+    osg_imu_preintegrated unused{}, out{};
+    osg_imu_problem p{};
+    H::preint_get(self, unused, p.nga, p.nga_walk, p.bias);
+    std::vector<float> list;
+    H::preint_measurements(pPrev, list);
+    H::preint_measurements(self, list);
+    p.meas = list.data();
+    p.n = (int32_t)(list.size() / 7);
+    osg_ctx *ctx = thread_ctx();
+    if (call(ctx, "osg_imu_preintegrate", [&] { return osg_imu_preintegrate(ctx, &p, &out); }) < 0) return;
+    H::preint_restart(self, out, list.data(), p.n);
 }
 
 }  // namespace osg_orbslam3

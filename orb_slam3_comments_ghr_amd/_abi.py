@@ -213,6 +213,18 @@ class OsgPioPreintegrated(C.Structure):
     ]
 
 
+class OsgImuPreintegrated(C.Structure):
+    _fields_ = [("pre", OsgPioPreintegrated), ("avgA", f32 * 3), ("avgW", f32 * 3)]
+
+
+class OsgImuProblem(C.Structure):
+    _fields_ = [("meas", P), ("n", i32), ("bias", f32 * 6), ("nga", f32 * 6), ("nga_walk", f32 * 6), ("init", P)]
+
+
+OSG_IMU_MAX_STEPS = 65536
+OSG_IMU_MAX_BATCH_STEPS = 1 << 24
+
+
 class OsgPioPrior(C.Structure):
     _fields_ = [("Rwb", f64 * 9), ("twb", f64 * 3), ("vwb", f64 * 3), ("bg", f64 * 3), ("ba", f64 * 3),
                 ("H", f64 * 225)]
@@ -420,6 +432,12 @@ EXPORTS = [
     "osg_debug_distribute_oct_tree", "osg_orb_pyramid_layout", "osg_orb_pyramid", "osg_debug_gaussian_kernel7",
 ]
 
+# Every symbol include/osg_imu.h declares (checked by tests/test_preintegration_abi.py).
+IMU_EXPORTS = [
+    "osg_imu_preintegrate", "osg_imu_preintegrate_batch", "osg_imu_preintegrate_check",
+    "osg_imu_select", "osg_imu_integrables", "osg_imu_delta", "osg_imu_predict_state",
+]
+
 
 def declare(lib: C.CDLL) -> C.CDLL:
     """Attach argtypes/restypes for the product library."""
@@ -474,6 +492,15 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.osg_pose_inertial_check.argtypes = [C.POINTER(OsgPoseInertialProblem)]
     lib.osg_pose_inertial_informations.argtypes = [vp, vp, vp, vp, vp]
     lib.osg_pose_inertial_informations.restype = None
+    lib.osg_imu_preintegrate.argtypes = [vp, C.POINTER(OsgImuProblem), C.POINTER(OsgImuPreintegrated)]
+    lib.osg_imu_preintegrate_batch.argtypes = [vp, C.POINTER(OsgImuProblem), i32, C.POINTER(OsgImuPreintegrated)]
+    lib.osg_imu_preintegrate_check.argtypes = [C.POINTER(OsgImuProblem)]
+    lib.osg_imu_select.argtypes = [vp, i32, C.c_double, C.c_double, C.c_double, vp, vp]
+    lib.osg_imu_integrables.argtypes = [vp, vp, vp, i32, C.c_double, C.c_double, vp]
+    lib.osg_imu_delta.argtypes = [C.POINTER(OsgImuPreintegrated), vp, vp, vp, vp]
+    lib.osg_imu_delta.restype = None
+    lib.osg_imu_predict_state.argtypes = [C.POINTER(OsgImuPreintegrated), vp, vp, vp, vp, vp, vp, vp]
+    lib.osg_imu_predict_state.restype = None
     lib.osg_optimize_sim3.argtypes = [vp, C.POINTER(OsgSim3Problem), C.POINTER(OsgSim3Result)]
     lib.osg_optimize_sim3_batch.argtypes = [vp, C.POINTER(OsgSim3Problem), i32, C.POINTER(OsgSim3Result)]
     lib.osg_sim3_ransac.argtypes = [vp, C.POINTER(OsgSim3RansacProblem), C.POINTER(OsgSim3RansacResult)]
