@@ -22,8 +22,11 @@ ifdef MLPNP_PROF
 HIPFLAGS += -DOSG_MLPNP_PROF
 endif
 HDRS = include/osg.h include/osg_ba.h include/osg_imu.h $(CSRC)/osg_internal.h
+# the small dense routines (host and device) and the SO(3) functions built on them
+LINALG_HDRS = $(CSRC)/small_linalg.h $(CSRC)/osg_hd.h
+SO3_HDRS = $(CSRC)/so3_common.h $(LINALG_HDRS)
 # the RANSAC solvers' shared device helpers and host batch scaffolding
-RANSAC_HDRS = $(CSRC)/ransac_common.h $(CSRC)/batch_io.h $(CSRC)/glibc_math.h
+RANSAC_HDRS = $(CSRC)/ransac_common.h $(CSRC)/batch_io.h $(CSRC)/glibc_math.h $(LINALG_HDRS)
 # the pointer-binding packer and the launch sequence of the entry points built on it
 PACKED_HDRS = $(CSRC)/match_common.h $(CSRC)/packed_launch.h
 
@@ -44,13 +47,13 @@ $(OBJDIR)/hamming_mfma.o: $(CSRC)/hamming_mfma.hip $(HDRS) $(CSRC)/top2_key.h $(
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 $(OBJDIR)/match.o: $(CSRC)/match.hip $(HDRS) $(CSRC)/match_common.h $(CSRC)/frustum_common.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
-$(OBJDIR)/pose.o: $(CSRC)/pose.hip $(HDRS) $(CSRC)/ba_common.h $(CSRC)/exact_math.h $(CSRC)/glibc_math.h $(CSRC)/match_common.h | $(OBJDIR)
+$(OBJDIR)/pose.o: $(CSRC)/pose.hip $(HDRS) $(CSRC)/ba_common.h $(CSRC)/exact_math.h $(CSRC)/glibc_math.h $(CSRC)/match_common.h $(LINALG_HDRS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
-$(OBJDIR)/poseinertial.o: $(CSRC)/poseinertial.hip $(HDRS) $(CSRC)/ba_common.h $(CSRC)/poseinertial_common.h $(CSRC)/so3_common.h $(CSRC)/exact_math.h $(RANSAC_HDRS) | $(OBJDIR)
+$(OBJDIR)/poseinertial.o: $(CSRC)/poseinertial.hip $(HDRS) $(CSRC)/ba_common.h $(CSRC)/poseinertial_common.h $(SO3_HDRS) $(CSRC)/exact_math.h $(RANSAC_HDRS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
-$(OBJDIR)/preintegrate.o: $(CSRC)/preintegrate.hip $(HDRS) $(CSRC)/imu_common.h $(CSRC)/so3_common.h $(CSRC)/batch_io.h | $(OBJDIR)
+$(OBJDIR)/preintegrate.o: $(CSRC)/preintegrate.hip $(HDRS) $(CSRC)/imu_common.h $(SO3_HDRS) $(CSRC)/batch_io.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
-$(OBJDIR)/sim3opt.o: $(CSRC)/sim3opt.hip $(HDRS) $(CSRC)/ba_common.h $(CSRC)/sim3_common.h $(CSRC)/exact_math.h $(CSRC)/glibc_math.h $(CSRC)/batch_io.h | $(OBJDIR)
+$(OBJDIR)/sim3opt.o: $(CSRC)/sim3opt.hip $(HDRS) $(CSRC)/ba_common.h $(CSRC)/sim3_common.h $(CSRC)/exact_math.h $(CSRC)/glibc_math.h $(CSRC)/batch_io.h $(LINALG_HDRS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
 $(OBJDIR)/sim3ransac.o: $(CSRC)/sim3ransac.hip $(HDRS) $(CSRC)/sim3ransac_select.h $(RANSAC_HDRS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
@@ -58,9 +61,9 @@ $(OBJDIR)/mlpnp.o: $(CSRC)/mlpnp.hip $(HDRS) $(CSRC)/mlpnp_select.h $(RANSAC_HDR
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
 $(OBJDIR)/twoview.o: $(CSRC)/twoview.hip $(HDRS) $(CSRC)/twoview_select.h $(RANSAC_HDRS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
-$(OBJDIR)/essgraph.o: $(CSRC)/essgraph.hip $(HDRS) $(CSRC)/sim3_common.h $(CSRC)/exact_math.h $(CSRC)/essgraph4_common.h $(CSRC)/so3_common.h | $(OBJDIR)
+$(OBJDIR)/essgraph.o: $(CSRC)/essgraph.hip $(HDRS) $(CSRC)/sim3_common.h $(CSRC)/exact_math.h $(CSRC)/essgraph4_common.h $(SO3_HDRS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
-$(OBJDIR)/ba.o: $(CSRC)/ba.hip $(HDRS) $(CSRC)/ba_common.h $(CSRC)/exact_math.h $(CSRC)/glibc_math.h $(CSRC)/match_common.h | $(OBJDIR)
+$(OBJDIR)/ba.o: $(CSRC)/ba.hip $(HDRS) $(CSRC)/ba_common.h $(CSRC)/exact_math.h $(CSRC)/glibc_math.h $(CSRC)/match_common.h $(CSRC)/osg_hd.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 $(OBJDIR)/dbow.o: $(CSRC)/dbow.hip $(HDRS) include/osg_dbow.h $(CSRC)/match_common.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@

@@ -16,11 +16,7 @@
 #pragma once
 #include <cmath>
 
-#ifdef __HIPCC__
-#define OSG_HD __host__ __device__
-#else
-#define OSG_HD
-#endif
+#include "osg_hd.h"
 // no contraction inside the error-free transforms, whatever the translation unit's flags
 #ifdef __clang__
 #define OSGX_NOCONTRACT _Pragma("clang fp contract(off)")

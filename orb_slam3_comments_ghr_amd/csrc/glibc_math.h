@@ -16,11 +16,7 @@
 #include <cstdint>
 #include <cstring>
 
-#ifdef __HIPCC__
-#define OSG_GM_HD __host__ __device__
-#else
-#define OSG_GM_HD
-#endif
+#include "osg_hd.h"
 #ifdef __clang__
 #define OSG_GM_NOCONTRACT _Pragma("clang fp contract(off)")
 #else
@@ -29,13 +25,13 @@
 
 namespace osgm {
 
-OSG_GM_HD inline int32_t f2i(float x)
+OSG_HD inline int32_t f2i(float x)
 {
     int32_t i;
     __builtin_memcpy(&i, &x, 4);
     return i;
 }
-OSG_GM_HD inline float i2f(int32_t i)
+OSG_HD inline float i2f(int32_t i)
 {
     float x;
     __builtin_memcpy(&x, &i, 4);
@@ -46,7 +42,7 @@ OSG_GM_HD inline float i2f(int32_t i)
 // the numerator / denominator of its interval's reduction with the same float operations and
 // divides once (x / 1 = x exactly on the |x| < 0.4375 path), so a wave whose lanes fall into
 // different intervals runs one division, not one per interval.
-OSG_GM_HD inline float atanf_fd(float x)
+OSG_HD inline float atanf_fd(float x)
 {
     OSG_GM_NOCONTRACT
     const float aT0 = 3.3333334327e-01f, aT1 = -2.0000000298e-01f, aT2 = 1.4285714924e-01f,
@@ -82,7 +78,7 @@ OSG_GM_HD inline float atanf_fd(float x)
 }
 
 // fdlibm float atan2f (e_atan2f.c)
-OSG_GM_HD inline float atan2f_fd(float y, float x)
+OSG_HD inline float atan2f_fd(float y, float x)
 {
     OSG_GM_NOCONTRACT
     const float tiny = 1.0e-30f, pi_o_4 = 7.8539818525e-01f, pi_o_2 = 1.5707963705e+00f, pi = 3.1415927410e+00f,

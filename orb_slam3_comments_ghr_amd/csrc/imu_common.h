@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "../../include/osg_imu.h"
+#include "so3_common.h"
 
 namespace osgimu {
 
@@ -116,105 +117,11 @@ inline int integrables(const float *a, const float *w, const double *t, int32_t 
     return n;
 }
 
-inline void m3_mul(const float *A, const float *B, float *C)
-{
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) {
-            float s = A[3 * i] * B[j];
-            s += A[3 * i + 1] * B[3 + j];
-            s += A[3 * i + 2] * B[6 + j];
-            C[3 * i + j] = s;
-        }
-}
-inline void m3_vec(const float *A, const float *x, float *y)
-{
-    for (int i = 0; i < 3; i++) {
-        float s = A[3 * i] * x[0];
-        s += A[3 * i + 1] * x[1];
-        s += A[3 * i + 2] * x[2];
-        y[i] = s;
-    }
-}
-
-// IMU::NormalizeRotation as the polar factor R (R'R)^(-1/2), R'R diagonalised by cyclic Jacobi: the host
-// twin of osgso3::normalize_rotation<float>
-inline void normalize_rotation(float *R)
-{
-    float B[3][3], V[3][3];
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) {
-            float s = R[i] * R[j];
-            s += R[3 + i] * R[3 + j];
-            s += R[6 + i] * R[6 + j];
-            B[i][j] = s;
-            V[i][j] = i == j ? 1.f : 0.f;
-        }
-    for (int sweep = 0; sweep < 12; sweep++) {
-        const float off = B[0][1] * B[0][1] + B[0][2] * B[0][2] + B[1][2] * B[1][2];
-        const float diag = B[0][0] * B[0][0] + B[1][1] * B[1][1] + B[2][2] * B[2][2];
-        if (!(off > 1e-16f * diag)) break;
-        for (int p = 0; p < 2; p++)
-            for (int q = p + 1; q < 3; q++) {
-                const float apq = B[p][q];
-                if (apq == 0.f) continue;
-                const float th = (B[q][q] - B[p][p]) / (2.f * apq);
-                const float tt = (th >= 0.f ? 1.f : -1.f) / (std::fabs(th) + std::sqrt(th * th + 1.f));
-                const float c = 1.f / std::sqrt(tt * tt + 1.f), s = tt * c;
-                for (int k = 0; k < 3; k++) {
-                    const float akp = B[k][p], akq = B[k][q];
-                    B[k][p] = c * akp - s * akq;
-                    B[k][q] = s * akp + c * akq;
-                }
-                for (int k = 0; k < 3; k++) {
-                    const float apk = B[p][k], aqk = B[q][k];
-                    B[p][k] = c * apk - s * aqk;
-                    B[q][k] = s * apk + c * aqk;
-                }
-                for (int k = 0; k < 3; k++) {
-                    const float vkp = V[k][p], vkq = V[k][q];
-                    V[k][p] = c * vkp - s * vkq;
-                    V[k][q] = s * vkp + c * vkq;
-                }
-            }
-    }
-    float isq[3], M[9], O[9];
-    for (int k = 0; k < 3; k++) isq[k] = 1.f / std::sqrt(B[k][k]);
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) {
-            float s = V[i][0] * isq[0] * V[j][0];
-            s += V[i][1] * isq[1] * V[j][1];
-            s += V[i][2] * isq[2] * V[j][2];
-            M[3 * i + j] = s;
-        }
-    m3_mul(R, M, O);
-    for (int i = 0; i < 9; i++) R[i] = O[i];
-}
-
-// Sophus::SO3f::exp(w).matrix(): the unit quaternion of the half angle (Taylor below theta^2 < 1e-10), then
-// Eigen's toRotationMatrix; the host twin of so3f_exp_matrix in poseinertial.hip
-inline void so3f_exp_matrix(const float *w, float *R)
-{
-    const float theta_sq = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-    float imag, real;
-    if (theta_sq < 1e-5f * 1e-5f) {
-        const float theta_po4 = theta_sq * theta_sq;
-        imag = 0.5f - (1.0f / 48.0f) * theta_sq + (1.0f / 3840.0f) * theta_po4;
-        real = 1.0f - (1.0f / 8.0f) * theta_sq + (1.0f / 384.0f) * theta_po4;
-    } else {
-        const float theta = std::sqrt(theta_sq);
-        const float half = 0.5f * theta;
-        imag = std::sin(half) / theta;
-        real = std::cos(half);
-    }
-    const float x = imag * w[0], y = imag * w[1], z = imag * w[2], qw = real;
-    const float tx = 2 * x, ty = 2 * y, tz = 2 * z;
-    const float twx = tx * qw, twy = ty * qw, twz = tz * qw;
-    const float txx = tx * x, txy = ty * x, txz = tz * x;
-    const float tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    R[0] = 1 - (tyy + tzz), R[1] = txy - twz, R[2] = txz + twy;
-    R[3] = txy + twz, R[4] = 1 - (txx + tzz), R[5] = tyz - twx;
-    R[6] = txz - twy, R[7] = tyz + twx, R[8] = 1 - (txx + tyy);
-}
+// the bias-corrected deltas and PredictStateIMU, on the SO(3) functions the kernels run (so3_common.h)
+using osgla::m3_mul;
+using osgla::m3_vec;
+using osgso3::normalize_rotation;
+using osgso3::so3f_exp_matrix;
 
 inline void delta(const osg_imu_preintegrated *s, const float *bias, float *dR, float *dV, float *dP)
 {
@@ -229,7 +136,7 @@ inline void delta(const osg_imu_preintegrated *s, const float *bias, float *dR, 
         m3_vec(q.JRg, dbg, w);
         so3f_exp_matrix(w, E);
         m3_mul(q.dR, E, dR);
-        normalize_rotation(dR);
+        normalize_rotation<float>(dR);
     }
     float t1[3], t2[3];
     if (dV) {
@@ -252,7 +159,7 @@ inline void predict_state(const osg_imu_preintegrated *s, const float *bias, con
     float dR[9], dV[3], dP[3], r[3];
     delta(s, bias, dR, dV, dP);
     m3_mul(Rwb1, dR, Rwb2);
-    normalize_rotation(Rwb2);
+    normalize_rotation<float>(Rwb2);
     m3_vec(Rwb1, dP, r);
     for (int i = 0; i < 3; i++) twb2[i] = ((twb1[i] + vwb1[i] * t12) + ((0.5f * t12) * t12) * Gz[i]) + r[i];
     m3_vec(Rwb1, dV, r);

@@ -150,7 +150,7 @@ __device__ inline void eig3_ascending(const double *S, double *G /* columns = ei
 {
     double A[3][3] = {{S[0], S[1], S[2]}, {S[3], S[4], S[5]}, {S[6], S[7], S[8]}};
     double V[3][3];
-    jacobi_sym<3>(A, V, 16, 1e-40);
+    jacobi_sym<double, 3>(A, V, 16, 1e-40);
     // ascending order of the three diagonal entries
     int o0 = 0, o1 = 1, o2 = 2;
     double d0 = A[0][0], d1 = A[1][1], d2 = A[2][2];

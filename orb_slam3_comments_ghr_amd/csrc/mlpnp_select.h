@@ -16,11 +16,7 @@
 
 #include <cmath>
 
-#if defined(__HIPCC__)
-#define OSG_MLPNP_HD __host__ __device__
-#else
-#define OSG_MLPNP_HD
-#endif
+#include "osg_hd.h"
 
 struct osg_mlpnp_window {
     int32_t converged;     // counts[hyp] > min_inliers ended the window (bNoMore stays false)
@@ -31,7 +27,7 @@ struct osg_mlpnp_window {
 };
 
 // the iterations one iterate(n_iterations) consumes when entered at mnIterations = it and not ended early
-OSG_MLPNP_HD inline int32_t osg_mlpnp_window_length(int32_t it, int32_t max_its, int32_t n_iterations)
+OSG_HD inline int32_t osg_mlpnp_window_length(int32_t it, int32_t max_its, int32_t n_iterations)
 {
     const int32_t a = max_its - it;
     return a > n_iterations ? a : n_iterations;
@@ -39,7 +35,7 @@ OSG_MLPNP_HD inline int32_t osg_mlpnp_window_length(int32_t it, int32_t max_its,
 
 // counts[first .. first + len): inlier counts in draw order; n_best / best_hyp: mnBestInliers and its slot
 // as the previous call left them (0, -1 on a fresh solver).
-OSG_MLPNP_HD inline osg_mlpnp_window osg_mlpnp_replay(const int32_t *counts, int32_t min_inliers, int32_t first,
+OSG_HD inline osg_mlpnp_window osg_mlpnp_replay(const int32_t *counts, int32_t min_inliers, int32_t first,
                                                       int32_t len, int32_t n_best, int32_t best_hyp)
 {
     osg_mlpnp_window w;

@@ -178,7 +178,7 @@ __global__ __launch_bounds__(NT) void k_np_eval(const NpArgs A)
                     for (int c = 0; c < 4; c++)
                         G[a][c] = (double)M[0][a] * M[0][c] + (double)M[1][a] * M[1][c] + (double)M[2][a] * M[2][c] +
                                   (double)M[3][a] * M[3][c];
-                jacobi_sym<4>(G, E, NP_SWEEPS, NP_TOL);
+                jacobi_sym<double, 4>(G, E, NP_SWEEPS, NP_TOL);
                 int m = 0;
                 double lm = G[0][0];
 #pragma unroll

@@ -33,6 +33,7 @@
 #include "ba_common.h"
 #include "exact_math.h"
 #include "match_common.h"
+#include "small_linalg.h"
 
 using namespace osgba;
 
@@ -73,46 +74,6 @@ __device__ inline double readlane_d(double v, int l)
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
     const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
     return __hiloint2double(hi, lo);
-}
-
-// unpivoted LDL^T of the damped 6x6 system, the oracle's ldlt_solve (require_positive)
-__device__ inline bool ldlt6(double A[6][6], const double *b, double *x)
-{
-#pragma unroll
-    for (int j = 0; j < 6; j++) {
-        double d = A[j][j];
-#pragma unroll
-        for (int k = 0; k < j; k++) d -= A[j][k] * A[j][k] * A[k][k];
-        if (!(d > 0.0)) return false;
-        A[j][j] = d;
-#pragma unroll
-        for (int i = j + 1; i < 6; i++) {
-            double s = A[i][j];
-#pragma unroll
-            for (int k = 0; k < j; k++) s -= A[i][k] * A[j][k] * A[k][k];
-            A[i][j] = s / d;
-        }
-    }
-    double y[6];
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-        double s = b[i];
-#pragma unroll
-        for (int k = 0; k < i; k++) s -= A[i][k] * y[k];
-        y[i] = s;
-    }
-#pragma unroll
-    for (int i = 0; i < 6; i++) y[i] /= A[i][i];
-#pragma unroll
-    for (int i = 5; i >= 0; i--) {
-        double s = y[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; k++) s -= A[k][i] * y[k];
-        y[i] = s;
-    }
-#pragma unroll
-    for (int i = 0; i < 6; i++) x[i] = y[i];
-    return true;
 }
 
 // one edge of the frame, as read from the packed arrays
@@ -581,7 +542,7 @@ __global__ __launch_bounds__(NW *PW) void k_pose_opt(const PoseProbDev *__restri
                             for (int i = 0; i < 6; i++) bvec[i] = sys[21 + i];
                         }
                         double x[6];
-                        okw = ldlt6(A, bvec, x);
+                        okw = osgla::ldlt_solve<6>(A, bvec, x);
                         if (okw)
 #pragma unroll
                             for (int i = 0; i < 6; i++) xs[i] = x[i];

@@ -58,67 +58,6 @@ struct PioShared {
     int ok;
 };
 
-// ref:src/G2oTypes.cc:951-962
-__device__ inline void inv_right_jacobian_so3(const double *v, double *J)
-{
-    const double d2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
-    const double d = sqrt(d2);
-    double W[9], W2[9];
-    hat3(v, W);
-    m3_mul(W, W, W2);
-    if (d < 1e-5) {
-#pragma unroll
-        for (int i = 0; i < 9; i++) J[i] = (i % 4 == 0) ? 1.0 : 0.0;
-    } else {
-        const double f = 1.0 / d2 - (1.0 + cos(d)) / (2.0 * d * sin(d));
-#pragma unroll
-        for (int i = 0; i < 9; i++) J[i] = ((i % 4 == 0) ? 1.0 : 0.0) + W[i] / 2 + W2[i] * f;
-    }
-}
-// ref:src/G2oTypes.cc:969-984
-__device__ inline void right_jacobian_so3(const double *v, double *J)
-{
-    const double d2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
-    const double d = sqrt(d2);
-    double W[9], W2[9];
-    hat3(v, W);
-    m3_mul(W, W, W2);
-    if (d < 1e-5) {
-#pragma unroll
-        for (int i = 0; i < 9; i++) J[i] = (i % 4 == 0) ? 1.0 : 0.0;
-    } else {
-        const double sd = sin(d), cd = cos(d);
-#pragma unroll
-        for (int i = 0; i < 9; i++) J[i] = ((i % 4 == 0) ? 1.0 : 0.0) - W[i] * (1.0 - cd) / d2 + W2[i] * (d - sd) / (d2 * d);
-    }
-}
-
-// Sophus::SO3f::exp(w).matrix(): the unit quaternion (cos(theta / 2), sin(theta / 2) w / theta), Taylor below
-// theta^2 < 1e-10, then Eigen's toRotationMatrix
-__device__ inline void so3f_exp_matrix(const float *w, float *R)
-{
-    const float theta_sq = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-    float imag, real;
-    if (theta_sq < 1e-5f * 1e-5f) {
-        const float theta_po4 = theta_sq * theta_sq;
-        imag = 0.5f - (1.0f / 48.0f) * theta_sq + (1.0f / 3840.0f) * theta_po4;
-        real = 1.0f - (1.0f / 8.0f) * theta_sq + (1.0f / 384.0f) * theta_po4;
-    } else {
-        const float theta = sqrtf(theta_sq);
-        const float half = 0.5f * theta;
-        imag = sinf(half) / theta;
-        real = cosf(half);
-    }
-    const float x = imag * w[0], y = imag * w[1], z = imag * w[2], qw = real;
-    const float tx = 2 * x, ty = 2 * y, tz = 2 * z;
-    const float twx = tx * qw, twy = ty * qw, twz = tz * qw;
-    const float txx = tx * x, txy = ty * x, txz = tz * x;
-    const float tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    R[0] = 1 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
-    R[3] = txy + twz; R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1 - (txx + tyy);
-}
-
 // ImuCamPose::Update (ref:src/G2oTypes.cc:221-249) on vertex k; the cameras belong to the current frame
 __device__ inline void pose_update(PioShared &S, const ProbDev &P, int k, const double *pu)
 {

@@ -8,6 +8,7 @@
 
 #include "../../include/osg.h"
 #include "../../include/osg_ba.h"
+#include "small_linalg.h"
 
 namespace osgpio {
 
@@ -94,61 +95,22 @@ inline void inverse(const double *A, double *inv)
         for (int j = 0; j < N; j++) inv[i * N + j] = M[i][N + j];
 }
 
-// cyclic Jacobi on the symmetric n x n row-major A: A -> diagonal, V -> eigenvectors in columns
-template <int N>
-inline void jacobi_host(double *A, double *V)
-{
-    for (int i = 0; i < N; i++)
-        for (int j = 0; j < N; j++) V[i * N + j] = i == j ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 60; sweep++) {
-        double off = 0, diag = 0;
-        for (int i = 0; i < N; i++) {
-            diag += A[i * N + i] * A[i * N + i];
-            for (int j = i + 1; j < N; j++) off += A[i * N + j] * A[i * N + j];
-        }
-        if (!(off > 1e-36 * diag)) break;
-        for (int p = 0; p < N - 1; p++)
-            for (int q = p + 1; q < N; q++) {
-                const double apq = A[p * N + q];
-                if (apq == 0.0) continue;
-                const double th = (A[q * N + q] - A[p * N + p]) / (2.0 * apq);
-                const double tt = (th >= 0 ? 1.0 : -1.0) / (std::fabs(th) + std::sqrt(th * th + 1.0));
-                const double c = 1.0 / std::sqrt(tt * tt + 1.0), s = tt * c;
-                for (int k = 0; k < N; k++) {
-                    const double akp = A[k * N + p], akq = A[k * N + q];
-                    A[k * N + p] = c * akp - s * akq;
-                    A[k * N + q] = s * akp + c * akq;
-                }
-                for (int k = 0; k < N; k++) {
-                    const double apk = A[p * N + k], aqk = A[q * N + k];
-                    A[p * N + k] = c * apk - s * aqk;
-                    A[q * N + k] = s * apk + c * aqk;
-                }
-                for (int k = 0; k < N; k++) {
-                    const double vkp = V[k * N + p], vkq = V[k * N + q];
-                    V[k * N + p] = c * vkp - s * vkq;
-                    V[k * N + q] = s * vkp + c * vkq;
-                }
-            }
-    }
-}
-
 inline void informations(const float *C, const float *C_rw, double *info9, double *info_g, double *info_a)
 {
     if (info9 && C) {
-        double A[81], inv[81], S[81], V[81];
+        double A[81], inv[81], S[9][9], V[9][9];
         for (int i = 0; i < 9; i++)
             for (int j = 0; j < 9; j++) A[i * 9 + j] = (double)C[i * 15 + j];
         inverse<9>(A, inv);
         for (int i = 0; i < 9; i++)
-            for (int j = 0; j < 9; j++) S[i * 9 + j] = (inv[i * 9 + j] + inv[j * 9 + i]) / 2;
-        jacobi_host<9>(S, V);
+            for (int j = 0; j < 9; j++) S[i][j] = (inv[i * 9 + j] + inv[j * 9 + i]) / 2;
+        osgla::jacobi_sym<double, 9>(S, V, 60, 1e-36);
         double eig[9];
-        for (int i = 0; i < 9; i++) eig[i] = S[i * 9 + i] < 1e-12 ? 0.0 : S[i * 9 + i];
+        for (int i = 0; i < 9; i++) eig[i] = S[i][i] < 1e-12 ? 0.0 : S[i][i];
         for (int i = 0; i < 9; i++)
             for (int j = 0; j < 9; j++) {
                 double s = 0;
-                for (int k = 0; k < 9; k++) s += V[i * 9 + k] * eig[k] * V[j * 9 + k];
+                for (int k = 0; k < 9; k++) s += V[i][k] * eig[k] * V[j][k];
                 info9[i * 9 + j] = s;
             }
     }

@@ -50,13 +50,6 @@ __device__ __forceinline__ void wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-__device__ __forceinline__ void hat3f(const float *w, float *W)
-{
-    W[0] = 0.f; W[1] = -w[2]; W[2] = w[1];
-    W[3] = w[2]; W[4] = 0.f; W[5] = -w[0];
-    W[6] = -w[1]; W[7] = w[0]; W[8] = 0.f;
-}
-
 // ref:src/ImuTypes.cc:264-305, 318-322 on the registers of one lane; M receives the blocks of A and B
 __device__ __forceinline__ void chain_step(Chain &s, const float *m, float *M)
 {
@@ -86,7 +79,7 @@ __device__ __forceinline__ void chain_step(Chain &s, const float *m, float *M)
     }
     // the velocity and position blocks of A and B
     float Wacc[9], X[9], Rdt[9], hRdt2[9];
-    hat3f(acc, Wacc);
+    hat3(acc, Wacc);
 #pragma unroll
     for (int i = 0; i < 9; i++) X[i] = -s.dR[i] * dt;
     m3_mul(X, Wacc, M + 9 * M_A30);
@@ -123,7 +116,7 @@ __device__ __forceinline__ void chain_step(Chain &s, const float *m, float *M)
     const float d2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
     const float d = sqrtf(d2);
     float Wv[9], deltaR[9], rightJ[9];
-    hat3f(v, Wv);
+    hat3(v, Wv);
     if (d < IMU_EPS) {
 #pragma unroll
         for (int i = 0; i < 9; i++) {

@@ -1,10 +1,15 @@
 // ransac_common.h — device helpers and the sample-set check shared by the RANSAC solvers (sim3ransac.hip,
 // mlpnp.hip, twoview.hip).  Every unit that includes it is compiled with -ffp-contract=off and without
 // fast-math: a helper performs the same IEEE operations in the same order wherever it is called, so the bits
-// of a result do not depend on which unit called it (tests/test_ransac_bits_gpu.py pins them).
+// of a result do not depend on which unit called it (tests/test_ransac_bits_gpu.py pins them).  The Jacobi
+// routines they share with the optimisers are small_linalg.h's.
 #pragma once
 #include "glibc_math.h"
 #include "osg_internal.h"
+#include "small_linalg.h"
+
+using osgla::jacobi_rotation;
+using osgla::jacobi_sym;
 
 // GeometricCamera::project in float, of an Eigen::Vector3f (ref:src/CameraModels/Pinhole.cpp:64-71,
 // ref:src/CameraModels/KannalaBrandt8.cpp:87-104) and of a cv::Point3f (ref:src/CameraModels/Pinhole.cpp:39-43,
@@ -26,66 +31,6 @@ __device__ __forceinline__ void project_f(const osg_camera &c, float x, float y,
     } else {
         u = c.p[0] * x / z + c.p[2];
         v = c.p[1] * y / z + c.p[3];
-    }
-}
-
-// the Jacobi rotation that annihilates apq of the pair (app, aqq, apq), apq != 0: c = cos, s = sin
-__device__ __forceinline__ void jacobi_rotation(double app, double aqq, double apq, double &c, double &s)
-{
-    const double th = (aqq - app) / (2.0 * apq);
-    const double tt = (th >= 0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));
-    c = 1.0 / sqrt(tt * tt + 1.0);
-    s = tt * c;
-}
-
-// cyclic Jacobi on the symmetric N x N matrix A (registers, fully unrolled): A -> diagonal, V -> eigenvectors
-// in columns.  At most max_sweeps sweeps, until the squared off-diagonal part is within tol of the squared
-// diagonal; a zero matrix or one with a NaN stops at once.  The sweep limit and tol are the caller's: each
-// module's margins were measured with its own.
-template <int N>
-__device__ inline void jacobi_sym(double (&A)[N][N], double (&V)[N][N], int max_sweeps, double tol)
-{
-#pragma unroll
-    for (int i = 0; i < N; i++)
-#pragma unroll
-        for (int j = 0; j < N; j++) V[i][j] = i == j ? 1.0 : 0.0;
-#pragma unroll 1
-    for (int sweep = 0; sweep < max_sweeps; sweep++) {
-        double off = 0, diag = 0;
-#pragma unroll
-        for (int i = 0; i < N; i++) {
-            diag += A[i][i] * A[i][i];
-#pragma unroll
-            for (int j = i + 1; j < N; j++) off += A[i][j] * A[i][j];
-        }
-        if (!(off > tol * diag)) break;
-#pragma unroll
-        for (int p = 0; p < N - 1; p++)
-#pragma unroll
-            for (int q = p + 1; q < N; q++) {
-                const double apq = A[p][q];
-                if (apq == 0.0) continue;
-                double c, s;
-                jacobi_rotation(A[p][p], A[q][q], apq, c, s);
-#pragma unroll
-                for (int k = 0; k < N; k++) {
-                    const double akp = A[k][p], akq = A[k][q];
-                    A[k][p] = c * akp - s * akq;
-                    A[k][q] = s * akp + c * akq;
-                }
-#pragma unroll
-                for (int k = 0; k < N; k++) {
-                    const double apk = A[p][k], aqk = A[q][k];
-                    A[p][k] = c * apk - s * aqk;
-                    A[q][k] = s * apk + c * aqk;
-                }
-#pragma unroll
-                for (int k = 0; k < N; k++) {
-                    const double vkp = V[k][p], vkq = V[k][q];
-                    V[k][p] = c * vkp - s * vkq;
-                    V[k][q] = s * vkp + c * vkq;
-                }
-            }
     }
 }
 

@@ -29,6 +29,7 @@
 #include "ba_common.h"
 #include "batch_io.h"
 #include "sim3_common.h"
+#include "small_linalg.h"
 
 using namespace osgba;
 using osgs3::Sim3;
@@ -98,49 +99,6 @@ __device__ inline double chi2_2(double e0, double e1, double w)
     s += e0 * (w * e0);
     s += e1 * (w * e1);
     return s;
-}
-
-// unpivoted LDL^T of the damped N x N system (pose.hip's ldlt6 for any N); false when a pivot is not
-// positive.  Eigen's LDLT, which the reference's LinearSolverDense uses, pivots on the largest
-// remaining diagonal entry; the solutions agree to rounding.
-template <int N>
-__device__ inline bool ldlt_solve(double A[N][N], const double *b, double *x)
-{
-#pragma unroll
-    for (int j = 0; j < N; j++) {
-        double d = A[j][j];
-#pragma unroll
-        for (int k = 0; k < j; k++) d -= A[j][k] * A[j][k] * A[k][k];
-        if (!(d > 0.0)) return false;
-        A[j][j] = d;
-#pragma unroll
-        for (int i = j + 1; i < N; i++) {
-            double s = A[i][j];
-#pragma unroll
-            for (int k = 0; k < j; k++) s -= A[i][k] * A[j][k] * A[k][k];
-            A[i][j] = s / d;
-        }
-    }
-    double y[N];
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-        double s = b[i];
-#pragma unroll
-        for (int k = 0; k < i; k++) s -= A[i][k] * y[k];
-        y[i] = s;
-    }
-#pragma unroll
-    for (int i = 0; i < N; i++) y[i] /= A[i][i];
-#pragma unroll
-    for (int i = N - 1; i >= 0; i--) {
-        double s = y[i];
-#pragma unroll
-        for (int k = i + 1; k < N; k++) s -= A[k][i] * y[k];
-        y[i] = s;
-    }
-#pragma unroll
-    for (int i = 0; i < N; i++) x[i] = y[i];
-    return true;
 }
 
 __global__ __launch_bounds__(NT) void k_sim3_opt(const S3ProbDev *__restrict__ probs,
@@ -372,7 +330,7 @@ __global__ __launch_bounds__(NT) void k_sim3_opt(const S3ProbDev *__restrict__ p
 #pragma unroll
                     for (int i = 0; i < 7; i++) bvec[i] = S.sys[28 + i];
                     double x[7];
-                    ok2 = ldlt_solve<7>(A, bvec, x);
+                    ok2 = osgla::ldlt_solve<7>(A, bvec, x);
                     if (ok2)
 #pragma unroll
                         for (int i = 0; i < 7; i++) xs[i] = x[i];

@@ -73,7 +73,7 @@ __device__ inline void top_eigenvector(const double n[10], double q[4])
 {
     double A[4][4] = {{n[0], n[1], n[2], n[3]}, {n[1], n[4], n[5], n[6]}, {n[2], n[5], n[7], n[8]}, {n[3], n[6], n[8], n[9]}};
     double V[4][4];
-    jacobi_sym<4>(A, V, 16, 1e-40);  // stops when converged, zero, or NaN
+    jacobi_sym<double, 4>(A, V, 16, 1e-40);  // stops when converged, zero, or NaN
     int top = 0;
     double best = A[0][0];
 #pragma unroll

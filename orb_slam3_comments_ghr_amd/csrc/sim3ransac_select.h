@@ -14,11 +14,7 @@
 
 #include <cmath>
 
-#if defined(__HIPCC__)
-#define OSG_S3R_HD __host__ __device__
-#else
-#define OSG_S3R_HD
-#endif
+#include "osg_hd.h"
 
 struct osg_s3r_window {
     int32_t converged;     // bConverge: counts[hyp] > min_inliers ended the window
@@ -30,7 +26,7 @@ struct osg_s3r_window {
 
 // counts[0..n_hyp): inlier count per hypothesis in draw order (n_hyp = mRansacMaxIts).  One call of
 // iterate(window, ...) entered with mnIterations = start_iteration and mnBestInliers = n_best.
-OSG_S3R_HD inline osg_s3r_window osg_s3r_replay(const int32_t *counts, int32_t n_hyp, int32_t min_inliers,
+OSG_HD inline osg_s3r_window osg_s3r_replay(const int32_t *counts, int32_t n_hyp, int32_t min_inliers,
                                                 int32_t start_iteration, int32_t window, int32_t n_best)
 {
     osg_s3r_window w;

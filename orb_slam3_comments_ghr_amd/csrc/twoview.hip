@@ -102,7 +102,7 @@ __device__ inline void svd3(const float *M, float *U, float *w, float *V)
 #pragma unroll
         for (int j = 0; j < 3; j++)
             G[i][j] = (double)M[i] * M[j] + (double)M[3 + i] * M[3 + j] + (double)M[6 + i] * M[6 + j];
-    jacobi_sym<3>(G, E, JS_SWEEPS, JS_TOL);
+    jacobi_sym<double, 3>(G, E, JS_SWEEPS, JS_TOL);
     int o0 = 0, o1 = 1, o2 = 2;
     double l0 = G[0][0], l1 = G[1][1], l2 = G[2][2];
     if (l1 > l0) { double x = l0; l0 = l1; l1 = x; int y = o0; o0 = o1; o1 = y; }
@@ -284,7 +284,7 @@ __global__ __launch_bounds__(NT) void k_tvr_eval(const TProbDev *__restrict__ pr
 #pragma unroll
             for (int j = 0; j < 3; j++)
                 G[i][j] = (double)Mn[i] * Mn[j] + (double)Mn[3 + i] * Mn[3 + j] + (double)Mn[6 + i] * Mn[6 + j];
-        jacobi_sym<3>(G, E, JS_SWEEPS, JS_TOL);
+        jacobi_sym<double, 3>(G, E, JS_SWEEPS, JS_TOL);
         int e = 0;
         double lm = G[0][0];
         if (G[1][1] < lm) lm = G[1][1], e = 1;
@@ -579,7 +579,7 @@ __global__ __launch_bounds__(NT) void k_tvr_checkrt(const TProbDev *__restrict__
 #pragma unroll
                 for (int b = 0; b < 4; b++)
                     G[a][b] = (double)A[0][a] * A[0][b] + (double)A[1][a] * A[1][b] + (double)A[2][a] * A[2][b] + (double)A[3][a] * A[3][b];
-            jacobi_sym<4>(G, E, JS_SWEEPS, JS_TOL);
+            jacobi_sym<double, 4>(G, E, JS_SWEEPS, JS_TOL);
             int e = 0;
             double lm = G[0][0];
 #pragma unroll

@@ -14,18 +14,14 @@
 #pragma once
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define OSG_TVR_HD __host__ __device__
-#else
-#define OSG_TVR_HD
-#endif
+#include "osg_hd.h"
 
 struct osg_tvr_choice {
     int32_t ok;    // the reference's return value
     int32_t cand;  // the candidate the rule looked at last (F: first with maxGood; H: bestSolutionIdx; -1: none)
 };
 
-OSG_TVR_HD inline osg_tvr_choice osg_tvr_choose_f(const int32_t n_good[4], const float parallax[4], int32_t n_inliers,
+OSG_HD inline osg_tvr_choice osg_tvr_choose_f(const int32_t n_good[4], const float parallax[4], int32_t n_inliers,
                                                   float min_parallax, int32_t min_triangulated)
 {
     osg_tvr_choice c;
@@ -49,7 +45,7 @@ OSG_TVR_HD inline osg_tvr_choice osg_tvr_choose_f(const int32_t n_good[4], const
     return c;
 }
 
-OSG_TVR_HD inline osg_tvr_choice osg_tvr_choose_h(const int32_t n_good[8], const float parallax[8], int32_t n_inliers,
+OSG_HD inline osg_tvr_choice osg_tvr_choose_h(const int32_t n_good[8], const float parallax[8], int32_t n_inliers,
                                                   float min_parallax, int32_t min_triangulated)
 {
     osg_tvr_choice c;

@@ -3,9 +3,13 @@
 //   imu_host check       runs the host side of osg_imu_* without a device: every argument check, the queue rule,
 //                        the four interpolation branches, the deltas, PredictStateIMU and the packing of the
 //                        kernel's per-problem block; prints "ok"
+//   imu_host bits        prints the raw bytes, as hex, of delta and predict_state on a fixed state at three bias
+//                        steps (none, 1e-2, and one that puts JRg dbg below Sophus's small-angle cut), for
+//                        tests/golden/imu_host_bits.txt
 // Plain host C++: tests/test_preintegration.py builds it with -fsanitize=address,undefined and runs it directly.
 #include <cmath>
 #include <cstddef>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <limits>
@@ -139,10 +143,64 @@ static int check()
     return 0;
 }
 
+static void hex(const char *name, const float *v, int n)
+{
+    std::printf("%s", name);
+    for (int i = 0; i < n; i++) {
+        uint32_t u;
+        std::memcpy(&u, v + i, 4);
+        std::printf(" %08x", u);
+    }
+    std::printf("\n");
+}
+
+static int bits()
+{
+    // a state like a 65-step preintegration: a rotation of 0.2 rad about a skew axis, Jacobians of mixed sign
+    uint32_t lcg = 12345u;
+    auto next = [&lcg]() {
+        lcg = lcg * 1664525u + 1013904223u;
+        return (float)(lcg >> 8) / 16777216.0f - 0.5f;
+    };
+    osg_imu_preintegrated s;
+    std::memset(&s, 0, sizeof s);
+    const float c = 0.98006658f, sn = 0.19866933f;
+    const float R0[9] = {c, -sn, 0.f, sn, c, 0.f, 0.f, 0.f, 1.f};
+    const float R1[9] = {1.f, 0.f, 0.f, 0.f, c, -sn, 0.f, sn, c};
+    float Rwb[9];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+            float a = 0.f, b = 0.f;
+            for (int k = 0; k < 3; k++) a += R0[3 * i + k] * R1[3 * k + j], b += R1[3 * i + k] * R0[3 * k + j];
+            s.pre.dR[3 * i + j] = a, Rwb[3 * i + j] = b;
+        }
+    for (int i = 0; i < 9; i++) {
+        s.pre.JRg[i] = (i % 4 == 0 ? -0.3f : 0.f) + 0.02f * next();
+        s.pre.JVg[i] = 0.5f * next(), s.pre.JVa[i] = (i % 4 == 0 ? -0.3f : 0.f) + 0.05f * next();
+        s.pre.JPg[i] = 0.1f * next(), s.pre.JPa[i] = (i % 4 == 0 ? -0.05f : 0.f) + 0.01f * next();
+        Rwb[i] += 1e-4f * next();   // a stored rotation, not exactly orthonormal
+    }
+    for (int i = 0; i < 3; i++) s.pre.dV[i] = 2.f * next(), s.pre.dP[i] = 0.4f * next();
+    for (int i = 0; i < 6; i++) s.pre.b[i] = 0.05f * next();
+    s.pre.dT = 0.325f;
+    const float twb[3] = {1.5f, -2.25f, 0.75f}, vwb[3] = {0.3f, -0.1f, 0.9f};
+    const float step[3] = {0.f, 1e-2f, 1e-7f};
+    for (int k = 0; k < 3; k++) {
+        float bias[6], dR[9], dV[3], dP[3], R2[9], t2[3], v2[3];
+        for (int i = 0; i < 6; i++) bias[i] = s.pre.b[i] + step[k] * (2.f * next());
+        osgimu::delta(&s, bias, dR, dV, dP);
+        osgimu::predict_state(&s, bias, Rwb, twb, vwb, R2, t2, v2);
+        std::printf("step %d\n", k);
+        hex("dR", dR, 9), hex("dV", dV, 3), hex("dP", dP, 3), hex("Rwb2", R2, 9), hex("twb2", t2, 3), hex("vwb2", v2, 3);
+    }
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     if (argc >= 2 && !std::strcmp(argv[1], "layout")) return layout();
     if (argc >= 2 && !std::strcmp(argv[1], "check")) return check();
-    std::printf("usage: imu_host layout | check\n");
+    if (argc >= 2 && !std::strcmp(argv[1], "bits")) return bits();
+    std::printf("usage: imu_host layout | check | bits\n");
     return 2;
 }

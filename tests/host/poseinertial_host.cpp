@@ -4,10 +4,13 @@
 //   poseinertial_host check       runs the host side of osg_pose_inertial_optimization without a device: every
 //                                 argument check, the information matrices against their defining identities, and
 //                                 the packing of the kernel's per-problem block; prints "ok"
+//   poseinertial_host bits        prints the raw bytes, as hex, of info9, info_g and info_a of two fixed covariances,
+//                                 for tests/golden/poseinertial_host_bits.txt
 //   poseinertial_host info FILE   FILE holds C and C_rw (2 x 225 float32); prints info9, info_g, info_a
 // Plain host C++: tests/test_poseinertial.py builds it with -fsanitize=address,undefined and runs it directly.
 #include <cmath>
 #include <cstddef>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -196,11 +199,47 @@ static int info(const char *path)
     return 0;
 }
 
+static int bits()
+{
+    // covariances like make_C's, from a generator and powers that do not depend on the C library
+    uint32_t lcg = 2024u;
+    auto next = [&lcg]() {
+        lcg = lcg * 1664525u + 1013904223u;
+        return (double)(lcg >> 8) / 16777216.0 - 0.5;
+    };
+    for (int which = 0; which < 2; which++) {
+        std::vector<float> C(450);
+        for (int m = 0; m < 2; m++) {
+            double M[15][15], var[15];
+            for (int i = 0; i < 15; i++) {
+                var[i] = 1e-6;
+                for (int k = 0; k < (i + which) % 5; k++) var[i] /= 10.0;
+                for (int j = 0; j < 15; j++) M[i][j] = (i == j ? 1.0 : 0.0) + 0.05 * next();
+            }
+            for (int i = 0; i < 15; i++)
+                for (int j = 0; j < 15; j++) {
+                    double s = 0;
+                    for (int k = 0; k < 15; k++) s += M[i][k] * var[k] * M[j][k];
+                    C[225 * m + i * 15 + j] = (float)s;
+                }
+        }
+        double out[99];
+        osgpio::informations(C.data(), C.data() + 225, out, out + 81, out + 90);
+        for (int i = 0; i < 99; i++) {
+            uint64_t u;
+            std::memcpy(&u, out + i, 8);
+            std::printf("%016llx%c", (unsigned long long)u, i % 9 == 8 ? '\n' : ' ');
+        }
+    }
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     if (argc >= 2 && !std::strcmp(argv[1], "layout")) return layout();
     if (argc >= 2 && !std::strcmp(argv[1], "check")) return check();
+    if (argc >= 2 && !std::strcmp(argv[1], "bits")) return bits();
     if (argc >= 3 && !std::strcmp(argv[1], "info")) return info(argv[2]);
-    std::printf("usage: poseinertial_host layout | check | info FILE\n");
+    std::printf("usage: poseinertial_host layout | check | bits | info FILE\n");
     return 2;
 }

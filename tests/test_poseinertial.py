@@ -171,3 +171,14 @@ def test_host_informations_match_the_restatement(tmp_path):
     want = np.concatenate([info9.ravel(), np.linalg.inv(Crw[9:12, 9:12]).ravel(), np.linalg.inv(Crw[12:, 12:]).ravel()])
     # C's leading block has a condition number near 1e7: two double-precision inverses agree to about 1e-9
     np.testing.assert_allclose(got, want, rtol=0, atol=1e-8 * np.abs(want).max())
+
+
+def test_host_informations_have_the_recorded_bits(tmp_path):
+    """informations() on two fixed covariances, byte for byte against what the commit before the shared
+    csrc/small_linalg.h produced (tests/golden/poseinertial_host_bits.txt): its Jacobi is the kernels' own now."""
+    with open(os.path.join(ROOT, "tests", "golden", "poseinertial_host_bits.txt")) as f:
+        want = f.read()
+    for flags in (["-ffp-contract=off"], ["-ffp-contract=off", "-O1", "-g", "-fsanitize=address,undefined",
+                                          "-fno-sanitize-recover=all"]):
+        r = subprocess.run([host_program(tmp_path, flags), "bits"], capture_output=True, text=True)
+        assert r.returncode == 0 and r.stdout == want, r.stdout[-2000:] + r.stderr[-3000:]

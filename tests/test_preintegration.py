@@ -279,3 +279,14 @@ def test_host_side_under_sanitizers(tmp_path):
     exe = host_program(tmp_path, ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
     r = subprocess.run([exe, "check"], capture_output=True, text=True)
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-2000:] + r.stderr[-3000:]
+
+
+def test_host_delta_and_predict_state_have_the_recorded_bits(tmp_path):
+    """delta and predict_state on a fixed state at three bias steps (the last below Sophus's small-angle cut), byte
+    for byte against what the commit before the shared csrc/so3_common.h produced
+    (tests/golden/imu_host_bits.txt): they run the kernels' own SO(3) functions now."""
+    with open(os.path.join(ROOT, "tests", "golden", "imu_host_bits.txt")) as f:
+        want = f.read()
+    for flags in ([], ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]):
+        r = subprocess.run([host_program(tmp_path, flags), "bits"], capture_output=True, text=True)
+        assert r.returncode == 0 and r.stdout == want, r.stdout[-2000:] + r.stderr[-3000:]

@@ -1,12 +1,19 @@
 #!/usr/bin/env python3
-"""The bits of the four RANSAC / Sim3 modules' results on their committed fixtures.
+"""The bits of the modules' results on their committed fixtures, in two tables.
 
-One batched call per module over its BATCH fixture list (tests/sim3solver_fixtures.py, tests/mlpnp_fixtures.py,
-tests/twoview_fixtures.py, tests/sim3opt_fixtures.py), every optional per-hypothesis array requested, and a
-SHA-256 per fixture and result field: over an array's raw bytes, a scalar packed at its ABI width (int32 for
-integers and flags, float32 or double as include/osg.h declares it).  Writes tests/golden/ransac_digests.json,
-which tests/test_ransac_bits_gpu.py compares against.  The file is regenerated only by a change that means to
-alter these kernels' arithmetic; its header names the commit and the ROCm version it was recorded with."""
+``ransac`` (tests/golden/ransac_digests.json, tests/test_ransac_bits_gpu.py): the four RANSAC / Sim3 modules.  One
+batched call per module over its BATCH fixture list (tests/sim3solver_fixtures.py, tests/mlpnp_fixtures.py,
+tests/twoview_fixtures.py, tests/sim3opt_fixtures.py), every optional per-hypothesis array requested.
+
+``optimizer`` (tests/golden/optimizer_digests.json, tests/test_optimizer_bits_gpu.py): the modules built on the
+small dense routines of csrc/small_linalg.h and csrc/so3_common.h.  One call per module through the public Python
+API: PoseOptimization, PoseInertialOptimization, the IMU preintegration with its two host functions, and the two
+essential graphs (``optimizer_results`` lists the problems and sizes).
+
+A SHA-256 per fixture and result field: over an array's raw bytes, a scalar packed at its ABI width (int32 for
+integers and flags, float32 or double as include/osg.h declares it), a nested state field by field.  A golden file
+is regenerated only by a change that means to alter these kernels' arithmetic; its header names the commit and the
+ROCm version it was recorded with."""
 import argparse
 import dataclasses
 import hashlib
@@ -20,8 +27,21 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 GOLDEN = os.path.join(ROOT, "tests", "golden", "ransac_digests.json")
+GOLDEN_OPTIMIZER = os.path.join(ROOT, "tests", "golden", "optimizer_digests.json")
 # scalars the ABI declares as float (every other floating scalar is a double)
-FLOAT32 = {"sim3ransac": {"s"}, "twoview": {"score_h", "score_f"}}
+FLOAT32 = {"sim3ransac": {"s"}, "twoview": {"score_h", "score_f"}, "preintegration": {"dT"}}
+
+# PoseOptimization: (name, edges, stereo fraction, KB8 rig); 64 | 65 and 256 | 257 are the kernel's chunk edges
+POSE_CASES = [("mono_n0", 0, 0.0, False), ("stereo_n0", 0, 0.6, False), ("mono_n3", 3, 0.0, False),
+              ("stereo_n3", 3, 0.6, False), ("mono_n64", 64, 0.0, False), ("stereo_n64", 64, 0.6, False),
+              ("mono_n65", 65, 0.0, False), ("stereo_n65", 65, 0.6, False), ("mono_n257", 257, 0.0, False),
+              ("stereo_n257", 257, 0.6, False), ("kb8_rig_n257", 257, 0.0, True)]
+POSE_SEED = 31000
+# both essential graphs: 4 KeyFrames is the smallest graph their GPU tests run (the free3 fixtures); 12 KeyFrames
+# are 11 free vertices, more than the four (Sim3) or eight (4-DoF) that fill one 32 x 32 tile of the solver
+ESSGRAPH_CASES = [("kf4_free", 4, False, 32004), ("kf4_fixed", 4, True, 32005), ("kf12_free", 12, False, 32012),
+                  ("kf12_fixed", 12, True, 32013)]
+ESSGRAPH4_CASES = [("kf4", 4, 33004), ("kf12", 12, 33012)]
 
 
 def field_bytes(module, name, v):
@@ -33,6 +53,8 @@ def field_bytes(module, name, v):
         return np.int32(v).tobytes()
     if isinstance(v, (float, np.floating)):
         return (np.float32 if name in FLOAT32.get(module, ()) else np.float64)(v).tobytes()
+    if dataclasses.is_dataclass(v):
+        return b"".join(field_bytes(module, f.name, getattr(v, f.name)) for f in dataclasses.fields(v))
     raise TypeError("%s.%s: no packing for %r" % (module, name, type(v)))
 
 
@@ -51,14 +73,85 @@ def results(ctx):
             "sim3opt": run(sim3opt_fixtures, optimizer.Optimizer(ctx).OptimizeSim3)}
 
 
-def digests(ctx):
+def imu_host_results(state, seed):
+    """imu.delta and imu.predict_state (host code) on one state, at the three bias offsets of
+    tests/test_preintegration.py, drawn as it draws them: none, 1e-2, and 1e-7 (JRg dbg below Sophus's
+    small-angle cut).  Results as {field: array} dicts."""
+    from orb_slam3_comments_ghr_amd import imu
+    from tests import pyref_poseinertial as RP
+
+    f = np.float32
+    rng = np.random.default_rng(seed)
+    names, res = [], []
+    for i, db in enumerate((np.zeros(6, f), rng.normal(0, 0.01, 6).astype(f), rng.normal(0, 1e-7, 6).astype(f))):
+        bias = state.b + db
+        dR, dV, dP = imu.delta(state, bias)
+        Rwb = RP.NormalizeRotation(np.eye(3) + 0.3 * rng.normal(size=(3, 3))).astype(f)
+        twb, v = rng.normal(0, 2, 3).astype(f), rng.normal(0, 1, 3).astype(f)
+        R2, t2, v2 = imu.predict_state(state, bias, Rwb, twb, v)
+        names += ["n65.delta.db%d" % i, "n65.predict_state.db%d" % i]
+        res += [{"dR": dR, "dV": dV, "dP": dP}, {"Rwb": R2, "twb": t2, "vwb": v2}]
+    return names, res
+
+
+def optimizer_results(ctx):
+    """{module: (fixture names, results)}: one call per module"""
+    from orb_slam3_comments_ghr_amd import imu
+    from orb_slam3_comments_ghr_amd import optimizer as O
+    from tests import poseinertial_fixtures, preintegration_fixtures
+
+    opt = O.Optimizer(ctx)
+    out = {}
+    probs = [O.synth_pose_problem(np.random.default_rng(POSE_SEED + i), n, stereo_frac=sf,
+                                  cam=O.kb8_camera() if kb8 else None, body_frac=0.3 if kb8 else 0.0)
+             for i, (_, n, sf, kb8) in enumerate(POSE_CASES)]
+    out["pose"] = [c[0] for c in POSE_CASES], opt.PoseOptimization(probs)
+
+    fx = poseinertial_fixtures
+    names = list(fx.MIXED_BATCH) + list(fx.READMIT) + list(fx.BEHIND)
+    out["poseinertial"] = names, opt.pose_inertial_optimization_mixed([fx.build(k) for k in names])
+
+    fx = preintegration_fixtures
+    names = list(fx.FIXTURES)
+    built = [fx.build(k) for k in names]
+    states = imu.preintegrate_batch(ctx, [imu.ImuProblem(P.meas, P.bias, P.nga, P.nga_walk) for P in built])
+    host_names, host = imu_host_results(states[names.index("n65")], fx.FIXTURES["n65"].seed)
+    out["preintegration"] = names + host_names, states + host
+
+    out["essgraph"] = [c[0] for c in ESSGRAPH_CASES], [
+        opt.optimize_essential_graph(O.synth_essential_graph(np.random.default_rng(seed), n_kf, n_loop=min(3, n_kf - 2),
+                                                             fix_scale=fixed))
+        for _, n_kf, fixed, seed in ESSGRAPH_CASES]
+    out["essgraph4dof"] = [c[0] for c in ESSGRAPH4_CASES], [
+        opt.optimize_essential_graph_4dof(O.synth_essential_graph_4dof(np.random.default_rng(seed), n_kf,
+                                                                       n_loop=min(3, n_kf - 2)))
+        for _, n_kf, seed in ESSGRAPH4_CASES]
+    return out
+
+
+def fields_of(r):
+    return r.items() if isinstance(r, dict) else ((f.name, getattr(r, f.name)) for f in dataclasses.fields(r))
+
+
+def digests_of(table):
     """{module: {fixture: {field: sha256 hex}}}"""
     out = {}
-    for module, (names, res) in results(ctx).items():
-        assert len(names) == len(res)
-        out[module] = {name: {f.name: hashlib.sha256(field_bytes(module, f.name, getattr(r, f.name))).hexdigest()
-                              for f in dataclasses.fields(r)} for name, r in zip(names, res)}
+    for module, (names, res) in table.items():
+        assert len(names) == len(res) == len(set(names))
+        out[module] = {name: {k: hashlib.sha256(field_bytes(module, k, v)).hexdigest() for k, v in fields_of(r)}
+                       for name, r in zip(names, res)}
     return out
+
+
+def digests(ctx):
+    return digests_of(results(ctx))
+
+
+def optimizer_digests(ctx):
+    return digests_of(optimizer_results(ctx))
+
+
+TABLES = {"ransac": (digests, GOLDEN), "optimizer": (optimizer_digests, GOLDEN_OPTIMIZER)}
 
 
 def rocm_version():
@@ -71,20 +164,22 @@ def rocm_version():
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--table", choices=sorted(TABLES), default="ransac")
     ap.add_argument("--commit", default=None, help="the commit the loaded library was built from (default: HEAD)")
-    ap.add_argument("--out", default=GOLDEN)
+    ap.add_argument("--out", default=None, help="default: the table's golden file")
     a = ap.parse_args()
     commit = a.commit or subprocess.run(["git", "-C", ROOT, "rev-parse", "HEAD"], capture_output=True, text=True,
                                         check=True).stdout.strip()
     from orb_slam3_comments_ghr_amd import Context
 
+    table, golden = TABLES[a.table]
     ctx = Context(0)
-    out = {"recorded_at_commit": commit, "rocm_version": rocm_version(), "device": "gfx950", "digests": digests(ctx)}
+    out = {"recorded_at_commit": commit, "rocm_version": rocm_version(), "device": "gfx950", "digests": table(ctx)}
     ctx.close()
-    with open(a.out, "w") as f:
+    with open(a.out or golden, "w") as f:
         json.dump(out, f, indent=1, sort_keys=True)
         f.write("\n")
-    print("wrote", a.out, {m: len(v) for m, v in out["digests"].items()})
+    print("wrote", a.out or golden, {m: len(v) for m, v in out["digests"].items()})
 
 
 if __name__ == "__main__":
