@@ -40,8 +40,9 @@ def down(x):
 @dataclass
 class Case:
     name: str
-    kind: str     # fuse | sim3 | bysim3 | tri | init
-    args: tuple   # fuse (F, Q)  sim3 (F, Q, slot_query)  bysim3 (F1, F2, q12, q21)  tri (K1, K2, geom)  init (F1, F2, prev)
+    kind: str     # fuse | sim3 | bysim3 | tri | init, and match.hip's mps | last | kf | bow | bowkk
+    args: tuple   # fuse (F, Q)  sim3 (F, Q, slot_query)  bysim3 (F1, F2, q12, q21)  tri (K1, K2, geom)  init (F1, F2, prev);
+                  # match.hip's kinds: see tests/match_boundary_fixtures.py
     flips: tuple  # the decisions (pyref_match.FLIPS) the case discriminates
 
     @property
@@ -71,13 +72,27 @@ def cell_of(F, x, y):
 
 # ------------------------------------------------------------------------------------ running a case
 
+def _match():
+    """match.hip's five operators have their cases and their branches in a module of their own (which imports
+    this one's helpers, hence the late import)."""
+    from tests import match_boundary_fixtures
+    return match_boundary_fixtures
+
+
+MATCH_KINDS = ("mps", "last", "kf", "bow", "bowkk")
+
+
 def modes(case):
+    if case.kind in MATCH_KINDS:
+        return _match().modes(case)
     if case.kind == "fuse":
         return tuple(m for m in FUSE_MODES if not m[0] or case.args[0].nleft != -1)
     return {"sim3": SIM3_MODES, "tri": TRI_MODES}.get(case.kind, (None,))
 
 
 def run_oracle(oracle, case, mode):
+    if case.kind in MATCH_KINDS:
+        return _match().run_oracle(oracle, case, mode)
     a = case.args
     if case.kind == "fuse":
         return oc.fuse(oracle, a[0], a[1], TH, right=mode[0], gated=mode[1])
@@ -91,6 +106,8 @@ def run_oracle(oracle, case, mode):
 
 
 def run_pyref(case, mode, flip=None):
+    if case.kind in MATCH_KINDS:
+        return _match().run_pyref(case, mode, flip=flip)
     a = case.args
     if case.kind == "fuse":
         return pr.fuse_search(a[0], a[1], TH, right=mode[0], gated=mode[1], flip=flip)
@@ -101,6 +118,13 @@ def run_pyref(case, mode, flip=None):
     if case.kind == "tri":
         return pr.search_for_triangulation(*a, only_stereo=mode[0], coarse=mode[1], ori=True, flip=flip)
     return pr.search_for_initialization(*a, WINDOW, NNRATIO, True, flip=flip)
+
+
+def size(case):
+    """The larger side of a case: keypoints or queries."""
+    if case.kind in MATCH_KINDS:
+        return _match().size(case)
+    return max(case.args[0].n, case.args[1].n)
 
 
 def same(a, b):

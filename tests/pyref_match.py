@@ -54,6 +54,81 @@ FLIPS = {
     "init.accept": "b1 < TH_LOW",
     "init.accept:ratio": "b1 <= b2 * nnratio",
     "init.steal_hist": "only live matches counted in the histogram",
+    # SearchByProjection(Frame, MapPoints)
+    "mps.far": "depth >= thFar skips",
+    "mps.bad": "bad MapPoints searched",
+    "mps.radius": "viewCos > 0.998 compared in float",
+    "mps.level": "octave in [lvl - 1, lvl + 1]",
+    "mps.level:narrow": "octave in [lvl, lvl]",
+    "mps.taken": "a slot with any MapPoint is skipped, whatever its Observations",
+    "mps.taken:never": "taken slots are not skipped",
+    "mps.stereo": "|proj_xr - u_right| >= R skips",
+    "mps.stereo:kpr": "stereo gate iff u_right >= 0",
+    "mps.tie": "dist <= best: the last candidate wins",
+    "mps.top2": "a distance equal to the best is not the second best",
+    "mps.accept": "best < TH_HIGH",
+    "mps.ratio": "best >= nn * best2 rejects",
+    "mps.ratio:level": "ratio test whatever the two levels",
+    "mps.ratio:double": "nn * best2 in double",
+    "mps.skip_right": "the right pass runs after a left ratio failure",
+    "mps.partner": "left_to_right partner slot not written",
+    "mps.partner:r2l": "right_to_left partner slot not written",
+    "mps.own": "the query's own partner slot always blocks its right pass",
+    "mps.own:never": "the query's own partner slot never blocks its right pass",
+    "mps.level_r": "pred_level_r == -1 does not skip the right pass",
+    "mps.radius_r": "the right pass radius takes the th factor",
+    # SearchByProjection(Frame, LastFrame)
+    "last.invz": "invz <= 0 skips",
+    "last.bounds": "u <= min_x || u >= max_x, likewise v",
+    "last.forward": "tlc_z >= mb",
+    "last.backward": "-tlc_z >= mb",
+    "last.mono": "bMono does not disable forward / backward",
+    "last.level": "octave in [o - 2, o + 2]",
+    "last.level:narrow": "octave in [o, o]",
+    "last.level:fwd": "forward: octave in [o - 1, inf)",
+    "last.level:fwd_narrow": "forward: octave in [o + 1, inf)",
+    "last.level:bwd": "backward: octave in [0, o + 1]",
+    "last.level:bwd_narrow": "backward: octave in [0, o - 1]",
+    "last.taken": "a slot with any MapPoint is skipped, whatever its Observations",
+    "last.taken:never": "taken slots are not skipped",
+    "last.stereo": "|ur - u_right| >= radius skips",
+    "last.stereo:kpr": "stereo gate iff u_right >= 0",
+    "last.tie": "dist <= best: the last candidate wins",
+    "last.accept": "best < TH_HIGH",
+    "last.empty_left": "the right pass runs after an empty left window",
+    "last.hist_right": "right matches are left out of the histogram",
+    "last.hist_stale": "a match overwritten by a later one leaves the histogram",
+    # SearchByProjection(Frame, KeyFrame)
+    "kf.level": "octave in [lvl - 2, lvl + 2]",
+    "kf.level:narrow": "octave in [lvl - 1, lvl]",
+    "kf.taken": "slots with a MapPoint are not skipped",
+    "kf.tie": "dist <= best: the last candidate wins",
+    "kf.accept": "best < ORBdist",
+    "kf.accept:high": "best <= TH_HIGH, not the parameter",
+    # SearchByBoW(KF, F)
+    "bow.good": "KeyFrame features without a good MapPoint kept",
+    "bow.taken": "frame features already matched are not skipped",
+    "bow.tie": "dist <= best: the last candidate wins",
+    "bow.top2": "a distance equal to the best is not the second best",
+    "bow.accept": "best < TH_LOW",
+    "bow.ratio": "best <= nn * best2 accepts",
+    "bow.ratio:double": "nn * best2 in double",
+    "bow.side": "index == nleft goes to the left top-2",
+    "bow.right_gate": "the right match is looked at whatever the left best",
+    "bow.right_gate:ratio": "the right match is looked at only after a left ratio success",
+    "bow.right_ratio": "ratio test on the right match",
+    "bow.nodes": "nodes paired by position, not by id",
+    # SearchByBoW(KF, KF)
+    "bowkk.accept": "best <= TH_LOW",
+    "bowkk.ratio": "best <= nn * best2 accepts",
+    "bowkk.ratio:double": "nn * best2 in double",
+    "bowkk.matched2": "KF2 features already matched are not skipped",
+    "bowkk.mp2": "KF2 features without a MapPoint kept",
+    "bowkk.mp2:bad": "KF2 features with a bad MapPoint kept",
+    "bowkk.right": "KF1 indices >= nleft kept",
+    "bowkk.right:k2": "KF2 indices >= nleft kept",
+    "bowkk.tie": "dist <= best: the last candidate wins",
+    "bowkk.top2": "a distance equal to the best is not the second best",
 }
 
 
@@ -150,17 +225,36 @@ def apply_hist(hist, slots, nm, flip=None):
 
 
 class _Top2:
-    def __init__(self):
+    """bestDist / bestLevel / bestDist2 / bestLevel2 / bestIdx of the reference loops; ``tie``: the last of
+    equal distances wins, ``top2``: a distance equal to the best is not the second best (wrong forms)."""
+
+    def __init__(self, tie=False, top2=False):
         self.b, self.bl, self.b2, self.bl2, self.bi = 256, -1, 256, -1, -1
+        self.tie, self.top2 = tie, top2
 
     def push(self, d, lvl, idx):
-        if d < self.b:
+        if (d <= self.b and d < 256) if self.tie else d < self.b:
             self.b2, self.bl2, self.b, self.bl, self.bi = self.b, self.bl, d, lvl, idx
-        elif d < self.b2:
+        elif d < self.b2 and not (self.top2 and d == self.b):
             self.b2, self.bl2 = d, lvl
 
 
-def search_mps(F, Q, nn, th, far, thfar, slot_mp, slot_taken):
+def _ratio_gt(b, nn, b2, flip, name):
+    """(float)best > nnratio * (float)best2 and its wrong forms ``name`` (>=) and ``name:double``."""
+    if flip == name + ":double":
+        return float(b) > float(nn) * float(b2)
+    return f32(b) >= nn * f32(b2) if flip == name else f32(b) > nn * f32(b2)
+
+
+def _ratio_lt(b, nn, b2, flip, name):
+    """(float)best < nnratio * (float)best2 and its wrong forms ``name`` (<=) and ``name:double``."""
+    if flip == name + ":double":
+        return float(b) < float(nn) * float(b2)
+    return f32(b) <= nn * f32(b2) if flip == name else f32(b) < nn * f32(b2)
+
+
+def search_mps(F, Q, nn, th, far, thfar, slot_mp, slot_taken, flip=None):
+    _chk(flip)
     slots = slot_mp.copy()
     taken = slot_taken.copy()
     nm = 0
@@ -171,52 +265,90 @@ def search_mps(F, Q, nn, th, far, thfar, slot_mp, slot_taken):
         slots[s] = Q.mp_id[i]
         taken[s] = Q.has_obs[i]
 
+    def radius(c):
+        if flip == "mps.radius":
+            return f32(2.5) if f32(c) > f32(0.998) else f32(4.0)
+        return f32(2.5) if float(c) > 0.998 else f32(4.0)
+
+    def blocked(s):
+        if flip == "mps.taken:never":
+            return False
+        return slots[s] >= 0 and (bool(taken[s]) or flip == "mps.taken")
+
+    def levels(lvl):
+        if lvl < 0:
+            return lvl - 1, lvl  # only under mps.level_r: no level check at all (Frame.cc:919)
+        if flip == "mps.level":
+            return lvl - 1, lvl + 1
+        return (lvl, lvl) if flip == "mps.level:narrow" else (lvl - 1, lvl)
+
+    def top2():
+        return _Top2(tie=flip == "mps.tie", top2=flip == "mps.top2")
+
+    def rejected(t):
+        same = t.bl == t.bl2 or flip == "mps.ratio:level"
+        return same and _ratio_gt(t.b, nn, t.b2, flip, "mps.ratio")
+
+    def accepted(t):
+        return t.b < TH_HIGH if flip == "mps.accept" else t.b <= TH_HIGH
+
     for i in range(len(Q.mp_id)):
         in_r = Q.in_view_r is not None and bool(Q.in_view_r[i])
         if not Q.in_view[i] and not in_r:
             continue
-        if far and Q.track_depth[i] > f32(thfar):
+        if far and (Q.track_depth[i] >= f32(thfar) if flip == "mps.far" else Q.track_depth[i] > f32(thfar)):
             continue
-        if not Q.usable[i]:
+        if not Q.usable[i] and flip != "mps.bad":
             continue
+        own = -1
         if Q.in_view[i]:
             lvl = int(Q.pred_level[i])
-            r = f32(2.5) if float(Q.view_cos[i]) > 0.998 else f32(4.0)
+            r = radius(Q.view_cos[i])
             if f32(th) != f32(1.0):
                 r = f32(r * f32(th))
             R = f32(r * F.scale[lvl])
-            t = _Top2()
-            for idx in features_in_area(F, Q.proj_x[i], Q.proj_y[i], R, lvl - 1, lvl):
-                if slots[idx] >= 0 and taken[idx]:
+            t = top2()
+            for idx in features_in_area(F, Q.proj_x[i], Q.proj_y[i], R, *levels(lvl), flip=flip):
+                if blocked(idx):
                     continue
-                if not two and F.u_right is not None and F.u_right[idx] > 0:
-                    if abs(f32(Q.proj_xr[i] - F.u_right[idx])) > R:
+                kpr = F.u_right[idx] if not two and F.u_right is not None else f32(-1)
+                if kpr >= 0 if flip == "mps.stereo:kpr" else kpr > 0:
+                    er = abs(f32(Q.proj_xr[i] - kpr))
+                    if er >= R if flip == "mps.stereo" else er > R:
                         continue
                 t.push(dist(Q.desc[i], F.desc[idx]), int(F.kp_octave[idx]), idx)
-            if t.b <= TH_HIGH:
-                if t.bl == t.bl2 and f32(t.b) > nn * f32(t.b2):
-                    continue  # skips the right-camera pass too
-                assign(t.bi, i)
-                nm += 1
-                if two and F.left_to_right is not None and F.left_to_right[t.bi] != -1:
-                    assign(F.left_to_right[t.bi] + F.nleft, i)
+            if accepted(t):
+                if rejected(t):
+                    if flip != "mps.skip_right":
+                        continue  # skips the right-camera pass too
+                else:
+                    assign(t.bi, i)
                     nm += 1
+                    if two and F.left_to_right is not None and F.left_to_right[t.bi] != -1 and flip != "mps.partner":
+                        own = F.left_to_right[t.bi] + F.nleft
+                        assign(own, i)
+                        nm += 1
         if two and in_r:
             lvl = int(Q.pred_level_r[i])
-            if lvl == -1:
+            if lvl == -1 and flip != "mps.level_r":
                 continue
-            r = f32(2.5) if float(Q.view_cos_r[i]) > 0.998 else f32(4.0)
-            R = f32(r * F.scale[lvl])
-            t = _Top2()
-            for idx in features_in_area(F, Q.proj_xr[i], Q.proj_yr[i], R, lvl - 1, lvl, right=True):
+            r = radius(Q.view_cos_r[i])
+            if flip == "mps.radius_r" and f32(th) != f32(1.0):
+                r = f32(r * f32(th))
+            R = f32(r * F.scale[max(lvl, 0)])
+            t = top2()
+            for idx in features_in_area(F, Q.proj_xr[i], Q.proj_yr[i], R, *levels(lvl), right=True, flip=flip):
                 s_ = idx + F.nleft
-                if slots[s_] >= 0 and taken[s_]:
+                if s_ == own and flip in ("mps.own", "mps.own:never"):
+                    if flip == "mps.own":
+                        continue
+                elif blocked(s_):
                     continue
                 t.push(dist(Q.desc[i], F.desc[s_]), int(F.kp_octave[s_]), idx)
-            if t.b <= TH_HIGH:
-                if t.bl == t.bl2 and f32(t.b) > nn * f32(t.b2):
+            if accepted(t):
+                if rejected(t):
                     continue
-                if F.right_to_left is not None and F.right_to_left[t.bi] != -1:
+                if F.right_to_left is not None and F.right_to_left[t.bi] != -1 and flip != "mps.partner:r2l":
                     assign(F.right_to_left[t.bi], i)
                     nm += 1
                 assign(t.bi + F.nleft, i)
@@ -224,74 +356,106 @@ def search_mps(F, Q, nn, th, far, thfar, slot_mp, slot_taken):
     return nm, slots
 
 
-def search_last(F, L, th, mono, ori, slot_mp, slot_taken):
+def search_last(F, L, th, mono, ori, slot_mp, slot_taken, flip=None):
+    _chk(flip)
     slots = slot_mp.copy()
     taken = slot_taken.copy()
     hist = [[] for _ in range(HISTO)]
     nm = 0
     two = F.nleft != -1
-    fwd = f32(L.tlc_z) > f32(F.mb) and not mono
-    bwd = -f32(L.tlc_z) > f32(F.mb) and not mono
+    tz, mb = f32(L.tlc_z), f32(F.mb)
+    owner = {}  # slot -> the last query that wrote it
+    not_mono = not mono or flip == "last.mono"
+    fwd = (tz >= mb if flip == "last.forward" else tz > mb) and not_mono
+    bwd = (-tz >= mb if flip == "last.backward" else -tz > mb) and not_mono
+    wide = {"last.level": (1, 1), "last.level:narrow": (-1, -1), "last.level:fwd": (1, 0),
+            "last.level:fwd_narrow": (-1, 0), "last.level:bwd": (0, 1), "last.level:bwd_narrow": (0, -1)}
+    lo_, hi_ = wide.get(flip, (0, 0))
 
     def window(u, v, rad, o, right):
         if fwd:
-            return features_in_area(F, u, v, rad, o, -1, right)
+            lo_f = lo_ if flip in ("last.level:fwd", "last.level:fwd_narrow") else 0
+            return features_in_area(F, u, v, rad, o - lo_f, -1, right, flip=flip)
         if bwd:
-            return features_in_area(F, u, v, rad, 0, o, right)
-        return features_in_area(F, u, v, rad, o - 1, o + 1, right)
+            hi_b = hi_ if flip in ("last.level:bwd", "last.level:bwd_narrow") else 0
+            return features_in_area(F, u, v, rad, 0, o + hi_b, right, flip=flip)
+        w = lo_ if flip in ("last.level", "last.level:narrow") else 0
+        return features_in_area(F, u, v, rad, o - 1 - w, o + 1 + w, right, flip=flip)
+
+    def blocked(s):
+        if flip == "last.taken:never":
+            return False
+        return slots[s] >= 0 and (bool(taken[s]) or flip == "last.taken")
+
+    def better(d, b):
+        return (d <= b and d < 256) if flip == "last.tie" else d < b
+
+    def accepted(b):
+        return b < TH_HIGH if flip == "last.accept" else b <= TH_HIGH
 
     for i in range(len(L.mp_id)):
         if not L.valid[i]:
             continue
         invz = L.invz[i]
-        if invz < 0:
+        if invz <= 0 if flip == "last.invz" else invz < 0:
             continue
         u, v = L.u[i], L.v[i]
-        if u < f32(F.min_x) or u > f32(F.max_x) or v < f32(F.min_y) or v > f32(F.max_y):
+        x0, x1, y0, y1 = f32(F.min_x), f32(F.max_x), f32(F.min_y), f32(F.max_y)
+        if flip == "last.bounds":
+            if u <= x0 or u >= x1 or v <= y0 or v >= y1:
+                continue
+        elif u < x0 or u > x1 or v < y0 or v > y1:
             continue
         o = int(L.octave[i])
         rad = f32(f32(th) * F.scale[o])
         c = window(u, v, rad, o, False)
-        if not c:
+        if not c and flip != "last.empty_left":
             continue
         b, bi = 256, -1
         for i2 in c:
-            if slots[i2] >= 0 and taken[i2]:
+            if blocked(i2):
                 continue
-            if not two and F.u_right is not None and F.u_right[i2] > 0:
+            kpr = F.u_right[i2] if not two and F.u_right is not None else f32(-1)
+            if kpr >= 0 if flip == "last.stereo:kpr" else kpr > 0:
                 ur = f32(u - f32(f32(F.mbf) * invz))
-                if abs(f32(ur - F.u_right[i2])) > rad:
+                er = abs(f32(ur - kpr))
+                if er >= rad if flip == "last.stereo" else er > rad:
                     continue
             d = dist(L.desc[i], F.desc[i2])
-            if d < b:
+            if better(d, b):
                 b, bi = d, i2
-        if b <= TH_HIGH:
+        if accepted(b):
             slots[bi] = L.mp_id[i]
             taken[bi] = L.has_obs[i]
             nm += 1
+            owner[bi] = i
             if ori:
-                hist[rot_bin(L.angle[i], F.kp_angle[bi])].append(bi)
+                hist[rot_bin(L.angle[i], F.kp_angle[bi], flip)].append((bi, i))
         if two:
             b, bi = 256, -1
             for i2 in window(L.u_r[i], L.v_r[i], rad, o, True):
                 s_ = i2 + F.nleft
-                if slots[s_] >= 0 and taken[s_]:
+                if blocked(s_):
                     continue
                 d = dist(L.desc[i], F.desc[s_])
-                if d < b:
+                if better(d, b):
                     b, bi = d, s_
-            if b <= TH_HIGH:
+            if accepted(b):
                 slots[bi] = L.mp_id[i]
                 taken[bi] = L.has_obs[i]
                 nm += 1
-                if ori:
-                    hist[rot_bin(L.angle[i], F.kp_angle[bi])].append(bi)
+                owner[bi] = i
+                if ori and flip != "last.hist_right":
+                    hist[rot_bin(L.angle[i], F.kp_angle[bi], flip)].append((bi, i))
     if ori:
-        nm = apply_hist(hist, slots, nm)
+        # rotHist keeps every accepted match, also one whose slot a later query took again
+        stale = flip == "last.hist_stale"
+        nm = apply_hist([[s for s, i in h if not stale or owner[s] == i] for h in hist], slots, nm, flip)
     return nm, slots
 
 
-def search_kf(F, K, th, orb, ori, slot_mp):
+def search_kf(F, K, th, orb, ori, slot_mp, flip=None):
+    _chk(flip)
     slots = slot_mp.copy()
     hist = [[] for _ in range(HISTO)]
     nm = 0
@@ -300,68 +464,88 @@ def search_kf(F, K, th, orb, ori, slot_mp):
             continue
         lvl = int(K.pred_level[i])
         rad = f32(f32(th) * F.scale[lvl])
-        c = features_in_area(F, K.u[i], K.v[i], rad, lvl - 1, lvl + 1)
+        lo, hi = lvl - 1, lvl + 1
+        if flip == "kf.level":
+            lo, hi = lvl - 2, lvl + 2
+        elif flip == "kf.level:narrow":
+            hi = lvl
+        c = features_in_area(F, K.u[i], K.v[i], rad, lo, hi, flip=flip)
         if not c:
             continue
         b, bi = 256, -1
         for i2 in c:
-            if slots[i2] >= 0:
+            if slots[i2] >= 0 and flip != "kf.taken":
                 continue
             d = dist(K.desc[i], F.desc[i2])
-            if d < b:
+            if (d <= b and d < 256) if flip == "kf.tie" else d < b:
                 b, bi = d, i2
-        if b <= orb:
+        lim = TH_HIGH if flip == "kf.accept:high" else orb
+        if b < lim if flip == "kf.accept" else b <= lim:
             slots[bi] = K.mp_id[i]
             nm += 1
             if ori:
-                hist[rot_bin(K.angle[i], F.kp_angle[bi])].append(bi)
+                hist[rot_bin(K.angle[i], F.kp_angle[bi], flip)].append(bi)
     if ori:
-        nm = apply_hist(hist, slots, nm)
+        nm = apply_hist(hist, slots, nm, flip)
     return nm, slots
 
 
-def _shared_nodes(A, B):
-    ma = {int(n): (A.node_start[k], A.node_start[k + 1]) for k, n in enumerate(A.node_id)}
-    mb = {int(n): (B.node_start[k], B.node_start[k + 1]) for k, n in enumerate(B.node_id)}
+def _shared_nodes(A, B, by_position=False):
+    ra = [(A.node_start[k], A.node_start[k + 1]) for k in range(len(A.node_id))]
+    rb = [(B.node_start[k], B.node_start[k + 1]) for k in range(len(B.node_id))]
+    if by_position:  # wrong form (bow.nodes): the k-th node of one side against the k-th of the other
+        yield from zip(ra, rb)
+        return
+    ma = {int(n): r for n, r in zip(A.node_id, ra)}
+    mb = {int(n): r for n, r in zip(B.node_id, rb)}
     for n in sorted(set(ma) & set(mb)):
         yield ma[n], mb[n]
 
 
-def search_bow_kf_f(KF, F, nn, ori):
+def search_bow_kf_f(KF, F, nn, ori, flip=None):
+    _chk(flip)
     out = np.full(F.n, -1, np.int32)
     hist = [[] for _ in range(HISTO)]
     nm = 0
     nn = f32(nn)
-    for (a0, a1), (b0, b1) in _shared_nodes(KF, F):
+    for (a0, a1), (b0, b1) in _shared_nodes(KF, F, flip == "bow.nodes"):
         for a in range(a0, a1):
             ik = int(KF.feat[a])
-            if not KF.mp_good[ik]:
+            if not KF.mp_good[ik] and flip != "bow.good":
                 continue
-            tl, tr = _Top2(), _Top2()
+            tl, tr = (_Top2(tie=flip == "bow.tie", top2=flip == "bow.top2") for _ in range(2))
             for j in range(b0, b1):
                 jf = int(F.feat[j])
-                if out[jf] >= 0:
+                if out[jf] >= 0 and flip != "bow.taken":
                     continue
                 d = dist(KF.desc[ik], F.desc[jf])
-                (tl if F.nleft == -1 or jf < F.nleft else tr).push(d, 0, jf)
-            if tl.b <= TH_LOW:
-                if f32(tl.b) < nn * f32(tl.b2):
-                    out[tl.bi] = KF.mp_id[ik]
-                    nm += 1
-                    if ori:
-                        hist[rot_bin(KF.angle[ik], F.angle[tl.bi])].append(tl.bi)
-                if tr.b <= TH_LOW:  # right match: ratio test disabled ('|| true')
-                    out[tr.bi] = KF.mp_id[ik]
-                    nm += 1
-                    if ori:
-                        hist[rot_bin(KF.angle[ik], F.angle[tr.bi])].append(tr.bi)
+                left = F.nleft == -1 or (jf <= F.nleft if flip == "bow.side" else jf < F.nleft)
+                (tl if left else tr).push(d, 0, jf)
+            gate = tl.b < TH_LOW if flip == "bow.accept" else tl.b <= TH_LOW
+            ratio = gate and _ratio_lt(tl.b, nn, tl.b2, flip, "bow.ratio")
+            if ratio:
+                out[tl.bi] = KF.mp_id[ik]
+                nm += 1
+                if ori:
+                    hist[rot_bin(KF.angle[ik], F.angle[tl.bi], flip)].append(tl.bi)
+            if flip == "bow.right_gate":
+                gate = True
+            elif flip == "bow.right_gate:ratio":
+                gate = ratio
+            # right match: ratio test disabled ('|| true')
+            if gate and tr.b <= TH_LOW and (flip != "bow.right_ratio" or f32(tr.b) < nn * f32(tr.b2)):
+                out[tr.bi] = KF.mp_id[ik]
+                nm += 1
+                if ori:
+                    hist[rot_bin(KF.angle[ik], F.angle[tr.bi], flip)].append(tr.bi)
     if ori:
-        nm = apply_hist(hist, out, nm)
+        nm = apply_hist(hist, out, nm, flip)
     return nm, out
 
 
-def search_bow_kf_kf(K1, K2, nn, ori):
+def search_bow_kf_kf(K1, K2, nn, ori, flip=None):
     """Two-camera keyframes: indices >= mvKeysUn.size() == NLeft are skipped on both sides."""
+    _chk(flip)
     out = np.full(K1.n, -1, np.int32)
     matched2 = np.zeros(K2.n, bool)
     hist = [[] for _ in range(HISTO)]
@@ -370,30 +554,31 @@ def search_bow_kf_kf(K1, K2, nn, ori):
     for (a0, a1), (b0, b1) in _shared_nodes(K1, K2):
         for a in range(a0, a1):
             i1 = int(K1.feat[a])
-            if K1.nleft != -1 and i1 >= K1.nleft:
+            if K1.nleft != -1 and i1 >= K1.nleft and flip != "bowkk.right":
                 continue
             if not K1.mp_good[i1]:
                 continue
-            b, bi, b2 = 256, -1, 256
+            t = _Top2(tie=flip == "bowkk.tie", top2=flip == "bowkk.top2")
             for j in range(b0, b1):
                 i2 = int(K2.feat[j])
-                if K2.nleft != -1 and i2 >= K2.nleft:
+                if K2.nleft != -1 and i2 >= K2.nleft and flip != "bowkk.right:k2":
                     continue
-                if matched2[i2] or K2.mp_id[i2] < 0 or not K2.mp_good[i2]:
+                if matched2[i2] and flip != "bowkk.matched2":
                     continue
-                d = dist(K1.desc[i1], K2.desc[i2])
-                if d < b:
-                    b2, b, bi = b, d, i2
-                elif d < b2:
-                    b2 = d
-            if b < TH_LOW and f32(b) < nn * f32(b2):
-                out[i1] = K2.mp_id[bi]
-                matched2[bi] = True
+                if K2.mp_id[i2] < 0 and flip != "bowkk.mp2":
+                    continue
+                if not K2.mp_good[i2] and flip != "bowkk.mp2:bad":
+                    continue
+                t.push(dist(K1.desc[i1], K2.desc[i2]), 0, i2)
+            if (t.b <= TH_LOW if flip == "bowkk.accept" else t.b < TH_LOW) and \
+                    _ratio_lt(t.b, nn, t.b2, flip, "bowkk.ratio"):
+                out[i1] = K2.mp_id[t.bi]
+                matched2[t.bi] = True
                 nm += 1
                 if ori:
-                    hist[rot_bin(K1.angle[i1], K2.angle[bi])].append(i1)
+                    hist[rot_bin(K1.angle[i1], K2.angle[t.bi], flip)].append(i1)
     if ori:
-        nm = apply_hist(hist, out, nm)
+        nm = apply_hist(hist, out, nm, flip)
     return nm, out
 
 
