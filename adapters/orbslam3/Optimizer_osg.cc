@@ -1,5 +1,5 @@
 // Optimizer_osg.cc — drop-in bodies for Optimizer::PoseOptimization, Optimizer::PoseInertialOptimizationLastKeyFrame /
-// LastFrame, the g2o part of
+// LastFrame, the three overloads of Optimizer::InertialOptimization, the g2o part of
 // Optimizer::LocalBundleAdjustment (both overloads), Optimizer::BundleAdjustment (global BA) and
 // Optimizer::OptimizeSim3, Optimizer::OptimizeEssentialGraph (the loop-closure overload) and
 // Optimizer::OptimizeEssentialGraph4DoF on the MI355X path (ORB-SLAM3 tree built with -DORB_SLAM3_OSG;
@@ -24,6 +24,47 @@ int Optimizer::PoseInertialOptimizationLastFrame(Frame *pFrame, bool bRecInit)
 {  // ref:src/Optimizer.cc:1002-1640; a previous frame without mpcpi is refused by the library (the reference
    // dereferences null at :1275) and 0 is returned with the frame untouched
     return osg_orbslam3::pose_inertial_optimization_last_frame<OsgHooks>(pFrame, bRecInit, &MapPoint::mGlobalMutex);
+}
+
+namespace {
+void rwg_to_rows(const Eigen::Matrix3d &Rwg, double r[9])
+{
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) r[3 * i + j] = Rwg(i, j);
+}
+}  // namespace
+
+void Optimizer::InertialOptimization(Map *pMap, Eigen::Matrix3d &Rwg, double &scale, Eigen::Vector3d &bg,
+                                     Eigen::Vector3d &ba, bool bMono, Eigen::MatrixXd &covInertial, bool bFixedVel,
+                                     bool bGauss, float priorG, float priorA)
+{  // ref:src/Optimizer.cc:3706-3898 (LocalMapping::InitializeIMU); covInertial and bGauss are unused there too
+    double r[9], g[3], a[3];
+    rwg_to_rows(Rwg, r);
+    if (!osg_orbslam3::inertial_optimization_init<OsgHooks>(pMap->GetAllKeyFrames(), pMap->GetMaxKFid(), r, scale, g, a,
+                                                            bMono, bFixedVel, priorG, priorA))
+        return;
+    Rwg = Eigen::Map<const Eigen::Matrix<double, 3, 3, Eigen::RowMajor>>(r);
+    bg = Eigen::Vector3d(g[0], g[1], g[2]);
+    ba = Eigen::Vector3d(a[0], a[1], a[2]);
+}
+
+void Optimizer::InertialOptimization(Map *pMap, Eigen::Vector3d &bg, Eigen::Vector3d &ba, float priorG, float priorA)
+{  // ref:src/Optimizer.cc:3910-4076 (LoopClosing::MergeLocal2)
+    double g[3], a[3];
+    if (!osg_orbslam3::inertial_optimization_bias<OsgHooks>(pMap->GetAllKeyFrames(), pMap->GetMaxKFid(), g, a, priorG,
+                                                            priorA))
+        return;
+    bg = Eigen::Vector3d(g[0], g[1], g[2]);
+    ba = Eigen::Vector3d(a[0], a[1], a[2]);
+}
+
+void Optimizer::InertialOptimization(Map *pMap, Eigen::Matrix3d &Rwg, double &scale)
+{  // ref:src/Optimizer.cc:4085-4197 (LocalMapping::ScaleRefinement)
+    double r[9];
+    rwg_to_rows(Rwg, r);
+    if (!osg_orbslam3::inertial_optimization_scale<OsgHooks>(pMap->GetAllKeyFrames(), pMap->GetMaxKFid(), r, scale))
+        return;
+    Rwg = Eigen::Map<const Eigen::Matrix<double, 3, 3, Eigen::RowMajor>>(r);
 }
 
 // The local window (ref:src/Optimizer.cc:1762-1873) is the reference's code unchanged; it ends with

@@ -589,6 +589,13 @@ struct OsgHooks {
         for (int k = 0; k < 3; k++) g[k] = v(k);
     }
     static void set_new_bias(KeyFrame &K, const float b[6]) { K.SetNewBias(IMU::Bias(b[0], b[1], b[2], b[3], b[4], b[5])); }
+    // ---- InertialOptimization ("InertialOptimization")
+    static bool is_bad(KeyFrame &K) { return K.isBad(); }
+    static void set_velocity(KeyFrame &K, const double v[3])
+    {
+        const Eigen::Vector3d Vw(v[0], v[1], v[2]);
+        K.SetVelocity(Vw.cast<float>());
+    }
     // KeyFrameDatabase: the vocabulary on the device, set by System right after it loads ORBvoc
     // (osg_vocabulary_load_text) and before it constructs the database
     static const osg_vocabulary *&device_vocabulary()

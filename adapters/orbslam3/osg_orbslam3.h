@@ -4279,5 +4279,147 @@ void merge_previous(PreintT *self, PreintT *pPrev)
     H::preint_restart(self, out, list.data(), p.n);
 }
 
+// ------------------------------------------------- a10g InertialOptimization (the three overloads)
+// ref:src/Optimizer.cc:3706-3898, 3910-4076, 4085-4197.  The gather follows the reference: a vertex pair for every
+// KeyFrame of vpKFs with mnId <= maxKFid; an edge for every such KeyFrame with an mPrevKF unless it isBad() or the
+// mPrevKF's mnId is above maxKFid (or the mPrevKF is not among the vertices, the reference's "Error" continue); the
+// bias vertices start from vpKFs.front().  A KeyFrame without a preintegration gets the reference's message and no
+// edge (the reference dereferences the null pointer).  The SetNewBias(mPrevKF->GetImuBias()) of overloads 1 and 2 is
+// left out: the edge passes its own bias to the getters, and the write-back's SetNewBias(b) overwrites bu and db.
+//   H::imu_state(KeyFrame&, osg_pio_state&)      GetImuRotation / GetImuPosition / GetVelocity / biases in double
+//   H::preintegrated(pInt, osg_pio_preintegrated&)
+//   H::is_bad(KeyFrame&)                         isBad()
+//   H::set_velocity(KeyFrame&, const double[3])  SetVelocity(Vw.cast<float>())
+// and, through reintegrate_keyframes, gyro_bias, set_new_bias, preint_get, preint_measurements, preint_restart.
+struct InertialOptions {
+    bool priors = true, free_vel_bias = true, free_gdir = true, free_scale = true;
+    int algorithm = OSG_INERTIAL_LM, iterations = 200;
+    double lambda_init = 0.0, huber_delta = 0.0, prior_g = 0.0, prior_a = 0.0;
+};
+
+template <class H, class KeyFrameT>
+struct InertialGather {
+    std::vector<KeyFrameT *> kfs;  // the KeyFrames with a vertex, in vpKFs order
+    std::vector<double> Rwb, twb, v, v_out;
+    std::vector<int32_t> prev, cur;
+    std::vector<osg_pio_preintegrated> pre;
+    osg_inertial_problem p{};
+
+    void assign(const std::vector<KeyFrameT *> &vpKFs, unsigned long maxKFid, const InertialOptions &o,
+                const double Rwg[9], double scale)
+    {
+        std::unordered_map<KeyFrameT *, int32_t> index;
+        for (KeyFrameT *pKFi : vpKFs) {
+            if (pKFi->mnId > maxKFid) continue;
+            osg_pio_state s{};
+            H::imu_state(*pKFi, s);
+            index[pKFi] = (int32_t)kfs.size();
+            kfs.push_back(pKFi);
+            Rwb.insert(Rwb.end(), s.Rwb, s.Rwb + 9);
+            twb.insert(twb.end(), s.twb, s.twb + 3);
+            v.insert(v.end(), s.v, s.v + 3);
+        }
+        for (KeyFrameT *pKFi : vpKFs) {
+            if (!(pKFi->mPrevKF && pKFi->mnId <= maxKFid)) continue;
+            if (H::is_bad(*pKFi) || pKFi->mPrevKF->mnId > maxKFid) continue;
+            if (!pKFi->mpImuPreintegrated) {
+                std::cout << "Not preintegrated measurement" << std::endl;
+                continue;
+            }
+            const auto it = index.find(pKFi->mPrevKF);
+            if (it == index.end()) continue;
+            prev.push_back(it->second);
+            cur.push_back(index[pKFi]);
+            pre.emplace_back();
+            H::preintegrated(pKFi->mpImuPreintegrated, pre.back());
+        }
+        p = osg_inertial_problem{};
+        p.n_kf = (int32_t)kfs.size();
+        p.Rwb = Rwb.data(), p.twb = twb.data(), p.v = v.data();
+        p.n_edges = (int32_t)prev.size();
+        p.prev = prev.data(), p.cur = cur.data(), p.preint = pre.data();
+        if (!vpKFs.empty()) {  // VertexGyroBias(vpKFs.front()), VertexAccBias(vpKFs.front())
+            osg_pio_state s{};
+            H::imu_state(*vpKFs.front(), s);
+            std::memcpy(p.bg, s.bg, sizeof p.bg);
+            std::memcpy(p.ba, s.ba, sizeof p.ba);
+        }
+        std::memcpy(p.Rwg, Rwg, sizeof p.Rwg);
+        p.scale = scale;
+        p.prior_g = o.prior_g, p.prior_a = o.prior_a;
+        p.has_priors = o.priors, p.free_vel_bias = o.free_vel_bias, p.free_gdir = o.free_gdir;
+        p.free_scale = o.free_scale;
+        p.algorithm = o.algorithm, p.iterations = o.iterations;
+        p.lambda_init = o.lambda_init, p.huber_delta = o.huber_delta;
+        v_out.assign(v.size(), 0.0);
+    }
+};
+
+// One library call; false (nothing written) when it fails.  Rwg (row-major), scale, bg and ba are written as the
+// reference writes its reference arguments; with write_kfs the velocities and the bias go back to the KeyFrames in
+// vpKFs order and every Reintegrate() of the call is one launch.
+template <class H, class KeyFrameT>
+bool inertial_optimization(const std::vector<KeyFrameT *> &vpKFs, unsigned long maxKFid, const InertialOptions &o,
+                           double Rwg[9], double &scale, double bg[3], double ba[3], bool write_kfs)
+{
+    osg_ctx *ctx = thread_ctx();
+    InertialGather<H, KeyFrameT> g;
+    g.assign(vpKFs, maxKFid, o, Rwg, scale);
+    osg_inertial_result r{};
+    r.v = g.v_out.data();
+    if (call(ctx, "osg_inertial_optimization", [&] { return osg_inertial_optimization(ctx, &g.p, &r); }) < 0)
+        return false;
+    scale = r.scale;
+    std::memcpy(Rwg, r.Rwg, sizeof r.Rwg);
+    if (bg) std::memcpy(bg, r.bg, sizeof r.bg);
+    if (ba) std::memcpy(ba, r.ba, sizeof r.ba);
+    if (!write_kfs) return true;
+    for (size_t i = 0; i < g.kfs.size(); i++) H::set_velocity(*g.kfs[i], &g.v_out[3 * i]);
+    // IMU::Bias b(vb[3], vb[4], vb[5], vb[0], vb[1], vb[2]) with vb = (bg, ba): floats, (ba, bg)
+    const float b[6] = {(float)r.ba[0], (float)r.ba[1], (float)r.ba[2], (float)r.bg[0], (float)r.bg[1], (float)r.bg[2]};
+    reintegrate_keyframes<H>(g.kfs, b);
+    return true;
+}
+
+// overload 1: LocalMapping::InitializeIMU
+template <class H, class KeyFrameT>
+bool inertial_optimization_init(const std::vector<KeyFrameT *> &vpKFs, unsigned long maxKFid, double Rwg[9],
+                                double &scale, double bg[3], double ba[3], bool bMono, bool bFixedVel, float priorG,
+                                float priorA)
+{
+    InertialOptions o;
+    o.free_vel_bias = !bFixedVel;
+    o.free_scale = bMono;
+    o.prior_g = priorG, o.prior_a = priorA;
+    o.lambda_init = priorG != 0.f ? 1e3 : 0.0;
+    return inertial_optimization<H>(vpKFs, maxKFid, o, Rwg, scale, bg, ba, true);
+}
+
+// overload 2: LoopClosing::MergeLocal2
+template <class H, class KeyFrameT>
+bool inertial_optimization_bias(const std::vector<KeyFrameT *> &vpKFs, unsigned long maxKFid, double bg[3],
+                                double ba[3], float priorG, float priorA)
+{
+    InertialOptions o;
+    o.free_gdir = o.free_scale = false;
+    o.prior_g = priorG, o.prior_a = priorA;
+    o.lambda_init = 1e3;
+    double Rwg[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, scale = 1.0;
+    return inertial_optimization<H>(vpKFs, maxKFid, o, Rwg, scale, bg, ba, true);
+}
+
+// overload 3: LocalMapping::ScaleRefinement
+template <class H, class KeyFrameT>
+bool inertial_optimization_scale(const std::vector<KeyFrameT *> &vpKFs, unsigned long maxKFid, double Rwg[9],
+                                 double &scale)
+{
+    InertialOptions o;
+    o.priors = o.free_vel_bias = false;
+    o.algorithm = OSG_INERTIAL_GN;
+    o.iterations = 10;
+    o.huber_delta = 1.0;
+    return inertial_optimization<H>(vpKFs, maxKFid, o, Rwg, scale, nullptr, nullptr, false);
+}
+
 }  // namespace osg_orbslam3
 #endif

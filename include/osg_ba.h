@@ -171,6 +171,68 @@ int osg_pose_inertial_check(const osg_pose_inertial_problem *p);
 void osg_pose_inertial_informations(const float *C, const float *C_rw, double *info9, double *info_g,
                                     double *info_a);
 
+/* ---- InertialOptimization ------------------------------------------------------------------
+ * Optimizer::InertialOptimization (ref:src/Optimizer.cc:3706-3898, 3910-4076, 4085-4197): the IMU
+ * initialisation of LocalMapping::InitializeIMU, the bias-only form of LoopClosing::MergeLocal2 and
+ * LocalMapping::ScaleRefinement as one problem type.  Per KeyFrame a fixed pose and a velocity; one gyro bias,
+ * one accelerometer bias, one gravity direction (2 unknowns, Rwg = Rwg ExpSO3(u0, u1, 0)) and one scale
+ * (s = s exp(u)) shared by every edge; one 9-row EdgeInertialGS (ref:src/G2oTypes.cc:692-837) per KeyFrame
+ * with a predecessor, EdgePriorAcc and EdgePriorGyro towards a zero prior.  g2o's Levenberg-Marquardt or
+ * Gauss-Newton runs inside one launch, one workgroup per problem, on the block-arrowhead system (a
+ * block-tridiagonal chain of velocity blocks bordered by the shared unknowns).  Parity with the reference is
+ * tolerance-based. */
+#define OSG_INERTIAL_LM 0
+#define OSG_INERTIAL_GN 1
+#define OSG_INERTIAL_MAX_KF 4096
+#define OSG_INERTIAL_MAX_ITERATIONS 1000
+
+typedef struct osg_inertial_problem {
+    int32_t n_kf;             /* KeyFrames with mnId <= maxKFid, in any order */
+    const double *Rwb;        /* 9 per KeyFrame, row-major: GetImuRotation().cast<double>() */
+    const double *twb;        /* 3 per KeyFrame: GetImuPosition().cast<double>() */
+    const double *v;          /* 3 per KeyFrame: GetVelocity().cast<double>() */
+    int32_t n_edges;          /* one per KeyFrame with a usable mPrevKF */
+    const int32_t *prev;      /* per edge: index of mPrevKF */
+    const int32_t *cur;       /* per edge: index of the KeyFrame that owns the preintegration */
+    const osg_pio_preintegrated *preint; /* per edge: mpImuPreintegrated */
+    double bg[3], ba[3];      /* start of the two bias vertices: vpKFs.front()'s bias in all three overloads */
+    double Rwg[9];            /* row-major start of VertexGDir */
+    double scale;             /* start of VertexScale */
+    double prior_g, prior_a;  /* informations of EdgePriorGyro / EdgePriorAcc (float arguments cast to double) */
+    int32_t has_priors;       /* the two prior edges exist (overloads 1 and 2) */
+    int32_t free_vel_bias;    /* velocities and both biases are free (!bFixedVel) */
+    int32_t free_gdir;        /* VertexGDir is free */
+    int32_t free_scale;       /* VertexScale is free (bMono) */
+    int32_t algorithm;        /* OSG_INERTIAL_LM or OSG_INERTIAL_GN */
+    int32_t iterations;       /* optimize(its): 200, 200, 10 in the reference */
+    double lambda_init;       /* setUserLambdaInit; 0: g2o's own 1e-5 * max |diag H| */
+    double huber_delta;       /* Huber delta of every inertial edge; 0: no robust kernel */
+} osg_inertial_problem;
+
+typedef struct osg_inertial_result {
+    double *v;                /* 3 per KeyFrame, in the problem's order; an edge-less KeyFrame keeps its bits */
+    double bg[3], ba[3], Rwg[9], scale;
+    double chi2_initial;      /* activeRobustChi2 of the first computeActiveErrors */
+    double chi2_final;        /* of the last accepted state */
+    int32_t iterations;       /* outer iterations run */
+    int32_t trials_rejected;  /* LM trials that were popped */
+    int32_t solve_failed;     /* a pivot of the block LDL^T was not positive at least once */
+    double *trace;            /* optional (NULL: not written): (chi2, lambda, trials) per iteration run, room for
+                                 3 * problem.iterations */
+} osg_inertial_result;
+
+/* Returns the number of iterations run or a negative OSG_E_* code.  OSG_E_INVALID (nothing written, the context
+ * stays usable): a null pointer, a negative count, more than OSG_INERTIAL_MAX_KF KeyFrames, an edge index out of
+ * range or prev == cur, a KeyFrame that is cur of two edges or prev of two edges, a cycle, an unknown algorithm,
+ * iterations outside [0, OSG_INERTIAL_MAX_ITERATIONS], nothing free. */
+int osg_inertial_optimization(struct osg_ctx *ctx, const osg_inertial_problem *p, osg_inertial_result *r);
+/* n independent problems in one launch.  Returns the summed iterations or a negative OSG_E_* code.  No reference
+ * counterpart. */
+int osg_inertial_optimization_batch(struct osg_ctx *ctx, const osg_inertial_problem *p, int32_t n,
+                                    osg_inertial_result *r);
+/* The argument checks alone (host only, needs no context): 0 or OSG_E_INVALID. */
+int osg_inertial_check(const osg_inertial_problem *p);
+
 /* ---- OptimizeSim3 --------------------------------------------------------------------------
  * Optimizer::OptimizeSim3 (ref:src/Optimizer.cc:4213-4512), LoopClosing's Sim3 refinement between two
  * KeyFrames: one free g2o::Sim3 vertex S12, per kept match a pair of fixed camera-frame points and the

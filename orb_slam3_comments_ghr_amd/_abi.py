@@ -249,6 +249,28 @@ OSG_PIO_LAST_KEYFRAME = 0
 OSG_PIO_LAST_FRAME = 1
 
 
+class OsgInertialProblem(C.Structure):
+    _fields_ = [
+        ("n_kf", i32), ("Rwb", P), ("twb", P), ("v", P), ("n_edges", i32), ("prev", P), ("cur", P), ("preint", P),
+        ("bg", f64 * 3), ("ba", f64 * 3), ("Rwg", f64 * 9), ("scale", f64), ("prior_g", f64), ("prior_a", f64),
+        ("has_priors", i32), ("free_vel_bias", i32), ("free_gdir", i32), ("free_scale", i32), ("algorithm", i32),
+        ("iterations", i32), ("lambda_init", f64), ("huber_delta", f64),
+    ]
+
+
+class OsgInertialResult(C.Structure):
+    _fields_ = [
+        ("v", P), ("bg", f64 * 3), ("ba", f64 * 3), ("Rwg", f64 * 9), ("scale", f64), ("chi2_initial", f64),
+        ("chi2_final", f64), ("iterations", i32), ("trials_rejected", i32), ("solve_failed", i32), ("trace", P),
+    ]
+
+
+OSG_INERTIAL_LM = 0
+OSG_INERTIAL_GN = 1
+OSG_INERTIAL_MAX_KF = 4096
+OSG_INERTIAL_MAX_ITERATIONS = 1000
+
+
 class OsgSim3Problem(C.Structure):
     _fields_ = [
         ("q", f64 * 4), ("t", f64 * 3), ("s", f64), ("fix_scale", i32), ("th2", f32),
@@ -410,6 +432,7 @@ EXPORTS = [
     "osg_lba_kernel_times", "osg_optimize_sim3", "osg_optimize_sim3_batch",
     "osg_pose_inertial_optimization", "osg_pose_inertial_optimization_batch", "osg_pose_inertial_check",
     "osg_pose_inertial_informations",
+    "osg_inertial_optimization", "osg_inertial_optimization_batch", "osg_inertial_check",
     "osg_sim3_ransac", "osg_sim3_ransac_batch", "osg_sim3_ransac_iterations",
     "osg_mlpnp_ransac", "osg_mlpnp_ransac_batch", "osg_mlpnp_ransac_parameters", "osg_mlpnp_check_samples",
     "osg_optimize_essential_graph", "osg_essgraph_correct_points", "osg_essgraph_kernel_times",
@@ -492,6 +515,10 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.osg_pose_inertial_check.argtypes = [C.POINTER(OsgPoseInertialProblem)]
     lib.osg_pose_inertial_informations.argtypes = [vp, vp, vp, vp, vp]
     lib.osg_pose_inertial_informations.restype = None
+    lib.osg_inertial_optimization.argtypes = [vp, C.POINTER(OsgInertialProblem), C.POINTER(OsgInertialResult)]
+    lib.osg_inertial_optimization_batch.argtypes = [vp, C.POINTER(OsgInertialProblem), i32,
+                                                    C.POINTER(OsgInertialResult)]
+    lib.osg_inertial_check.argtypes = [C.POINTER(OsgInertialProblem)]
     lib.osg_imu_preintegrate.argtypes = [vp, C.POINTER(OsgImuProblem), C.POINTER(OsgImuPreintegrated)]
     lib.osg_imu_preintegrate_batch.argtypes = [vp, C.POINTER(OsgImuProblem), i32, C.POINTER(OsgImuPreintegrated)]
     lib.osg_imu_preintegrate_check.argtypes = [C.POINTER(OsgImuProblem)]

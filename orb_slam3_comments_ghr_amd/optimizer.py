@@ -489,6 +489,14 @@ class Optimizer:
         any mixture)."""
         return run_pose_inertial(self.ctx, list(problems))
 
+    def InertialOptimization(self, problems):
+        """``Optimizer::InertialOptimization`` (ref:src/Optimizer.cc:3706-4197) for one InertialProblem or a list of
+        them (one launch, a workgroup per map).  ``inertial_initialization_problem``, ``inertial_bias_problem`` and
+        ``inertial_scale_refinement_problem`` set the options of the three overloads."""
+        single = isinstance(problems, InertialProblem)
+        out = run_inertial(self.ctx, [problems] if single else list(problems))
+        return out[0] if single else out
+
     def OptimizeSim3(self, problems):
         """``Optimizer::OptimizeSim3`` (ref:src/Optimizer.cc:4213-4512) for one Sim3Problem or a list of
         them (one launch, a workgroup per problem).  The caller nulls ``vpMatches1`` where ``pair_state``
@@ -1599,3 +1607,195 @@ def synth_pose_inertial_problem(rng, n_edges=300, mode=_abi.OSG_PIO_LAST_KEYFRAM
         obs[i, 2] = 0.0
     return PoseInertialProblem(mode, cur, prev, cams, bf, kind, Xw, _f32(obs), inv_level_sigma2(n_levels)[octv],
                                np.maximum(depth, 0.0).astype(np.float32), pre, C_rw, prior, rec_init, truth)
+
+
+# ------------------------------------------------------------------------------------- InertialOptimization
+@dataclass
+class InertialMap:
+    """What the three overloads of ``Optimizer::InertialOptimization`` read of a map: the KeyFrames with
+    ``mnId <= maxKFid`` (fixed IMU poses, velocities), one edge per KeyFrame with a usable ``mPrevKF``, and
+    ``vpKFs.front()``'s bias, the start of the bias vertices."""
+    Rwb: np.ndarray           # n x 3 x 3 double
+    twb: np.ndarray           # n x 3
+    v: np.ndarray             # n x 3
+    prev: np.ndarray          # per edge: index of mPrevKF
+    cur: np.ndarray           # per edge: index of the KeyFrame that owns the preintegration
+    preint: list              # per edge: Preintegrated (or anything with its float32 fields)
+    bg: np.ndarray = field(default_factory=lambda: np.zeros(3))
+    ba: np.ndarray = field(default_factory=lambda: np.zeros(3))
+
+    def __post_init__(self):
+        self.Rwb = np.ascontiguousarray(self.Rwb, np.float64).reshape(-1, 3, 3)
+        self.twb = np.ascontiguousarray(self.twb, np.float64).reshape(-1, 3)
+        self.v = np.ascontiguousarray(self.v, np.float64).reshape(-1, 3)
+        self.prev = np.ascontiguousarray(self.prev, np.int32).reshape(-1)
+        self.cur = np.ascontiguousarray(self.cur, np.int32).reshape(-1)
+        self.bg = np.ascontiguousarray(self.bg, np.float64).reshape(3)
+        self.ba = np.ascontiguousarray(self.ba, np.float64).reshape(3)
+        self.preint = list(self.preint)
+
+
+@dataclass
+class InertialProblem:
+    """One ``osg_inertial_problem`` (include/osg_ba.h)."""
+    map: InertialMap
+    Rwg: np.ndarray
+    scale: float
+    prior_g: float = 0.0
+    prior_a: float = 0.0
+    has_priors: bool = False
+    free_vel_bias: bool = True
+    free_gdir: bool = True
+    free_scale: bool = True
+    algorithm: int = _abi.OSG_INERTIAL_LM
+    iterations: int = 200
+    lambda_init: float = 0.0
+    huber_delta: float = 0.0
+
+    def __post_init__(self):
+        self.Rwg = np.ascontiguousarray(self.Rwg, np.float64).reshape(3, 3)
+
+    @property
+    def n(self):
+        return len(self.map.twb)
+
+    def struct(self, keep):
+        """The C struct; ``keep`` collects the objects whose memory it points into."""
+        m = self.map
+        st = _abi.OsgInertialProblem()
+        st.n_kf, st.Rwb, st.twb, st.v = self.n, _p(m.Rwb), _p(m.twb), _p(m.v)
+        st.n_edges, st.prev, st.cur = len(m.prev), _p(m.prev), _p(m.cur)
+        if len(m.preint) != len(m.prev) or len(m.cur) != len(m.prev):
+            raise ValueError("one preintegration, one prev and one cur per edge")
+        if m.preint:
+            arr = (_abi.OsgPioPreintegrated * len(m.preint))()
+            for a, q in zip(arr, m.preint):
+                for k in ("dR", "dV", "dP", "JRg", "JVg", "JVa", "JPg", "JPa", "b", "C"):
+                    getattr(a, k)[:] = np.asarray(getattr(q, k), np.float32).ravel().tolist()
+                a.dT = float(q.dT)
+            keep.append(arr)
+            st.preint = C.addressof(arr)
+        st.bg[:], st.ba[:], st.Rwg[:] = m.bg.tolist(), m.ba.tolist(), self.Rwg.ravel().tolist()
+        st.scale, st.prior_g, st.prior_a = float(self.scale), float(self.prior_g), float(self.prior_a)
+        st.has_priors, st.free_vel_bias = int(bool(self.has_priors)), int(bool(self.free_vel_bias))
+        st.free_gdir, st.free_scale = int(bool(self.free_gdir)), int(bool(self.free_scale))
+        st.algorithm, st.iterations = int(self.algorithm), int(self.iterations)
+        st.lambda_init, st.huber_delta = float(self.lambda_init), float(self.huber_delta)
+        return st
+
+
+@dataclass
+class InertialResult:
+    v: np.ndarray             # n x 3, in the problem's KeyFrame order
+    bg: np.ndarray
+    ba: np.ndarray
+    Rwg: np.ndarray
+    scale: float
+    chi2_initial: float
+    chi2_final: float
+    iterations: int
+    trials_rejected: int
+    solve_failed: bool
+    trace: np.ndarray         # iterations x (chi2, lambda, trials)
+
+
+def inertial_initialization_problem(map, Rwg, scale, bg=None, ba=None, mono=True, fixed_vel=False, prior_g=1e2,
+                                    prior_a=1e6, iterations=200):
+    """Overload 1 (ref:src/Optimizer.cc:3706-3898): Levenberg-Marquardt, lambda_init 1e3 only if ``prior_g`` is not
+    zero, velocities and biases free unless ``fixed_vel``, the gravity direction free, the scale free only if
+    ``mono``.  ``bg`` / ``ba`` replace the map's (``vpKFs.front()``'s bias) when given."""
+    if bg is not None or ba is not None:
+        map = replace(map, bg=map.bg if bg is None else bg, ba=map.ba if ba is None else ba)
+    pg, pa = float(np.float32(prior_g)), float(np.float32(prior_a))
+    return InertialProblem(map, Rwg, scale, pg, pa, True, not fixed_vel, True, bool(mono), _abi.OSG_INERTIAL_LM,
+                           iterations, 1e3 if pg != 0.0 else 0.0, 0.0)
+
+
+def inertial_bias_problem(map, prior_g=1e2, prior_a=1e6, iterations=200):
+    """Overload 2 (ref:src/Optimizer.cc:3910-4076): Levenberg-Marquardt with lambda_init 1e3, the gravity direction
+    (identity) and the scale (1) fixed, velocities and biases free."""
+    pg, pa = float(np.float32(prior_g)), float(np.float32(prior_a))
+    return InertialProblem(map, np.eye(3), 1.0, pg, pa, True, True, False, False, _abi.OSG_INERTIAL_LM, iterations,
+                           1e3, 0.0)
+
+
+def inertial_scale_refinement_problem(map, Rwg, scale, iterations=10):
+    """Overload 3 (ref:src/Optimizer.cc:4085-4197): Gauss-Newton, only the gravity direction and the scale free,
+    Huber with delta 1 on every inertial edge, no prior edges."""
+    return InertialProblem(map, Rwg, scale, 0.0, 0.0, False, False, True, True, _abi.OSG_INERTIAL_GN, iterations,
+                           0.0, 1.0)
+
+
+def inertial_check(problem) -> int:
+    """``osg_inertial_check``: 0 or OSG_E_INVALID (host only, no context)."""
+    from . import load_library
+
+    keep = []
+    st = problem.struct(keep)
+    return load_library().osg_inertial_check(C.byref(st))
+
+
+def run_inertial(ctx, probs):
+    nb = len(probs)
+    keep = []
+    ps = (_abi.OsgInertialProblem * max(1, nb))(*[q.struct(keep) for q in probs])
+    rs = (_abi.OsgInertialResult * max(1, nb))()
+    vs = [np.zeros((q.n, 3), np.float64) for q in probs]
+    trs = [np.zeros((max(1, q.iterations), 3), np.float64) for q in probs]
+    for r, v, t in zip(rs, vs, trs):
+        r.v, r.trace = _p(v), _p(t)
+    ctx.check(ctx.lib.osg_inertial_optimization_batch(ctx.handle, ps, nb, rs), "InertialOptimization")
+    return [InertialResult(v, np.array(r.bg[:]), np.array(r.ba[:]), np.array(r.Rwg[:]).reshape(3, 3), r.scale,
+                           r.chi2_initial, r.chi2_final, r.iterations, r.trials_rejected, bool(r.solve_failed),
+                           t[:r.iterations].copy())
+            for r, v, t in zip(rs[:nb], vs, trs)]
+
+
+def initial_gravity_rotation(Rwb_prev, preint):
+    """The ``dirG`` -> ``Rwg`` start value of ``LocalMapping::InitializeIMU`` (ref:src/LocalMapping.cc:1606-1654) in
+    float32: ``Rwb_prev[i]`` is ``mPrevKF->GetImuRotation()`` and ``preint[i]`` the preintegration of the i-th
+    KeyFrame that has both.  Returns the 3 x 3 float32 ``Rwg``, or None where the reference gives up
+    (``have_imu_num < 6``).  ``GetUpdatedDeltaVelocity`` is ``dV + JVg db[0:3] + JVa db[3:6]`` with
+    ``db = bu - b`` (zero unless the preintegration carries a ``bu``)."""
+    f = np.float32
+    dirG = np.zeros(3, f)
+    n = 0
+    for R, q in zip(Rwb_prev, preint):
+        dV = np.asarray(q.dV, f)
+        bu = getattr(q, "bu", None)
+        if bu is not None:
+            b, bu = np.asarray(q.b, f), np.asarray(bu, f)
+            dV = dV + np.asarray(q.JVg, f) @ (bu[3:] - b[3:]) + np.asarray(q.JVa, f) @ (bu[:3] - b[:3])
+        dirG = dirG - np.asarray(R, f).reshape(3, 3) @ dV
+        n += 1
+    if n < 6:
+        return None
+    dirG = dirG / f(np.sqrt(f(dirG @ dirG)))
+    gI = np.array([0.0, 0.0, -1.0], f)
+    v = np.cross(gI, dirG).astype(f)
+    nv = f(np.sqrt(f(v @ v)))
+    ang = f(np.arccos(f(gI @ dirG)))
+    vzg = v * ang / nv
+    return _so3f_exp_matrix(vzg)
+
+
+def _so3f_exp_matrix(w):
+    """Sophus::SO3f::exp(w).matrix() in float32 (the unit quaternion of the half angle, then toRotationMatrix)."""
+    f = np.float32
+    w = np.asarray(w, f)
+    theta_sq = f(w @ w)
+    if theta_sq < f(1e-5) * f(1e-5):
+        po4 = f(theta_sq * theta_sq)
+        imag = f(0.5) - f(1.0 / 48.0) * theta_sq + f(1.0 / 3840.0) * po4
+        real = f(1.0) - f(1.0 / 8.0) * theta_sq + f(1.0 / 384.0) * po4
+    else:
+        theta = f(np.sqrt(theta_sq))
+        half = f(0.5) * theta
+        imag, real = f(np.sin(half)) / theta, f(np.cos(half))
+    x, y, z = (f(imag * c) for c in w)
+    tx, ty, tz = f(2) * x, f(2) * y, f(2) * z
+    twx, twy, twz = tx * real, ty * real, tz * real
+    txx, txy, txz = tx * x, ty * x, tz * x
+    tyy, tyz, tzz = ty * y, tz * y, tz * z
+    return np.array([[1 - (tyy + tzz), txy - twz, txz + twy], [txy + twz, 1 - (txx + tzz), tyz - twx],
+                     [txz - twy, tyz + twx, 1 - (txx + tyy)]], f)
