@@ -7,47 +7,13 @@ import pytest
 from orb_slam3_comments_ghr_amd import stereo as st
 from tests import oracle_calls as oc
 from tests import pyref_stereo as ps
-
-MBF = 47.9
+from tests.stereo_boundary_fixtures import check_hand, hand_frame
 
 
 def same(a, b):
     np.testing.assert_array_equal(np.asarray(a[0]).view(np.int32), np.asarray(b[0]).view(np.int32))
     np.testing.assert_array_equal(np.asarray(a[1]).view(np.int32), np.asarray(b[1]).view(np.int32))
     assert int(a[2]) == int(b[2])
-
-
-def hand_frame(noisy):
-    """40 x 80 single-level pair.  Columns < 44 of the right image are the left image shifted 4 px
-    (plus +-6 noise when `noisy`); columns >= 44 are identical and mirror-symmetric about column 60.
-    Keypoints (16, 10), (22, 20), (28, 30) match right keypoints 4 px to the left; keypoint (60, 20)
-    matches (60, 20) at zero disparity (noisy case only)."""
-    rng = np.random.default_rng(4242)
-    L = rng.integers(0, 256, (40, 80)).astype(np.int64)
-    for k in range(1, 16):
-        L[:, 60 + k] = L[:, 60 - k]
-    R = L.copy()
-    R[:, :44] = L[:, 4:48] + (rng.integers(-6, 7, (40, 44)) if noisy else 0)
-    L, R = (np.clip(a, 0, 255).astype(np.uint8) for a in (L, R))
-    u = [16.0, 22.0, 28.0] + ([60.0] if noisy else [])
-    v = [10.0, 20.0, 30.0] + ([20.0] if noisy else [])
-    ur = [x - 4 for x in u[:3]] + ([60.0] if noisy else [])
-    desc = rng.integers(0, 256, (len(u), 32), dtype=np.uint8)
-    one = st.ImagePyramid
-    return st.StereoFrame(desc=desc, x=u, y=v, octave=np.zeros(len(u)), desc_r=desc.copy(), xr=ur, yr=v,
-                          octave_r=np.zeros(len(u)), left=one([L]), right=one([R]), scale=[1.0], mbf=MBF)
-
-
-def check_hand(res):
-    """noise-free: every SAD minimum is 0, so the median is 0 and `dist < 0` never holds — the
-    reference's cut removes every match.  Noisy: the three shifted matches land within half a pixel
-    of 4 px, the zero-disparity one takes the 0.01 clamp (bestuR = uL - 0.01 in double)."""
-    (ur0, d0, n0), (ur1, d1, n1) = res
-    assert n0 == 0 and (ur0 == -1).all() and (d0 == -1).all()
-    assert n1 == 4
-    np.testing.assert_allclose(ur1[:3], [12, 18, 24], atol=0.5)
-    np.testing.assert_array_equal(d1[:3], (np.float32(MBF) / (np.float32([16, 22, 28]) - ur1[:3])).astype(np.float32))
-    assert ur1[3] == np.float32(60.0 - 0.01) and d1[3] == np.float32(np.float32(MBF) / np.float32(0.01))
 
 
 @pytest.mark.parametrize("seed", range(3))
