@@ -30,7 +30,7 @@ RANSAC_HDRS = $(CSRC)/ransac_common.h $(CSRC)/batch_io.h $(CSRC)/glibc_math.h $(
 # the pointer-binding packer and the launch sequence of the entry points built on it
 PACKED_HDRS = $(CSRC)/match_common.h $(CSRC)/packed_launch.h
 
-OBJS = $(OBJDIR)/runtime.o $(OBJDIR)/hamming.o $(OBJDIR)/hamming_mfma.o $(OBJDIR)/match.o $(OBJDIR)/pose.o $(OBJDIR)/poseinertial.o $(OBJDIR)/inertialopt.o $(OBJDIR)/preintegrate.o $(OBJDIR)/sim3opt.o $(OBJDIR)/sim3ransac.o $(OBJDIR)/mlpnp.o $(OBJDIR)/twoview.o $(OBJDIR)/essgraph.o $(OBJDIR)/ba.o $(OBJDIR)/dbow.o $(OBJDIR)/kfdb.o $(OBJDIR)/fuse.o $(OBJDIR)/triang.o $(OBJDIR)/newpoints.o $(OBJDIR)/frustum.o $(OBJDIR)/desc.o $(OBJDIR)/sim3.o $(OBJDIR)/init.o $(OBJDIR)/stereo.o $(OBJDIR)/orb.o $(OBJDIR)/fast.o $(OBJDIR)/pyramid.o
+OBJS = $(OBJDIR)/runtime.o $(OBJDIR)/hamming.o $(OBJDIR)/hamming_mfma.o $(OBJDIR)/match.o $(OBJDIR)/pose.o $(OBJDIR)/poseinertial.o $(OBJDIR)/inertialopt.o $(OBJDIR)/localinertialba.o $(OBJDIR)/preintegrate.o $(OBJDIR)/sim3opt.o $(OBJDIR)/sim3ransac.o $(OBJDIR)/mlpnp.o $(OBJDIR)/twoview.o $(OBJDIR)/essgraph.o $(OBJDIR)/ba.o $(OBJDIR)/dbow.o $(OBJDIR)/kfdb.o $(OBJDIR)/fuse.o $(OBJDIR)/triang.o $(OBJDIR)/newpoints.o $(OBJDIR)/frustum.o $(OBJDIR)/desc.o $(OBJDIR)/sim3.o $(OBJDIR)/init.o $(OBJDIR)/stereo.o $(OBJDIR)/orb.o $(OBJDIR)/fast.o $(OBJDIR)/pyramid.o
 
 WALL_BENCH = tools/adapter_wall_bench
 
@@ -52,6 +52,8 @@ $(OBJDIR)/pose.o: $(CSRC)/pose.hip $(HDRS) $(CSRC)/ba_common.h $(CSRC)/exact_mat
 $(OBJDIR)/poseinertial.o: $(CSRC)/poseinertial.hip $(HDRS) $(CSRC)/ba_common.h $(CSRC)/poseinertial_common.h $(SO3_HDRS) $(CSRC)/exact_math.h $(RANSAC_HDRS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
 $(OBJDIR)/inertialopt.o: $(CSRC)/inertialopt.hip $(HDRS) $(CSRC)/ba_common.h $(CSRC)/inertialopt_common.h $(CSRC)/poseinertial_common.h $(SO3_HDRS) $(CSRC)/exact_math.h $(CSRC)/batch_io.h | $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
+$(OBJDIR)/localinertialba.o: $(CSRC)/localinertialba.hip $(HDRS) $(CSRC)/ba_common.h $(CSRC)/inertialba_edges.h $(CSRC)/localinertialba_common.h $(CSRC)/poseinertial_common.h $(SO3_HDRS) $(CSRC)/exact_math.h $(CSRC)/glibc_math.h $(CSRC)/batch_io.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@
 $(OBJDIR)/preintegrate.o: $(CSRC)/preintegrate.hip $(HDRS) $(CSRC)/imu_common.h $(SO3_HDRS) $(CSRC)/batch_io.h | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(EXACT) -c $< -o $@

@@ -136,4 +136,13 @@ void Optimizer::OptimizeEssentialGraph4DoF(Map *pMap, KeyFrame *pLoopKF, KeyFram
                                                           LoopConnections);
 }
 
+void Optimizer::LocalInertialBA(KeyFrame *pKF, bool *pbStopFlag, Map *pMap, int &num_fixedKF, int &num_OptKF,
+                                int &num_MPs, int &num_edges, bool bLarge, bool bRecInit)
+{  // ref:src/Optimizer.cc:2221-2816 (LocalMapping::Run once the IMU is initialised); the stop flag is set after
+   // optimize() in the reference and never read, and the four counters are never written there
+    auto out = osg_orbslam3::local_inertial_ba<OsgHooks, KeyFrame, MapPoint>(pKF, bLarge, bRecInit);
+    std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);  // :2746
+    osg_orbslam3::apply_local_inertial_ba<OsgHooks>(out, pMap);
+}
+
 }  // namespace ORB_SLAM3

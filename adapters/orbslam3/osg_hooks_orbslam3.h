@@ -474,6 +474,62 @@ struct OsgHooks {
             putv(-Rcb1.transpose() * tcb1, p.cams[1].tbc);
         }
     }
+    // ImuCamPose(KeyFrame*) (ref:src/G2oTypes.cc:34-78)
+    static void liba_cameras(KeyFrame &K, osg_liba_keyframe &k)
+    {
+        auto put3 = [](const Eigen::Matrix3d &M, double *o) {
+            for (int r = 0; r < 3; r++)
+                for (int c = 0; c < 3; c++) o[3 * r + c] = M(r, c);
+        };
+        auto putv = [](const Eigen::Vector3d &v, double *o) {
+            for (int r = 0; r < 3; r++) o[r] = v(r);
+        };
+        k.n_cams = K.mpCamera2 ? 2 : 1;
+        const Eigen::Vector3d tcw0 = K.GetTranslation().cast<double>();
+        const Eigen::Matrix3d Rcw0 = K.GetRotation().cast<double>();
+        const Eigen::Vector3d tcb0 = K.mImuCalib.mTcb.translation().cast<double>();
+        const Eigen::Matrix3d Rcb0 = K.mImuCalib.mTcb.rotationMatrix().cast<double>();
+        camera(K, false, k.cams[0].cam);
+        put3(Rcw0, k.cams[0].Rcw), putv(tcw0, k.cams[0].tcw), put3(Rcb0, k.cams[0].Rcb), putv(tcb0, k.cams[0].tcb);
+        putv(K.mImuCalib.mTbc.translation().cast<double>(), k.cams[0].tbc);
+        k.bf = K.mbf;
+        if (k.n_cams > 1) {
+            const Eigen::Matrix4d Trl = K.GetRelativePoseTrl().matrix().cast<double>();
+            const Eigen::Matrix3d Rrl = Trl.block<3, 3>(0, 0);
+            const Eigen::Vector3d trl = Trl.block<3, 1>(0, 3);
+            const Eigen::Matrix3d Rcb1 = Rrl * Rcb0;
+            const Eigen::Vector3d tcb1 = Rrl * tcb0 + trl;
+            camera(K, true, k.cams[1].cam);
+            put3(Rrl * Rcw0, k.cams[1].Rcw), putv(Rrl * tcw0 + trl, k.cams[1].tcw);
+            put3(Rcb1, k.cams[1].Rcb), putv(tcb1, k.cams[1].tcb);
+            putv(-Rcb1.transpose() * tcb1, k.cams[1].tbc);
+        }
+    }
+    static void preint_take_prev_bias(KeyFrame &K) { K.mpImuPreintegrated->SetNewBias(K.mPrevKF->GetImuBias()); }
+    static void keypoint_un(KeyFrame &K, int i, float xy[2], int &octave)
+    {
+        const cv::KeyPoint &kp = K.mvKeysUn[i];
+        xy[0] = kp.pt.x, xy[1] = kp.pt.y, octave = kp.octave;
+    }
+    static void keypoint_right(KeyFrame &K, int i, float xy[2])
+    {
+        const cv::KeyPoint &kp = K.mvKeysRight[i];
+        xy[0] = kp.pt.x, xy[1] = kp.pt.y;
+    }
+    static float uncertainty2(KeyFrame &K, float x, float y)
+    {
+        return K.mpCamera->uncertainty2(Eigen::Matrix<double, 2, 1>((double)x, (double)y));
+    }
+    static void mp_update_normal_and_depth(MapPoint *pMP) { pMP->UpdateNormalAndDepth(); }
+    static void kf_set_pose_rt(KeyFrame &K, const float R[9], const float t[3])
+    {
+        K.SetPose(Sophus::SE3f(mat3(R), vec3(t)));
+    }
+    static void erase_match(KeyFrame *pKF, MapPoint *pMP)
+    {
+        pKF->EraseMapPointMatch(pMP);
+        pMP->EraseObservation(pKF);
+    }
     static void preintegrated(IMU::Preintegrated *pInt, osg_pio_preintegrated &q)
     {
         auto put3 = [](const Eigen::Matrix3f &M, float *o) {

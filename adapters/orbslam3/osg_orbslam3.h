@@ -4421,5 +4421,244 @@ bool inertial_optimization_scale(const std::vector<KeyFrameT *> &vpKFs, unsigned
     return inertial_optimization<H>(vpKFs, maxKFid, o, Rwg, scale, nullptr, nullptr, false);
 }
 
+// ------------------------------------------------- a10h LocalInertialBA
+// ref:src/Optimizer.cc:2221-2816.  The reference's host side restated with its quirks:
+//   * window selection (:2226-2292): up to Nd = min(KeyFramesInMap() - 2, 10 | 25) KeyFrames down the mPrevKF chain;
+//     the oldest one's mPrevKF is the first fixed KeyFrame, or, when it has none, the oldest one itself is popped
+//     into the fixed list (and "i == N - 1" below is taken after that pop);
+//   * maxCovKF = 0: lpOptVisKFs stays empty and marks nothing;
+//   * the fixed-KeyFrame walk (:2331-2350) iterates GetObservations() in its std::map order (pointer order), marks
+//     mnBAFixedForKF before the isBad() test, takes the first new fixed KeyFrame per point and stops at 200;
+//   * the edges (:2562-2688): uncertainty2 from the left camera for right observations too, and the right
+//     observation's inv_sigma2 from the octave of the left keypoint (octave 0 of a default cv::KeyPoint when
+//     leftIndex == -1);
+//   * SetNewBias(mPrevKF->GetImuBias()) on the preintegration before the link is read;
+//   * failed: return before any write, mnBALocalForKF / mnBAFixedForKF left as they are;
+//   * write-back (:2756-2815): the erasures first (mono edges, then stereo), SetPose from camera 0's float casts,
+//     SetVelocity, SetNewBias(IMU::Bias(b[3], b[4], b[5], b[0], b[1], b[2])), SetWorldPos, UpdateNormalAndDepth,
+//     IncreaseChangeIndex.
+// The types need the reference's members (mnId, mPrevKF, mnBALocalForKF, mnBAFixedForKF, bImu, mpImuPreintegrated,
+// mvuRight, NLeft, mpCamera2, mvInvLevelSigma2, GetMap, isBad, GetMapPointMatches, GetObservations, KeyFramesInMap,
+// IncreaseChangeIndex) and the hooks
+//   H::imu_state(KeyFrame&, osg_pio_state&), H::liba_cameras(KeyFrame&, osg_liba_keyframe&)   ImuCamPose(KeyFrame*)
+//   H::preint_take_prev_bias(KeyFrame&)            mpImuPreintegrated->SetNewBias(mPrevKF->GetImuBias())
+//   H::preintegrated(pInt, osg_pio_preintegrated&)
+//   H::keypoint_un(KeyFrame&, int, float xy[2], int &octave), H::keypoint_right(KeyFrame&, int, float xy[2])
+//   H::uncertainty2(KeyFrame&, float x, float y)   mpCamera->uncertainty2
+//   H::mp_world_pos, H::track_depth, H::mp_set_world_pos, H::mp_update_normal_and_depth(MapPoint*)
+//   H::kf_set_pose_rt(KeyFrame&, const float Rcw[9], const float tcw[3]), H::set_velocity, H::set_new_bias
+//   H::erase_match(KeyFrame*, MapPoint*)           EraseMapPointMatch + EraseObservation
+template <class H, class KeyFrameT, class MapPointT>
+struct LocalInertialBAGather {
+    std::vector<KeyFrameT *> opt_kfs, fixed_kfs;  // vpOptimizableKFs after the pop | lFixedKeyFrames
+    std::vector<MapPointT *> points;              // lLocalMapPoints
+    std::vector<osg_liba_keyframe> kf;            // the optimizable ones, then the fixed ones
+    std::vector<double> xw, obs;
+    std::vector<float> depth, w;
+    std::vector<int32_t> ep, ek;
+    std::vector<int8_t> kind;
+    std::vector<osg_liba_link> links;
+    osg_local_inertial_ba_problem p{};
+
+    void select(KeyFrameT *pKF, bool bLarge)
+    {
+        auto *pCurrentMap = pKF->GetMap();
+        const int maxOpt = bLarge ? 25 : 10;
+        const int Nd = std::min((int)pCurrentMap->KeyFramesInMap() - 2, maxOpt);
+        opt_kfs.push_back(pKF);
+        pKF->mnBALocalForKF = pKF->mnId;
+        for (int i = 1; i < Nd; i++) {
+            if (!opt_kfs.back()->mPrevKF) break;
+            opt_kfs.push_back(opt_kfs.back()->mPrevKF);
+            opt_kfs.back()->mnBALocalForKF = pKF->mnId;
+        }
+        for (KeyFrameT *pKFi : opt_kfs)
+            for (MapPointT *pMP : pKFi->GetMapPointMatches())
+                if (pMP && !pMP->isBad() && pMP->mnBALocalForKF != pKF->mnId) {
+                    points.push_back(pMP);
+                    pMP->mnBALocalForKF = pKF->mnId;
+                }
+        if (opt_kfs.back()->mPrevKF) {
+            fixed_kfs.push_back(opt_kfs.back()->mPrevKF);
+            opt_kfs.back()->mPrevKF->mnBAFixedForKF = pKF->mnId;
+        } else {
+            opt_kfs.back()->mnBALocalForKF = 0;
+            opt_kfs.back()->mnBAFixedForKF = pKF->mnId;
+            fixed_kfs.push_back(opt_kfs.back());
+            opt_kfs.pop_back();
+        }
+        const size_t maxFixKF = 200;
+        for (MapPointT *pMP : points) {
+            const auto observations = pMP->GetObservations();
+            for (const auto &ob : observations) {
+                KeyFrameT *pKFi = ob.first;
+                if (pKFi->mnBALocalForKF != pKF->mnId && pKFi->mnBAFixedForKF != pKF->mnId) {
+                    pKFi->mnBAFixedForKF = pKF->mnId;
+                    if (!pKFi->isBad()) {
+                        fixed_kfs.push_back(pKFi);
+                        break;
+                    }
+                }
+            }
+            if (fixed_kfs.size() >= maxFixKF) break;
+        }
+    }
+
+    void build(KeyFrameT *pKF, bool bLarge, bool bRecInit)
+    {
+        select(pKF, bLarge);
+        auto *pCurrentMap = pKF->GetMap();
+        std::unordered_map<KeyFrameT *, int32_t> index;
+        auto vertex = [&](KeyFrameT *pKFi, bool fixed) {
+            osg_liba_keyframe k{};
+            H::imu_state(*pKFi, k.state);
+            H::liba_cameras(*pKFi, k);
+            k.fixed = fixed;
+            index[pKFi] = (int32_t)kf.size();
+            kf.push_back(k);
+        };
+        for (KeyFrameT *pKFi : opt_kfs) vertex(pKFi, false);
+        for (KeyFrameT *pKFi : fixed_kfs) vertex(pKFi, true);
+        const int N = (int)opt_kfs.size();
+        for (int i = 0; i < N; i++) {
+            KeyFrameT *pKFi = opt_kfs[i];
+            if (!pKFi->mPrevKF) {
+                std::cout << "NOT INERTIAL LINK TO PREVIOUS FRAME!!!!" << std::endl;
+                continue;
+            }
+            if (!(pKFi->bImu && pKFi->mPrevKF->bImu && pKFi->mpImuPreintegrated)) {
+                std::cout << "ERROR building inertial edge" << std::endl;
+                continue;
+            }
+            H::preint_take_prev_bias(*pKFi);
+            const auto it = index.find(pKFi->mPrevKF);
+            if (it == index.end()) continue;  // the reference's "Error" continue: a vertex is missing
+            osg_liba_link L{};
+            L.prev = it->second, L.cur = index[pKFi];
+            L.huber = (i == N - 1 || bRecInit), L.downweight = (i == N - 1);
+            H::preintegrated(pKFi->mpImuPreintegrated, L.preint);
+            links.push_back(L);
+        }
+        auto edge = [&](int point, KeyFrameT *pKFi, int kd, float x, float y, float ur, int octave) {
+            const float unc2 = H::uncertainty2(*pKFi, x, y);
+            ep.push_back(point), ek.push_back(index[pKFi]), kind.push_back((int8_t)kd);
+            obs.push_back((double)x), obs.push_back((double)y), obs.push_back((double)ur);
+            w.push_back(pKFi->mvInvLevelSigma2[octave] / unc2);
+        };
+        for (size_t q = 0; q < points.size(); q++) {
+            MapPointT *pMP = points[q];
+            float x[3];
+            H::mp_world_pos(pMP, x);
+            for (int i = 0; i < 3; i++) xw.push_back((double)x[i]);
+            depth.push_back(H::track_depth(pMP));
+            const auto observations = pMP->GetObservations();
+            for (const auto &ob : observations) {
+                KeyFrameT *pKFi = ob.first;
+                if (pKFi->mnBALocalForKF != pKF->mnId && pKFi->mnBAFixedForKF != pKF->mnId) continue;
+                if (pKFi->isBad() || pKFi->GetMap() != pCurrentMap) continue;
+                if (index.find(pKFi) == index.end()) continue;  // marked past the 200 limit: the reference has no vertex
+                const int leftIndex = std::get<0>(ob.second);
+                int octave = 0;  // of a default cv::KeyPoint
+                float xy[2];
+                if (leftIndex != -1) {
+                    H::keypoint_un(*pKFi, leftIndex, xy, octave);
+                    if (pKFi->mvuRight[leftIndex] < 0)
+                        edge((int)q, pKFi, OSG_EDGE_MONO, xy[0], xy[1], 0.f, octave);
+                    else
+                        edge((int)q, pKFi, OSG_EDGE_STEREO, xy[0], xy[1], pKFi->mvuRight[leftIndex], octave);
+                }
+                if (pKFi->mpCamera2) {
+                    int rightIndex = std::get<1>(ob.second);
+                    if (rightIndex != -1) {
+                        rightIndex -= pKFi->NLeft;
+                        H::keypoint_right(*pKFi, rightIndex, xy);
+                        edge((int)q, pKFi, OSG_EDGE_BODY, xy[0], xy[1], 0.f, octave);  // the left keypoint's octave
+                    }
+                }
+            }
+        }
+        p = osg_local_inertial_ba_problem{};
+        p.n_kf = (int32_t)kf.size(), p.kf = kf.data();
+        p.n_points = (int32_t)points.size(), p.xw = xw.data(), p.track_depth = depth.data();
+        p.n_edges = (int32_t)ep.size(), p.e_point = ep.data(), p.e_kf = ek.data(), p.e_kind = kind.data();
+        p.e_obs = obs.data(), p.e_inv_sigma2 = w.data();
+        p.n_links = (int32_t)links.size(), p.links = links.data();
+        p.iterations = bLarge ? 4 : 10, p.large = bLarge, p.lambda_init = bLarge ? 1e-2 : 1e0;
+    }
+};
+
+// What the call returned, for the write-back
+template <class KeyFrameT, class MapPointT>
+struct LocalInertialBAOut {
+    bool ok = false, failed = false;
+    std::vector<KeyFrameT *> opt_kfs, fixed_kfs;
+    std::vector<MapPointT *> points;
+    std::vector<std::pair<KeyFrameT *, MapPointT *>> erase;  // vToErase: mono edges first, then stereo
+    std::vector<osg_pio_state> state;
+    std::vector<double> Rcw, tcw, xw;
+};
+
+template <class H, class KeyFrameT, class MapPointT>
+LocalInertialBAOut<KeyFrameT, MapPointT> local_inertial_ba(KeyFrameT *pKF, bool bLarge, bool bRecInit)
+{
+    LocalInertialBAOut<KeyFrameT, MapPointT> out;
+    LocalInertialBAGather<H, KeyFrameT, MapPointT> g;
+    g.build(pKF, bLarge, bRecInit);
+    out.opt_kfs = g.opt_kfs, out.fixed_kfs = g.fixed_kfs, out.points = g.points;
+    const size_t nk = g.kf.size(), ne = g.ep.size();
+    out.state.resize(nk), out.Rcw.resize(9 * nk), out.tcw.resize(3 * nk), out.xw.resize(3 * g.points.size());
+    std::vector<uint8_t> bad(ne);
+    osg_local_inertial_ba_result r{};
+    r.state = out.state.data(), r.Rcw = out.Rcw.data(), r.tcw = out.tcw.data(), r.xw = out.xw.data();
+    r.edge_bad = bad.data();
+    osg_ctx *ctx = thread_ctx();
+    if (call(ctx, "osg_local_inertial_ba", [&] { return osg_local_inertial_ba(ctx, &g.p, &r); }) < 0) return out;
+    out.ok = true;
+    out.failed = r.failed != 0;
+    std::vector<KeyFrameT *> all(g.opt_kfs);
+    all.insert(all.end(), g.fixed_kfs.begin(), g.fixed_kfs.end());
+    for (int pass = 0; pass < 2; pass++)  // vpEdgesMono (EdgeMono(0) and EdgeMono(1)), then vpEdgesStereo
+        for (size_t i = 0; i < ne; i++) {
+            if ((g.kind[i] == OSG_EDGE_STEREO) != (pass == 1)) continue;
+            MapPointT *pMP = g.points[g.ep[i]];
+            if (pMP->isBad()) continue;
+            if (bad[i]) out.erase.push_back(std::make_pair(all[g.ek[i]], pMP));
+        }
+    return out;
+}
+
+// the write-back, under the caller's map lock; nothing when the call failed or the reference's `failed` rule fired
+template <class H, class KeyFrameT, class MapPointT, class MapT>
+void apply_local_inertial_ba(const LocalInertialBAOut<KeyFrameT, MapPointT> &out, MapT *pMap)
+{
+    if (!out.ok || out.failed) {
+        if (out.ok) std::cout << "FAIL LOCAL-INERTIAL BA!!!!" << std::endl;
+        return;
+    }
+    for (const auto &e : out.erase) H::erase_match(e.first, e.second);
+    for (KeyFrameT *pKFi : out.fixed_kfs) pKFi->mnBAFixedForKF = 0;
+    for (size_t i = 0; i < out.opt_kfs.size(); i++) {
+        KeyFrameT *pKFi = out.opt_kfs[i];
+        float R[9], t[3];
+        for (int k = 0; k < 9; k++) R[k] = (float)out.Rcw[9 * i + k];
+        for (int k = 0; k < 3; k++) t[k] = (float)out.tcw[3 * i + k];
+        H::kf_set_pose_rt(*pKFi, R, t);
+        pKFi->mnBALocalForKF = 0;
+        if (pKFi->bImu) {
+            const osg_pio_state &s = out.state[i];
+            H::set_velocity(*pKFi, s.v);
+            // b << VG, VA; IMU::Bias(b[3], b[4], b[5], b[0], b[1], b[2]): floats, (ba, bg)
+            const float b[6] = {(float)s.ba[0], (float)s.ba[1], (float)s.ba[2], (float)s.bg[0], (float)s.bg[1], (float)s.bg[2]};
+            H::set_new_bias(*pKFi, b);
+        }
+    }
+    for (size_t q = 0; q < out.points.size(); q++) {
+        const float x[3] = {(float)out.xw[3 * q], (float)out.xw[3 * q + 1], (float)out.xw[3 * q + 2]};
+        H::mp_set_world_pos(out.points[q], x);
+        H::mp_update_normal_and_depth(out.points[q]);
+    }
+    pMap->IncreaseChangeIndex();
+}
+
 }  // namespace osg_orbslam3
 #endif

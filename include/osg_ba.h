@@ -233,6 +233,88 @@ int osg_inertial_optimization_batch(struct osg_ctx *ctx, const osg_inertial_prob
 /* The argument checks alone (host only, needs no context): 0 or OSG_E_INVALID. */
 int osg_inertial_check(const osg_inertial_problem *p);
 
+/* ---- LocalInertialBA -----------------------------------------------------------------------
+ * The g2o part of Optimizer::LocalInertialBA (ref:src/Optimizer.cc:2356-2743): what LocalMapping::Run calls in
+ * place of LocalBundleAdjustment once the IMU is initialised.  Per KeyFrame a VertexPose (ImuCamPose),
+ * VertexVelocity, VertexGyroBias and VertexAccBias, free (15 unknowns) or fixed; per MapPoint a marginalised
+ * VertexSBAPointXYZ; per observation an EdgeMono / EdgeStereo (ref:src/G2oTypes.cc:398-436, 469-499) with a
+ * Huber kernel (sqrt(5.991) / sqrt(7.815), held as floats); per inertial link one EdgeInertial over six
+ * vertices, one EdgeGyroRW and one EdgeAccRW.  g2o's Levenberg-Marquardt over BlockSolverX with the points
+ * eliminated runs inside one launch, one workgroup per window.  Everything is gathered by the
+ * caller in the reference's insertion order.  Parity with the reference is tolerance-based. */
+#define OSG_LIBA_MAX_FREE_KF 32
+#define OSG_LIBA_MAX_FIXED_KF 512
+#define OSG_LIBA_MAX_POINTS 65536
+#define OSG_LIBA_MAX_EDGES 524288
+#define OSG_LIBA_MAX_PAIRS 16777216 /* sum over the points of (edges on free KeyFrames)^2 */
+#define OSG_LIBA_MAX_ITERATIONS 100
+
+typedef struct osg_liba_keyframe {
+    osg_pio_state state;      /* GetImuRotation / GetImuPosition / GetVelocity / GetGyroBias / GetAccBias in double */
+    int32_t fixed;            /* 0: 15 unknowns (pose 6, v 3, bg 3, ba 3); else every vertex of it is fixed */
+    int32_t n_cams;           /* 1, or 2 when mpCamera2 */
+    osg_pio_camera cams[2];   /* ImuCamPose(KeyFrame*); Rcw / tcw are read as passed until the first update */
+    double bf;                /* mbf cast to double */
+} osg_liba_keyframe;
+
+typedef struct osg_liba_link {
+    int32_t prev, cur;        /* KeyFrame indices: mPrevKF and the KeyFrame that owns the preintegration */
+    int32_t huber;            /* RobustKernelHuber with delta sqrt(16.92) on the EdgeInertial (i == N - 1 || bRecInit) */
+    int32_t downweight;       /* EdgeInertial's information times 1e-2 (i == N - 1) */
+    osg_pio_preintegrated preint; /* after SetNewBias(mPrevKF->GetImuBias()); the informations come from its C */
+} osg_liba_link;
+
+typedef struct osg_local_inertial_ba_problem {
+    int32_t n_kf;
+    const osg_liba_keyframe *kf;
+    int32_t n_points;
+    const double *xw;          /* 3 per point: GetWorldPos().cast<double>() */
+    const float *track_depth;  /* per point: mTrackDepth (the classification of mono edges) */
+    int32_t n_edges;           /* visual edges in insertion order */
+    const int32_t *e_point;
+    const int32_t *e_kf;
+    const int8_t *e_kind;      /* OSG_EDGE_MONO: EdgeMono(0); OSG_EDGE_STEREO: EdgeStereo(0); OSG_EDGE_BODY: EdgeMono(1) */
+    const double *e_obs;       /* 3 per edge: (u, v, ur), ur read for STEREO only */
+    const float *e_inv_sigma2; /* mvInvLevelSigma2[octave] / uncertainty2 */
+    int32_t n_links;
+    const osg_liba_link *links;
+    int32_t iterations;        /* optimize(opt_it): 10, or 4 when large */
+    int32_t large;             /* bLarge: `failed` is never set */
+    double lambda_init;        /* setUserLambdaInit: 1e0, or 1e-2 when large; must be positive */
+} osg_local_inertial_ba_problem;
+
+typedef struct osg_local_inertial_ba_result {
+    osg_pio_state *state;      /* n_kf; a fixed KeyFrame's is bit-equal to its input, and so are v, bg, ba of a
+                                  free KeyFrame without a link */
+    double *Rcw;               /* 9 per KeyFrame: camera 0, for SetPose */
+    double *tcw;               /* 3 per KeyFrame */
+    double *xw;                /* 3 per point */
+    uint8_t *edge_bad;         /* n_edges: the function's own erase rule (ref:src/Optimizer.cc:2713-2743) */
+    double *edge_chi2;         /* optional (NULL: not written), n_edges: e->chi2() of the last computed errors */
+    double chi2_initial;       /* err: activeRobustChi2 before optimize() */
+    double chi2_last;          /* err_end: activeRobustChi2 of the last computed errors (a popped trial's included) */
+    double chi2_accepted;      /* of the last accepted state */
+    int32_t iterations;        /* outer iterations run */
+    int32_t trials_rejected;
+    int32_t solve_failed;      /* a pivot of the reduced system's Cholesky factor was not positive at least once */
+    int32_t failed;            /* (2 * err < err_end || isnan(err) || isnan(err_end)) && !large, on the float casts */
+    double *trace;             /* optional: (chi2, lambda, trials) per iteration run, room for 3 * iterations */
+} osg_local_inertial_ba_result;
+
+/* Returns the number of iterations run or a negative OSG_E_* code.  OSG_E_INVALID (nothing uploaded, nothing
+ * written, the context stays usable): a null pointer, a negative count, a count above the caps above, an index out
+ * of range, a link with prev == cur, a KeyFrame that is cur of two links, n_cams outside {1, 2}, a BODY edge on a
+ * one-camera KeyFrame, an unknown edge kind, more than OSG_LIBA_MAX_PAIRS edge pairs, iterations outside
+ * [0, OSG_LIBA_MAX_ITERATIONS], a lambda_init that is not positive, no free KeyFrame. */
+int osg_local_inertial_ba(struct osg_ctx *ctx, const osg_local_inertial_ba_problem *p,
+                          osg_local_inertial_ba_result *r);
+/* n independent windows in one launch, each with its own lambda, decisions and stop; bit-equal to the single
+ * calls.  Returns the summed iterations or a negative OSG_E_* code.  No reference counterpart. */
+int osg_local_inertial_ba_batch(struct osg_ctx *ctx, const osg_local_inertial_ba_problem *p, int32_t n,
+                                osg_local_inertial_ba_result *r);
+/* The argument checks alone (host only, needs no context): 0 or OSG_E_INVALID. */
+int osg_local_inertial_ba_check(const osg_local_inertial_ba_problem *p);
+
 /* ---- OptimizeSim3 --------------------------------------------------------------------------
  * Optimizer::OptimizeSim3 (ref:src/Optimizer.cc:4213-4512), LoopClosing's Sim3 refinement between two
  * KeyFrames: one free g2o::Sim3 vertex S12, per kept match a pair of fixed camera-frame points and the

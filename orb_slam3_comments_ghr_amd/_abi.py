@@ -271,6 +271,38 @@ OSG_INERTIAL_MAX_KF = 4096
 OSG_INERTIAL_MAX_ITERATIONS = 1000
 
 
+class OsgLibaKeyframe(C.Structure):
+    _fields_ = [("state", OsgPioState), ("fixed", i32), ("n_cams", i32), ("cams", OsgPioCamera * 2), ("bf", f64)]
+
+
+class OsgLibaLink(C.Structure):
+    _fields_ = [("prev", i32), ("cur", i32), ("huber", i32), ("downweight", i32), ("preint", OsgPioPreintegrated)]
+
+
+class OsgLocalInertialBaProblem(C.Structure):
+    _fields_ = [
+        ("n_kf", i32), ("kf", P), ("n_points", i32), ("xw", P), ("track_depth", P), ("n_edges", i32), ("e_point", P),
+        ("e_kf", P), ("e_kind", P), ("e_obs", P), ("e_inv_sigma2", P), ("n_links", i32), ("links", P),
+        ("iterations", i32), ("large", i32), ("lambda_init", f64),
+    ]
+
+
+class OsgLocalInertialBaResult(C.Structure):
+    _fields_ = [
+        ("state", P), ("Rcw", P), ("tcw", P), ("xw", P), ("edge_bad", P), ("edge_chi2", P), ("chi2_initial", f64),
+        ("chi2_last", f64), ("chi2_accepted", f64), ("iterations", i32), ("trials_rejected", i32),
+        ("solve_failed", i32), ("failed", i32), ("trace", P),
+    ]
+
+
+OSG_LIBA_MAX_FREE_KF = 32
+OSG_LIBA_MAX_FIXED_KF = 512
+OSG_LIBA_MAX_POINTS = 65536
+OSG_LIBA_MAX_EDGES = 524288
+OSG_LIBA_MAX_PAIRS = 16777216
+OSG_LIBA_MAX_ITERATIONS = 100
+
+
 class OsgSim3Problem(C.Structure):
     _fields_ = [
         ("q", f64 * 4), ("t", f64 * 3), ("s", f64), ("fix_scale", i32), ("th2", f32),
@@ -433,6 +465,7 @@ EXPORTS = [
     "osg_pose_inertial_optimization", "osg_pose_inertial_optimization_batch", "osg_pose_inertial_check",
     "osg_pose_inertial_informations",
     "osg_inertial_optimization", "osg_inertial_optimization_batch", "osg_inertial_check",
+    "osg_local_inertial_ba", "osg_local_inertial_ba_batch", "osg_local_inertial_ba_check",
     "osg_sim3_ransac", "osg_sim3_ransac_batch", "osg_sim3_ransac_iterations",
     "osg_mlpnp_ransac", "osg_mlpnp_ransac_batch", "osg_mlpnp_ransac_parameters", "osg_mlpnp_check_samples",
     "osg_optimize_essential_graph", "osg_essgraph_correct_points", "osg_essgraph_kernel_times",
@@ -519,6 +552,11 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.osg_inertial_optimization_batch.argtypes = [vp, C.POINTER(OsgInertialProblem), i32,
                                                     C.POINTER(OsgInertialResult)]
     lib.osg_inertial_check.argtypes = [C.POINTER(OsgInertialProblem)]
+    lib.osg_local_inertial_ba.argtypes = [vp, C.POINTER(OsgLocalInertialBaProblem),
+                                          C.POINTER(OsgLocalInertialBaResult)]
+    lib.osg_local_inertial_ba_batch.argtypes = [vp, C.POINTER(OsgLocalInertialBaProblem), i32,
+                                                C.POINTER(OsgLocalInertialBaResult)]
+    lib.osg_local_inertial_ba_check.argtypes = [C.POINTER(OsgLocalInertialBaProblem)]
     lib.osg_imu_preintegrate.argtypes = [vp, C.POINTER(OsgImuProblem), C.POINTER(OsgImuPreintegrated)]
     lib.osg_imu_preintegrate_batch.argtypes = [vp, C.POINTER(OsgImuProblem), i32, C.POINTER(OsgImuPreintegrated)]
     lib.osg_imu_preintegrate_check.argtypes = [C.POINTER(OsgImuProblem)]

@@ -497,6 +497,13 @@ class Optimizer:
         out = run_inertial(self.ctx, [problems] if single else list(problems))
         return out[0] if single else out
 
+    def LocalInertialBA(self, problems):
+        """``Optimizer::LocalInertialBA`` (ref:src/Optimizer.cc:2221-2816), its g2o part, for one
+        LocalInertialBAProblem or a list of them (one launch, a workgroup per window)."""
+        single = isinstance(problems, LocalInertialBAProblem)
+        out = run_local_inertial_ba(self.ctx, [problems] if single else list(problems))
+        return out[0] if single else out
+
     def OptimizeSim3(self, problems):
         """``Optimizer::OptimizeSim3`` (ref:src/Optimizer.cc:4213-4512) for one Sim3Problem or a list of
         them (one launch, a workgroup per problem).  The caller nulls ``vpMatches1`` where ``pair_state``
@@ -1799,3 +1806,256 @@ def _so3f_exp_matrix(w):
     tyy, tyz, tzz = ty * y, tz * y, tz * z
     return np.array([[1 - (tyy + tzz), txy - twz, txz + twy], [txy + twz, 1 - (txx + tzz), tyz - twx],
                      [txz - twy, tyz + twx, 1 - (txx + tyy)]], f)
+
+
+# ------------------------------------------------------------------------------------- LocalInertialBA
+@dataclass
+class LibaKeyFrame:
+    """One KeyFrame of a LocalInertialBA window: its four vertices and ``ImuCamPose(KeyFrame*)``'s cameras."""
+    state: ImuState
+    cams: list                # one or two ImuCamera
+    bf: float
+    fixed: bool = False
+
+
+@dataclass
+class LibaLink:
+    """EdgeInertial + EdgeGyroRW + EdgeAccRW between ``prev`` (mPrevKF) and ``cur``."""
+    prev: int
+    cur: int
+    preint: Preintegrated
+    huber: bool = False       # i == N - 1 || bRecInit
+    downweight: bool = False  # i == N - 1
+
+
+@dataclass
+class LocalInertialBAProblem:
+    """One ``osg_local_inertial_ba_problem`` (include/osg_ba.h): the g2o part of ``Optimizer::LocalInertialBA``
+    (ref:src/Optimizer.cc:2356-2743) as arrays, in the reference's insertion order."""
+    kfs: list                 # LibaKeyFrame
+    xw: np.ndarray            # n_points x 3 double
+    track_depth: np.ndarray   # float32 per point
+    e_point: np.ndarray       # int32 per visual edge
+    e_kf: np.ndarray
+    e_kind: np.ndarray        # int8: EDGE_MONO (EdgeMono(0)), EDGE_STEREO, EDGE_BODY (EdgeMono(1))
+    e_obs: np.ndarray         # n_edges x 3 double
+    e_inv_sigma2: np.ndarray  # float32
+    links: list               # LibaLink
+    iterations: int = 10
+    large: bool = False
+    lambda_init: float = 1.0
+    truth: object = None      # generator only: (list of ImuState, n_points x 3)
+
+    def __post_init__(self):
+        self.xw = np.ascontiguousarray(self.xw, np.float64).reshape(-1, 3)
+        self.track_depth = np.ascontiguousarray(self.track_depth, np.float32).reshape(-1)
+        self.e_point = np.ascontiguousarray(self.e_point, np.int32).reshape(-1)
+        self.e_kf = np.ascontiguousarray(self.e_kf, np.int32).reshape(-1)
+        self.e_kind = np.ascontiguousarray(self.e_kind, np.int8).reshape(-1)
+        self.e_obs = np.ascontiguousarray(self.e_obs, np.float64).reshape(-1, 3)
+        self.e_inv_sigma2 = np.ascontiguousarray(self.e_inv_sigma2, np.float32).reshape(-1)
+
+    @property
+    def n_kf(self):
+        return len(self.kfs)
+
+    @property
+    def n_points(self):
+        return len(self.xw)
+
+    @property
+    def n_edges(self):
+        return len(self.e_point)
+
+    def struct(self, keep):
+        """The C struct; ``keep`` collects the objects whose memory it points into."""
+        st = _abi.OsgLocalInertialBaProblem()
+        kf = (_abi.OsgLibaKeyframe * max(1, self.n_kf))()
+        for d, k in zip(kf, self.kfs):
+            k.state.fill(d.state)
+            d.fixed, d.n_cams, d.bf = int(bool(k.fixed)), len(k.cams), float(k.bf)
+            for c, m in zip(d.cams, k.cams):
+                c.cam = m.cam
+                for name in ("Rcw", "tcw", "Rcb", "tcb", "tbc"):
+                    getattr(c, name)[:] = np.asarray(getattr(m, name), np.float64).ravel().tolist()
+        ln = (_abi.OsgLibaLink * max(1, len(self.links)))()
+        for d, l in zip(ln, self.links):
+            d.prev, d.cur, d.huber, d.downweight = int(l.prev), int(l.cur), int(bool(l.huber)), int(bool(l.downweight))
+            q = l.preint
+            for name in ("dR", "dV", "dP", "JRg", "JVg", "JVa", "JPg", "JPa", "b", "C"):
+                getattr(d.preint, name)[:] = np.asarray(getattr(q, name), np.float32).ravel().tolist()
+            d.preint.dT = float(q.dT)
+        keep.extend([kf, ln])
+        st.n_kf, st.kf = self.n_kf, C.addressof(kf)
+        st.n_points, st.xw, st.track_depth = self.n_points, _p(self.xw), _p(self.track_depth)
+        st.n_edges, st.e_point, st.e_kf, st.e_kind = self.n_edges, _p(self.e_point), _p(self.e_kf), _p(self.e_kind)
+        st.e_obs, st.e_inv_sigma2 = _p(self.e_obs), _p(self.e_inv_sigma2)
+        st.n_links, st.links = len(self.links), C.addressof(ln)
+        st.iterations, st.large, st.lambda_init = int(self.iterations), int(bool(self.large)), float(self.lambda_init)
+        return st
+
+
+@dataclass
+class LocalInertialBAResult:
+    states: list              # ImuState per KeyFrame
+    Rcw: np.ndarray           # n_kf x 3 x 3: camera 0, for SetPose
+    tcw: np.ndarray           # n_kf x 3
+    xw: np.ndarray            # n_points x 3
+    edge_bad: np.ndarray      # the function's erase rule per visual edge
+    edge_chi2: np.ndarray
+    chi2_initial: float       # err
+    chi2_last: float          # err_end
+    chi2_accepted: float
+    iterations: int
+    trials_rejected: int
+    solve_failed: bool
+    failed: bool              # the reference returns before any write
+    trace: np.ndarray         # iterations x (chi2, lambda, trials)
+
+
+def local_inertial_ba_check(problem) -> int:
+    """``osg_local_inertial_ba_check``: 0 or OSG_E_INVALID (host only, no context)."""
+    from . import load_library
+
+    keep = []
+    st = problem.struct(keep)
+    return load_library().osg_local_inertial_ba_check(C.byref(st))
+
+
+def run_local_inertial_ba(ctx, probs):
+    nb = len(probs)
+    keep = []
+    ps = (_abi.OsgLocalInertialBaProblem * max(1, nb))(*[q.struct(keep) for q in probs])
+    rs = (_abi.OsgLocalInertialBaResult * max(1, nb))()
+    bufs = []
+    for r, q in zip(rs, probs):
+        b = dict(state=(_abi.OsgPioState * max(1, q.n_kf))(), Rcw=np.zeros((q.n_kf, 3, 3)), tcw=np.zeros((q.n_kf, 3)),
+                 xw=np.zeros((q.n_points, 3)), bad=np.zeros(q.n_edges, np.uint8), chi2=np.zeros(q.n_edges),
+                 trace=np.zeros((max(1, q.iterations), 3)))
+        r.state, r.Rcw, r.tcw, r.xw = C.addressof(b["state"]), _p(b["Rcw"]), _p(b["tcw"]), _p(b["xw"])
+        r.edge_bad, r.edge_chi2, r.trace = _p(b["bad"]), _p(b["chi2"]), _p(b["trace"])
+        bufs.append(b)
+    ctx.check(ctx.lib.osg_local_inertial_ba_batch(ctx.handle, ps, nb, rs), "LocalInertialBA")
+    return [LocalInertialBAResult([ImuState.of(s) for s in b["state"][:q.n_kf]], b["Rcw"], b["tcw"], b["xw"], b["bad"],
+                                  b["chi2"], r.chi2_initial, r.chi2_last, r.chi2_accepted, r.iterations,
+                                  r.trials_rejected, bool(r.solve_failed), bool(r.failed),
+                                  b["trace"][:r.iterations].copy())
+            for r, q, b in zip(rs[:nb], probs, bufs)]
+
+
+def synth_local_inertial_window(rng, truth, preints, n_points=100, cam="pinhole_mono", n_extra_fixed=0, large=False,
+                                rec_init=False, iterations=None, outlier_frac=0.05, pixel_noise=1.0,
+                                pose_err=(0.2, 0.01), vel_err=0.02, point_err=0.02, linkless=False, n_seen_once=1,
+                                n_fixed_only=1, p_obs=0.8, n_levels=8, wide_point=False):
+    """A LocalInertialBA window around a given trajectory.  ``truth``: the true ImuState of the chain, oldest first;
+    ``truth[0]`` is the fixed KeyFrame before the window and the rest are free.  ``preints[i]`` is the
+    preintegration from ``truth[i]`` to ``truth[i + 1]``.  KeyFrames are numbered as the reference visits them:
+    the free ones from the newest (0) to the oldest (N - 1), the fixed predecessor (N), then ``n_extra_fixed``
+    covisible fixed KeyFrames around the trajectory.  Link i joins free KeyFrame i to KeyFrame i + 1; the oldest
+    one is downweighted and robust, all are robust under ``rec_init``; ``linkless`` drops the newest one's.
+    ``cam``: "pinhole_mono", "pinhole_stereo" or "kb8_rig" (left and right observations, the right ones EdgeMono(1)).
+    Points are seen by each KeyFrame in view with probability ``p_obs`` (``wide_point``: point 0 by all of them);
+    ``n_seen_once`` points keep one observation and ``n_fixed_only`` points only those of fixed KeyFrames.
+    Observations carry pixel noise and a share of outliers; free poses, velocities and points are perturbed."""
+    N = len(truth) - 1
+    if N < 1 or len(preints) != N:
+        raise ValueError("truth holds the fixed predecessor and the free KeyFrames; one preintegration per step")
+    rig, stereo = cam == "kb8_rig", cam == "pinhole_stereo"
+    model = kb8_camera() if rig else pinhole_camera()
+    bf = 0.0 if rig else float(np.float32(EUROC_BF))
+    Rcb0, tcb0, tbc0 = _f32(_TBC_R.T), _f32(-_TBC_R.T @ _TBC_T), _f32(_TBC_T)
+    ext = [(Rcb0, tcb0, tbc0)]
+    if rig:
+        q = np.array(TUMVI_TRL[:4]) / np.linalg.norm(TUMVI_TRL[:4])
+        Rrl, trl = _f32(quat_to_rot(q)), _f32(TUMVI_TRL[4:])
+        Rcb1 = Rrl @ Rcb0
+        tcb1 = Rrl @ tcb0 + trl
+        ext.append((Rcb1, tcb1, -Rcb1.T @ tcb1))
+
+    def cam_pose(S, e):
+        Rbw = S.Rwb.T
+        return e[0] @ Rbw, e[0] @ (-Rbw @ S.twb) + e[1]
+
+    order = list(range(N, 0, -1)) + [0]              # KeyFrame index -> position in truth
+    true_states = [truth[i] for i in order]
+    for _ in range(n_extra_fixed):
+        a = true_states[int(rng.integers(0, N + 1))]
+        true_states.append(ImuState(_orthonormal(a.Rwb @ small_rotation(rng, 4.0)), a.twb + rng.normal(0, 0.15, 3),
+                                    np.zeros(3), np.zeros(3), np.zeros(3)))
+    nk = len(true_states)
+    fixed = [k >= N for k in range(nk)]
+    # points: in view of a random KeyFrame's left camera
+    W, Hh = (512, 512) if rig else (EUROC_W, EUROC_H)
+    Xw = np.zeros((n_points, 3))
+    for p in range(n_points):
+        Rc, tc = cam_pose(true_states[int(rng.integers(0, nk))], ext[0])
+        z = rng.uniform(2.0, 9.0) if rng.random() < 0.5 else rng.uniform(11.0, 25.0)
+        if rig:
+            th, ps = rng.uniform(0.05, 0.9), rng.uniform(-np.pi, np.pi)
+            Xc = z * np.array([np.sin(th) * np.cos(ps), np.sin(th) * np.sin(ps), np.cos(th)])
+        else:
+            u, v = rng.uniform(60, W - 60), rng.uniform(60, Hh - 60)
+            Xc = np.array([(u - EUROC_CX) / EUROC_FX * z, (v - EUROC_CY) / EUROC_FY * z, z])
+        Xw[p] = Rc.T @ (Xc - tc)
+    if wide_point:                                   # far away on the optical axis of the middle KeyFrame
+        Rc, tc = cam_pose(true_states[N // 2], ext[0])
+        Xw[0] = Rc.T @ (np.array([0.0, 0.0, 20.0]) - tc)
+    sig2 = inv_level_sigma2(n_levels)
+    p_octave = np.array([1.2 ** -i for i in range(n_levels)]) / sum(1.2 ** -i for i in range(n_levels))
+    e_point, e_kf, e_kind, e_obs, e_w = [], [], [], [], []
+    depth0 = np.zeros(n_points)
+    for p in range(n_points):
+        seen = []
+        for k in range(nk):
+            for ci in range(len(ext)):
+                Rc, tc = cam_pose(true_states[k], ext[ci])
+                Xc = Rc @ Xw[p] + tc
+                if Xc[2] < 0.5:
+                    continue
+                uv = _project(model, Xc[None])[0]
+                if not (5 < uv[0] < W - 5 and 5 < uv[1] < Hh - 5):
+                    continue
+                if k == 0 and ci == 0:
+                    depth0[p] = Xc[2]
+                if not (wide_point and p == 0 and ci == 0) and rng.random() > p_obs:
+                    continue
+                seen.append((k, ci, uv, Xc[2]))
+        q = p - (1 if wide_point else 0)             # the special points come after the wide one
+        if 0 <= q < n_seen_once:
+            seen = seen[:1]
+        elif n_seen_once <= q < n_seen_once + n_fixed_only:
+            seen = [s for s in seen if fixed[s[0]]]
+        for k, ci, uv, z in seen:
+            octv = int(rng.choice(n_levels, p=p_octave))
+            o = np.zeros(3)
+            o[:2] = uv + rng.normal(0, pixel_noise, 2) * 1.2 ** octv
+            if rng.random() < outlier_frac:
+                o[:2] += rng.uniform(8, 40, 2) * rng.choice([-1, 1], 2)
+            kind = _abi.EDGE_BODY if ci == 1 else _abi.EDGE_MONO
+            if stereo and z < 12.0:
+                kind = _abi.EDGE_STEREO
+                o[2] = o[0] - bf / z + rng.normal(0, 0.5 * pixel_noise)
+            e_point.append(p), e_kf.append(k), e_kind.append(kind), e_obs.append(_f32(o)), e_w.append(sig2[octv])
+    depth = np.where(depth0 > 0, depth0, rng.uniform(3.0, 20.0, n_points))
+    # the estimates the window starts from
+    kfs = []
+    for k, S in enumerate(true_states):
+        if fixed[k]:
+            est = ImuState(_f32(S.Rwb), _f32(S.twb), _f32(S.v), _f32(S.bg), _f32(S.ba))
+        else:
+            est = ImuState(_f32(_orthonormal(S.Rwb @ small_rotation(rng, pose_err[0]))),
+                           _f32(S.twb + rng.normal(0, pose_err[1], 3)), _f32(S.v + rng.normal(0, vel_err, 3)),
+                           _f32(S.bg), _f32(S.ba))
+        cams = []
+        for e in ext:
+            Rc, tc = cam_pose(est, e)
+            cams.append(ImuCamera(model, _f32(Rc), _f32(tc), e[0], e[1], e[2]))
+        kfs.append(LibaKeyFrame(est, cams, bf, fixed[k]))
+    links = [LibaLink(i + 1, i, preints[N - 1 - i], huber=(i == N - 1 or rec_init), downweight=(i == N - 1))
+             for i in range(N) if not (linkless and i == 0)]
+    X0 = _f32(Xw + rng.normal(0, point_err, Xw.shape))
+    if iterations is None:
+        iterations = 4 if large else 10
+    return LocalInertialBAProblem(kfs, X0, depth.astype(np.float32), e_point, e_kf, e_kind,
+                                  np.array(e_obs).reshape(-1, 3), np.array(e_w, np.float32), links, iterations, large,
+                                  1e-2 if large else 1.0, truth=(true_states, Xw))
